@@ -3,7 +3,16 @@
 bench.py -- env-steps/sec of the MI355X-native stepper on BASELINE.json's metric:
 "env-steps/sec whole node, 65 536 QQubeSwingUpSim envs, random policy".
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (plus the roofline of the dominant kernel where
+the timed region itself measures it).  --full adds everything else the line can carry: the CPU baseline, three repeats of
+the timed region, and the roofline legs that take runs of their own (bandwidth probes, full records, pack_traj, the
+16.7 M-env point, the in-kernel policy, BASELINE configs 2-5; in step mode the kernel time itself).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all; a
+fixed, seeded sample of the env lanes where the full arrays would be larger), so that two builds can be compared output
+for output: with the same arguments the inputs are the same from run to run.
 
 With --gpus N > 1 the command starts its own N ranks (one process per GPU, `python -m torch.distributed.run`, RCCL) and
 relays rank 0's JSON line -- like the reference's sampler, which owns its worker pool (P/sampling/sampler_pool.py:98-116,
@@ -21,9 +30,9 @@ the only collective is an RCCL all-gather of completed-episode return statistics
 The records of consecutive launches rotate through a buffer of more than 1 GiB (several times the 256 MiB Infinity Cache),
 so the record stream is a real HBM stream.
 
-The JSON line also carries the roofline of the dominant kernel (HIP-event timed on the kernel's stream), the single-step
-kernel at 16.7 M envs (the HBM-bound point), the full-record (record mode 2) rate, and the CPU baseline (the oracle's NumPy
-port timed on this box's host cores, bounded sample).
+The JSON line also carries the roofline of the dominant kernel (HIP-event timed on the kernel's stream) and, with --full,
+the single-step kernel at 16.7 M envs (the HBM-bound point), the full-record (record mode 2) rate, and the CPU baseline
+(the oracle's NumPy port timed on the host cores granted to the job, bounded sample).
 
 BENCH_REHEARSAL=1: every rank on GPU 0 with the gloo backend (a one-GPU rehearsal of the multi-rank path).
 BENCH_DRYRUN=1: no device work at all -- only the launch / rendezvous / collective / relay plumbing (CPU tests).
@@ -227,7 +236,7 @@ def launch_ranks(n, args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL needs on this pool
     env.setdefault("OMP_NUM_THREADS", "1")
     tmp = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         base = cpu_baseline(args.env, min(args.envs, 65536))
         base["timed_by"] = "launcher parent, before the ranks were started"
         fd, tmp = tempfile.mkstemp(prefix="bench_cpu_baseline_", suffix=".json")
@@ -258,10 +267,65 @@ def parse_args():
     ap.add_argument("--graph", type=int, default=0, help="step mode: capture `chunk` policy+step iterations in one hipGraph")
     ap.add_argument("--lean-step", type=int, default=0, help="step mode: vs_set_lean_step (no running return, no failed byte: the "
                     "117-B model of SURVEY 8(d) exactly; episode returns then read 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the large-N / full-record / probe legs (quick sweeps)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, the repeats of the timed region and the "
+                    "roofline legs that take runs of their own (off: set-up, warm-up, the timed steps and the line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the large-N / full-record / probe legs (quick sweeps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     ap.add_argument("--seed", type=int, default=0)
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64 * 2 ** 20
+DUMP_ENV_LANES = 65536       # per-env buffers: every env up to this many, else a seeded sample of this many
+DUMP_RECORD_BYTES = 32 * 2 ** 20  # records of the last launch: the lanes sampled so that they stay below this
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, env, chunk, last_rows=None):
+    """What a caller of the timed path receives from its last step, as host arrays in DIR/<name>.npy: the per-env buffers
+    (state, obs, rew, done, the episode accumulators) and, after a recording fused launch, that launch's records
+    [chunk, lanes, width] with their done flags.  Where the full arrays would pass DUMP_BYTES_MAX, a fixed, seeded sample
+    of the env lanes is kept (its indices in env_lanes.npy / record_lanes.npy)."""
+    import torch
+
+    from simurlacra_amd import _lib as L
+
+    env.sync()
+    torch.cuda.synchronize()
+    n = env.n_envs
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(k):
+        return np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+    lanes = sample(DUMP_ENV_LANES)
+    out = {"env_lanes": lanes.astype(np.float64)}
+    for name, which in (("state", L.VS_STATE), ("obs", L.VS_OBS), ("rew", L.VS_REW), ("done", L.VS_DONE)):
+        out[name] = env.get(which)[lanes].astype(np.float32)
+    for name, which in (("episode_count", L.VS_EPSTAT_COUNT), ("episode_return_sum", L.VS_EPSTAT_RETSUM),
+                        ("episode_length_sum", L.VS_EPSTAT_LENSUM)):
+        out[name] = env.get(which)[lanes].astype(np.float64)
+    if last_rows is not None:
+        planes, words = env.traj_planes()
+        F = env.traj_layout()[0]
+        k = max(1, min(n, DUMP_RECORD_BYTES // (chunk * (F + 1) * 4)))
+        rl = sample(k)
+        lane_t = torch.as_tensor(rl, device=words.device)
+        rec = torch.cat([p[last_rows:last_rows + chunk][:, lane_t] for p, _ in planes], dim=2)  # [chunk, k, F]
+        t = torch.arange(last_rows, last_rows + chunk, device=words.device)
+        done = (words[:, lane_t][t // 32] >> (t % 32).to(torch.int32)[:, None]) & 1  # bit t % 32 of word t // 32
+        rec, done = rec.cpu().numpy(), done.cpu().numpy().astype(np.float32)
+        out["record_lanes"] = rl.astype(np.float64)
+        for name, (c0, w) in env.record_fields().items():
+            out["record_" + name] = np.ascontiguousarray(rec[..., c0] if name == "rew" else rec[..., c0:c0 + w])
+        out["record_done"] = done
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES_MAX, f"outputs of {total} bytes exceed {DUMP_BYTES_MAX}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def measure(args, rank, world, local_rank, dist, rehearsal):
@@ -362,7 +426,12 @@ def measure(args, rank, world, local_rank, dist, rehearsal):
         run(preroll)
     run(max(args.warmup, 1))
     el = timed(steps)  # THE timed region: exactly `steps` launches between two barriers + synchronisations
-    repeats = [timed(steps) for _ in range(3)]  # untimed by the contract: run-to-run spread of the same region
+    if args.dump_outputs and rank == 0:
+        # the last timed launch wrote record slot (launches - 1) % slots
+        last_rows = ((launches[0] - 1) % slots) * chunk if args.mode == "fused" and args.record else None
+        dump_outputs(args.dump_outputs, env, chunk, last_rows)
+    # --full: run-to-run spread of the same region (untimed by the contract)
+    repeats = [timed(steps) for _ in range(3)] if args.full else []
     cnt_t, rs_t, ls_t = (env.tensor(w)[0, :n] for w in (L.VS_EPSTAT_COUNT, L.VS_EPSTAT_RETSUM, L.VS_EPSTAT_LENSUM))
     return dict(env=env, el=el, repeats=repeats, stats=(cnt_t, rs_t, ls_t), slots=slots, graph=graph is not None, preroll=preroll,
                 kernel_ms_timed_region=(ev_ms[0] / steps) if ev_ms else None,
@@ -388,7 +457,7 @@ def main():
     # ranks, else timed by rank 0 right here -- before its first HIP call (forked workers) and before the rendezvous, the
     # other ranks wait for it in init_process_group
     cpu_base = None
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         handed = os.environ.get("BENCH_CPU_BASELINE_JSON")
         if handed and os.path.exists(handed):
             cpu_base = json.load(open(handed))
@@ -461,7 +530,7 @@ def main():
             "ms_per_step": el / steps * 1e3, "env_steps_per_step": per_step, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "timed_region_s": el,
-            "repeat_ms_per_step": [r / steps * 1e3 for r in m["repeats"]],
+            "repeat_ms_per_step": [r / steps * 1e3 for r in m["repeats"]],  # (--full only)
             # evidence of the multi-rank path: how many ranks answered the all-gathers, what the return gather cost
             "ranks_seen": int(ep["per_rank"].shape[0]), "collective_ms": collective_ms,
             "collective": ("none (single rank)" if world == 1 else
@@ -481,7 +550,7 @@ def main():
         }
         if dryrun:
             out["dry_run"] = True
-        else:
+        elif args.full or m.get("kernel_ms_timed_region"):  # (a plain run: only what the timed region measured)
             out["roofline"] = roofline(args, env, local_rank, d, n, chunk, m.get("kernel_ms_timed_region"))
             out["roofline"]["kernel_ms_repeats"] = m.get("kernel_ms_repeats")
         out["cpu_baseline"] = cpu_base
@@ -667,8 +736,8 @@ def roofline(args, env, local_rank, d, n, chunk, ms_region=None):
             roof["traffic"], roof["traffic_source"] = tab[key]["traffic_bytes_per_launch"], os.path.basename(tf)
     except Exception:
         pass
-    if args.no_extras or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return roof  # the reference points and the extra legs are measured at N = 1 only: the other ranks would wait
+    if not args.full or args.no_extras or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return roof  # the reference points and the extra legs: --full, at N = 1 only (the other ranks would wait)
     # the practical HBM ceiling next to the nominal one -- in-repo float4 copy / fill kernels (1 GiB per pass,
     # far beyond the caches, 4 independent 16-B accesses per thread, non-temporal), timed with HIP events
     g = ctypes.c_float()

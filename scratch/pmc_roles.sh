@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for lib in simurlacra_amd/csrc/libvecsim.so scratch/libvecsim_NOC.so scratch/libvecsim_NOP.so; do
   for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_TRANS"; do
     OUT=gpurun_out/pmcr; rm -rf $OUT; mkdir -p $OUT
-    VS_LIB_PATH=$PWD/$lib rocprofv3 --pmc $set --output-format csv -d $OUT -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 > /dev/null 2> $OUT/err.txt || { echo "$lib [$set] failed: $(tail -2 $OUT/err.txt)"; continue; }
+    VS_LIB_PATH=$PWD/$lib rocprofv3 --pmc $set --output-format csv -d $OUT -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 > /dev/null 2> $OUT/err.txt || { echo "$lib [$set] failed: $(tail -2 $OUT/err.txt)"; continue; }
     python3 - <<PY
 import csv, glob, collections
 tot = collections.defaultdict(float); n = collections.defaultdict(int)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the tables of profiles/r03_* from the final library, one box: default bench line, BASELINE configs, families, sampler, pack
 OUT=gpurun_out/$1; mkdir -p $OUT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
 tail -c 300 $OUT/bench_default.json; echo
 bash scratch/r2_configs.sh > $OUT/configs.txt 2>&1 || exit 1
 bash scratch/r3/cfg.sh > $OUT/cfg.txt 2>&1 || exit 1

@@ -61,7 +61,7 @@ fetch, write, sq1, sq2 = collect("fetch"), collect("write"), collect("sq1"), col
 from simurlacra_amd import _lib as L
 
 res = {"lib_version": int(L.load().vs_version()),
-       "command": "rocprofv3 --pmc <counters> -- python3 bench.py --no-cpu-baseline --steps 200 --warmup 20 (BENCH_PREROLL=50), one pass per "
+       "command": "rocprofv3 --pmc <counters> -- python3 bench.py --full --no-cpu-baseline --steps 200 --warmup 20 (BENCH_PREROLL=50), one pass per "
                   "counter group: FETCH_SIZE | WRITE_SIZE | SQ group 1 | SQ group 2; averages per dispatch of the leg's kernel",
        "units": "FETCH/WRITE_SIZE in KB (FETCH doubled in fetch_bytes_corrected); SQ *_CYCLES / ACTIVE_INST_* / WAIT_* in quad-cycles "
                 "summed over all waves (or SIMDs for BUSY_CYCLES) of the chip"}

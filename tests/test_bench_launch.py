@@ -26,7 +26,7 @@ def run_bench(*argv, env_extra=None, timeout=300):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_bench_launches_its_own_ranks(n):
-    d = run_bench("--gpus", str(n), "--steps", "3", "--warmup", "1")
+    d = run_bench("--gpus", str(n), "--steps", "3", "--warmup", "1", "--full")
     assert d["dry_run"] is True and d["value"] is None
     assert d["n_gpus"] == n and d["ranks_seen"] == n  # as many ranks answered the all-gather as were asked for
     assert len(d["per_rank_env_steps_per_s"]) == n
@@ -42,9 +42,18 @@ def test_bench_launches_its_own_ranks(n):
 
 
 def test_bench_single_rank_needs_no_launcher():
-    d = run_bench("--steps", "2", "--warmup", "1")
+    d = run_bench("--steps", "2", "--warmup", "1", "--full")
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["collective"].startswith("none")
     assert d["cpu_baseline"]["timed_by"].startswith("rank 0") and "preroll" in d
+
+
+def test_plain_bench_run_is_lean():
+    """without --full the line carries the headline only: no CPU baseline is timed, the timed region is not repeated"""
+    for argv in (("--steps", "2", "--warmup", "1"), ("--gpus", "2", "--steps", "2", "--warmup", "1")):
+        d = run_bench(*argv)
+        assert d["cpu_baseline"] is None and "vs_cpu_baseline" not in d and d["repeat_ms_per_step"] == []
+        assert d["steps"] == 2 and d["warmup"] == 1 and "ms_per_step" in d
+        assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
 
 
 def test_bench_as_a_rank_of_an_external_launcher():
@@ -57,7 +66,7 @@ def test_bench_as_a_rank_of_an_external_launcher():
     env = dict(os.environ, BENCH_DRYRUN="1", OMP_NUM_THREADS="1", **SMALL_CPU_SAMPLE)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -75,3 +84,38 @@ def test_usable_cores_and_byte_models():
     assert bench.bytes_single_step(qq) == 117
     assert abs(bench.bytes_fused_step(qq, 100, 1) - (32.125 + 113 / 100)) < 1e-9
     assert abs(bench.bytes_fused_step(qq, 100, 2) - (52.125 + 113 / 100)) < 1e-9
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs: the last timed launch's records (a seeded lane sample) and the per-env buffers, float32 / float64,
+    at most 64 MB, the same from run to run with the same arguments"""
+    import numpy as np
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    line = run(a)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["cpu_baseline"] is None
+    assert "large_n" not in line["roofline"] and "configs" not in line["roofline"]  # (the legs of --full)
+    run(b)
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert {"state.npy", "obs.npy", "rew.npy", "done.npy", "record_obs.npy", "record_act.npy", "record_rew.npy",
+            "record_done.npy"} <= set(names)
+    total = 0
+    for name in names:
+        x, y = np.load(a / name), np.load(b / name)
+        assert x.dtype in (np.float32, np.float64), name
+        total += x.nbytes
+        assert np.array_equal(x, y, equal_nan=True), name
+    assert total <= 64 * 2 ** 20
+    n_lanes = np.load(a / "record_lanes.npy").size
+    assert np.load(a / "record_obs.npy").shape == (400, n_lanes, 6) and np.load(a / "record_rew.npy").shape == (400, n_lanes)
+    assert np.load(a / "state.npy").shape == (65536, 4)

@@ -310,14 +310,15 @@ def test_shard_layout():
 
 
 def test_register_with_pyrado_when_the_reference_is_importable():
-    """build container only: with the reference importable (stub harness of SURVEY 8(c)), the env classes of this
-    package satisfy Pyrado's own isinstance checks after register_with_pyrado()"""
+    """with the reference importable (stub harness of SURVEY 8(c)), the env classes of this package satisfy Pyrado's own
+    isinstance checks after register_with_pyrado().  The reference is not part of this repository: PYRADO_SRC names a
+    Pyrado source tree (the directory holding the `pyrado` package)."""
     import sys
     import types
 
-    ref = "/root/reference/Pyrado"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present (GPU box)")
+    ref = os.environ.get("PYRADO_SRC", "")
+    if not os.path.isdir(os.path.join(ref, "pyrado")):
+        pytest.skip("the reference is not available: set PYRADO_SRC to a Pyrado source tree")
     saved = dict(sys.modules)
     saved_path = list(sys.path)
     try:
