@@ -90,7 +90,12 @@ enum vs_buffer {
     VS_JAC_STATE = 22,     /* f32 [S][S+A][ld]  d s'_j / d (s, a)_k of the last vs_step_jac */
     VS_JAC_REW = 23,       /* f32 [S+A][ld]     d r / d (s, a)_k */
     VS_JAC_OBS = 24,       /* f32 [O][S+A][ld]  d obs'_j / d (s, a)_k */
-    VS_BUFFER_COUNT = 25
+    VS_POLICY_HIDDEN = 25,     /* f32 [Hp][ld]  running hidden state of the recurrent policy of vs_set_policy_rnn, packed like
+                                * Pyrado's: h of layer 0, 1 .. then (LSTM) c of layer 0, 1 .. (Hp = layers x hidden, x 2 for LSTM);
+                                * zeroed by vs_set_policy_rnn, by vs_reset (the reset lanes) and per lane at every auto-reset */
+    VS_POLICY_HIDDEN_REC = 26, /* f32 [T][W][ld] hidden-state record plane (vs_set_policy_hidden_record, W floats per env): row t =
+                                * the policy's hidden state BEFORE recorded step t; same rows as VS_TRAJ_REC (capacity, offset) */
+    VS_BUFFER_COUNT = 27
 };
 
 /* vs_task_cfg.flags */
@@ -156,6 +161,24 @@ typedef struct vs_fnn_desc {
     int32_t obs_idx[8];        /* ... and which (ObsPartialWrapper, P/environment_wrappers/observation_partial.py:36-75) */
     float noise_std[2];        /* exploration: + std * N(0, 1) per action dimension (NormalActNoiseExplStrat); 0 = none */
 } vs_fnn_desc;
+
+/* A recurrent policy for vs_step_policy: torch.nn.RNN / GRU / LSTM (bias, batch_first = False, no dropout / projection, one
+ * direction) and a Linear output layer -- RNNPolicy / GRUPolicy / LSTMPolicy of P/policies/recurrent/rnn.py. */
+#define VS_RNN_TANH 0  /* nn.RNN(nonlinearity='tanh') */
+#define VS_RNN_RELU 1  /* nn.RNN(nonlinearity='relu') */
+#define VS_RNN_GRU 2   /* nn.GRU, gates r, z, n */
+#define VS_RNN_LSTM 3  /* nn.LSTM, gates i, f, g, o */
+#define VS_RNN_MAX_LAYERS 2
+#define VS_RNN_MAX_HIDDEN 64
+typedef struct vs_rnn_desc {
+    int32_t cell;          /* VS_RNN_* */
+    int32_t n_layers;      /* 1 .. VS_RNN_MAX_LAYERS */
+    int32_t hidden;        /* units per layer, 1 .. VS_RNN_MAX_HIDDEN */
+    int32_t out_nonlin;    /* VS_NL_* of the output layer */
+    int32_t n_obs;         /* number of observation rows the policy sees; 0 = all of them, in order */
+    int32_t obs_idx[8];    /* ... and which (as vs_fnn_desc) */
+    float noise_std[2];    /* exploration: + std * N(0, 1) per action dimension (NormalActNoiseExplStrat); 0 = none */
+} vs_rnn_desc;
 
 typedef struct vs_env* vs_handle;
 
@@ -291,6 +314,20 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed);
  * run shape 0 whatever is asked).  No counterpart in the reference (which evaluates the torch module, P/sampling/rollout.py:203-219);
  * the shapes differ in the summation order of a layer only. */
 int vs_set_policy_shape(vs_handle h, int shape);
+/* vs_step_policy with a recurrent policy instead of a feed-forward one.  `params` is parameters_to_vector(policy.parameters())
+ * in torch order -- rnn_layers.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, [.. _l1], output_layer.weight, .bias --
+ * host or device memory, copied.  The hidden state of every lane is VS_POLICY_HIDDEN (zeroed here); per step and lane the
+ * kernel computes act, h' = policy(obs, h) with torch's cell equations, records, steps, and carries h' to the next step and
+ * launch.  desc == NULL removes the policy; setting one removes a network of vs_set_policy_fnn and the other way round.
+ * Refused like vs_set_policy_fnn (wrapper pipeline VS_ERR_STATE, discrete family / sizes / limits VS_ERR_ARG). */
+int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params, int64_t n_params);
+/* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
+ * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
+int vs_set_policy_hidden_record(vs_handle h, int width);
+/* the policy-in-the-loop counterpart: the caller's hidden state (device f32, element (env i, unit j) at
+ * hidden[i * env_stride + j * dim_stride], width units) into row `row` of VS_POLICY_HIDDEN_REC; row < 0: the device-side
+ * counter of vs_step_record, NOT advanced -- call it before the vs_step_record of the same step (captured graphs replay it) */
+int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64_t dim_stride, int row);
 /* The recorded steps of lanes 0 .. n_lanes - 1 (rows 0 .. of VS_TRAJ_REC, vs_set_record_mode's layout) as ROLLOUTS in one row-major
  * matrix rows[total + n_lanes][F] (F = vs_traj_layout's record width, device memory): rollout j = steps 0 .. lengths[j] - 1 of
  * lane j, the rollouts one after the other, starts[j] = lengths[0] + .. + lengths[j - 1] (both int64, device memory).

@@ -32,7 +32,8 @@ def __getattr__(name):
         from . import sampling
 
         return getattr(sampling, name)
-    if name in ("DummyPolicy", "IdlePolicy", "Policy", "FNN", "FNNPolicy", "NormalActNoiseExplStrat", "fnn_kernel_spec"):
+    if name in ("DummyPolicy", "IdlePolicy", "Policy", "FNN", "FNNPolicy", "NormalActNoiseExplStrat", "fnn_kernel_spec",
+                "RecurrentPolicy", "RNNPolicy", "GRUPolicy", "LSTMPolicy", "rnn_kernel_spec"):
         from . import policies
 
         return getattr(policies, name)

@@ -10,10 +10,13 @@ ENV_TYPES = {"omo": 0, "bob": 1, "qq-su": 2, "qcp-su": 3, "qbb": 4, "qq-st": 5, 
 (VS_STATE, VS_OBS, VS_REW, VS_DONE, VS_HIDDEN, VS_STEPCOUNT, VS_ERRFLAG, VS_RETURNS, VS_PARAMS, VS_CONSTS,
  VS_EP_RETURNS, VS_EP_LENGTHS, VS_EP_ENVIDX, VS_EP_COUNT, VS_TRAJ_REC, _VS_RESERVED_15, _VS_RESERVED_16, VS_TRAJ_DONE,
  VS_FAILED, VS_EPSTAT_COUNT, VS_EPSTAT_RETSUM, VS_EPSTAT_LENSUM, VS_JAC_STATE, VS_JAC_REW, VS_JAC_OBS) = range(25)
+VS_POLICY_HIDDEN, VS_POLICY_HIDDEN_REC = 25, 26  # the recurrent policy's running hidden state and its record plane
 VS_FLAG_SIMPLE_DYNAMICS, VS_FLAG_LONG_POLE, VS_FLAG_ACT_NORM, VS_FLAG_FREEZE_DONE, VS_FLAG_LEAN_STEP = 1, 2, 4, 8, 16
 RV_PLAIN, RV_WS256, RV_WS64, RV_WS64G, RV_WS256G = 0, 1, 2, 3, 4  # vs_rollout_variant
 VS_NL_NONE, VS_NL_TANH, VS_NL_RELU, VS_NL_SIGMOID = 0, 1, 2, 3  # vs_fnn_desc nonlinearities
 VS_FNN_MAX_HIDDEN, VS_FNN_MAX_WIDTH = 4, 64
+VS_RNN_TANH, VS_RNN_RELU, VS_RNN_GRU, VS_RNN_LSTM = 0, 1, 2, 3  # vs_rnn_desc cells
+VS_RNN_MAX_LAYERS, VS_RNN_MAX_HIDDEN = 2, 64
 VS_DP_NORMAL, VS_DP_UNIFORM, VS_DP_BERNOULLI = 0, 1, 2
 VS_MAX_ACT_DELAY = 64
 
@@ -33,6 +36,11 @@ class FnnDesc(C.Structure):
     _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * 4), ("hidden_nonlin", C.c_int32 * 4),
                 ("output_nonlin", C.c_int32), ("feat", C.c_int32), ("n_obs", C.c_int32), ("obs_idx", C.c_int32 * 8),
                 ("noise_std", C.c_float * 2)]
+
+
+class RnnDesc(C.Structure):
+    _fields_ = [("cell", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32), ("out_nonlin", C.c_int32),
+                ("n_obs", C.c_int32), ("obs_idx", C.c_int32 * 8), ("noise_std", C.c_float * 2)]
 
 
 _P = C.c_void_p
@@ -73,6 +81,9 @@ _SIGNATURES = {
     "vs_set_policy_fnn": (C.c_int, [_P, C.POINTER(FnnDesc), _P, C.c_int64]),
     "vs_step_policy": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64]),
     "vs_set_policy_shape": (C.c_int, [_P, C.c_int]),
+    "vs_set_policy_rnn": (C.c_int, [_P, C.POINTER(RnnDesc), _P, C.c_int64]),
+    "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
+    "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),
     "vs_rollout_lengths": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "vs_pack_traj": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vs_rollout_variant": (C.c_int, [_P]),

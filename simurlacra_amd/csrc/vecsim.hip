@@ -6,6 +6,23 @@ namespace vs {
 
 __global__ void k_bump_row(int* row) { *row += 1; }
 
+// vs_record_hidden: the caller's hidden state [i * es + j * ds] into row `row` (row < 0: the device-side counter) of the plane
+__global__ __launch_bounds__(256) void k_record_hidden(const float* __restrict__ src, long es, long ds, float* __restrict__ plane,
+                                                       const int* __restrict__ rec_row, int row, int rows, int width, size_t ld, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int r = row >= 0 ? row : *rec_row;
+    if (i >= n || r >= rows) return;
+    float* dst = plane + (size_t)r * width * ld + i;
+    for (int j = 0; j < width; ++j) dst[(size_t)j * ld] = src[(long)i * es + (long)j * ds];
+}
+
+// vs_reset with a mask: the recurrent policy's hidden state of the reset lanes
+__global__ __launch_bounds__(256) void k_zero_hidden(float* __restrict__ hid, int rows, size_t ld, const uint8_t* __restrict__ mask, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !mask[i]) return;
+    for (int j = 0; j < rows; ++j) hid[(size_t)j * ld + i] = 0.f;
+}
+
 // vs_rollout_lengths: per lane, the first recorded step whose done bit is set (words [t / 32][ld], bit t % 32)
 __global__ __launch_bounds__(256) void k_rollout_lengths(const uint32_t* __restrict__ words, size_t ld, int n, int t_steps,
                                                          long long* __restrict__ lengths, uint8_t* __restrict__ done_last) {
@@ -428,6 +445,9 @@ int vs_destroy(vs_handle h) {
     if (h->d_pbuf) (void)hipFree(h->d_pbuf);
     if (h->d_ring) (void)hipFree(h->d_ring);
     if (h->fnn.w) (void)hipFree((void*)h->fnn.w);
+    if (h->rnn.w) (void)hipFree((void*)h->rnn.w);
+    if (h->rnn.hid) (void)hipFree(h->rnn.hid);
+    if (h->d_hrec) (void)hipFree(h->d_hrec);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -616,6 +636,10 @@ int vs_reset(vs_handle h, const float* init_state, int64_t pitch, int full, cons
     rc = stage_mask(h, mask, &m);
     if (rc) return rc;
     DISPATCH_ENV(h->type, Launch<E>::reset(h, src, sp, full, m, seed));
+    if (h->rnn.hid) {  // a new rollout starts from init_hidden()
+        if (!m) HIPCHK(h, hipMemsetAsync(h->rnn.hid, 0, (size_t)h->rnn.hs * h->d.ld * sizeof(float), h->stream));
+        else hipLaunchKernelGGL(k_zero_hidden, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, h->rnn.hid, h->rnn.hs, (size_t)h->d.ld, m, h->d.n);
+    }
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }
@@ -711,6 +735,17 @@ int vs_step_jac(vs_handle h, const float* actions, int64_t env_stride, int64_t d
     return VS_OK;
 }
 
+// the hidden-state record plane: traj_cap rows of hrec_width floats per env (when both are set)
+static int alloc_hrec(vs_handle h) {
+    if (h->d_hrec) HIPCHK(h, hipFree(h->d_hrec));
+    h->d_hrec = nullptr;
+    if (h->hrec_width <= 0 || h->traj_cap <= 0) return VS_OK;
+    const size_t bytes = (size_t)h->traj_cap * h->hrec_width * h->d.ld * sizeof(float);
+    HIPCHK(h, hipMalloc((void**)&h->d_hrec, bytes));
+    HIPCHK(h, hipMemsetAsync(h->d_hrec, 0, bytes, h->stream));
+    return VS_OK;
+}
+
 // the record buffers of a superseded capacity / mode are released at once (a sampler that resizes per call must not grow)
 static int free_traj(vs_handle h) {
     Dev& d = h->d;
@@ -723,6 +758,8 @@ static int free_traj(vs_handle h) {
     }
     d.traj_rec = nullptr;
     d.traj_done = nullptr;
+    if (h->d_hrec) HIPCHK(h, hipFree(h->d_hrec));
+    h->d_hrec = nullptr;
     h->traj_cap = 0;
     d.traj_rows = 0;
     return VS_OK;
@@ -741,7 +778,7 @@ int vs_set_traj_capacity(vs_handle h, int t_max) {
     if ((rc = dalloc(h, &d.traj_done, (size_t)((t_max + 31) / 32) * ld))) return rc;
     h->traj_cap = t_max;
     d.traj_rows = t_max;
-    return VS_OK;
+    return alloc_hrec(h);
 }
 
 int vs_set_record_mode(vs_handle h, int mode) {
@@ -808,12 +845,20 @@ int vs_step_random(vs_handle h, uint64_t seed, int k_steps, int record) {
     return VS_OK;
 }
 
+static int drop_rnn(vs_handle h) {
+    if (h->rnn.w) HIPCHK(h, hipFree((void*)h->rnn.w));
+    if (h->rnn.hid) HIPCHK(h, hipFree(h->rnn.hid));
+    h->rnn = Rnn{};
+    return VS_OK;
+}
+
 int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params, int64_t n_params) {
     if (!h) return VS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }
     h->fnn = Fnn{};
+    if (int rc = drop_rnn(h)) return rc;  // one in-kernel policy at a time
     if (!desc) return VS_OK;
     const EnvInfo& ei = ENV_INFO[h->type];
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: the discrete-action family takes no network policy");
@@ -883,8 +928,125 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     return VS_OK;
 }
 
+int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params, int64_t n_params) {
+    if (!h) return VS_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = drop_rnn(h)) return rc;
+    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
+    h->fnn = Fnn{};
+    if (!desc) return VS_OK;
+    const EnvInfo& ei = ENV_INFO[h->type];
+    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: the discrete-action family takes no network policy");
+    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_policy_rnn: not available with a wrapper pipeline on the handle");
+    if (!params || desc->cell < VS_RNN_TANH || desc->cell > VS_RNN_LSTM) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: unknown cell kind or no parameter vector");
+    if (desc->n_layers < 1 || desc->n_layers > RNN_MAXL) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: 1 .. 2 recurrent layers");
+    if (desc->hidden < 1 || desc->hidden > RNN_MAXW) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: 1 .. 64 hidden units");
+    if (desc->out_nonlin < 0 || desc->out_nonlin > FNN_SIGMOID) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: unknown nonlinearity");
+    Rnn f{};
+    f.cell = desc->cell;
+    f.n_layers = desc->n_layers;
+    f.hidden = desc->hidden;
+    f.hp = (f.hidden + 3) / 4 * 4;
+    const int G = rnn_gates(f.cell), lstm = f.cell == VS_RNN_LSTM;
+    f.hs = f.n_layers * f.hidden * (lstm ? 2 : 1);
+    f.out_nonlin = desc->out_nonlin;
+    f.n_vis = desc->n_obs > 0 ? desc->n_obs : ei.O;
+    if (f.n_vis > ei.O || f.n_vis > RNN_XP) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: more visible observation rows than the env has");
+    f.ident = f.n_vis == ei.O;
+    for (int k = 0; k < f.n_vis; ++k) {
+        f.obs_idx[k] = desc->n_obs > 0 ? desc->obs_idx[k] : k;
+        if (f.obs_idx[k] < 0 || f.obs_idx[k] >= ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: obs_idx out of range");
+        if (f.obs_idx[k] != k) f.ident = 0;
+    }
+    for (int j = 0; j < ei.A; ++j) {
+        f.noise_std[j] = desc->noise_std[j];
+        if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: noise_std must be >= 0");
+        if (f.noise_std[j] > 0.f) f.noisy = 1;
+    }
+    const int64_t Hh = f.hidden;
+    int64_t need = 0;
+    int off = 0;
+    for (int l = 0; l < f.n_layers; ++l) {
+        const int64_t in = l == 0 ? f.n_vis : Hh;
+        need += G * Hh * in + G * Hh * Hh + 2 * G * Hh;
+        f.off[l] = off;
+        f.blk[l] = ((l == 0 ? RNN_XP : f.hp) + f.hp) * G + (2 * G + 3) / 4 * 4;
+        off += f.blk[l] * f.hidden;
+    }
+    need += (int64_t)ei.A * Hh + ei.A;
+    f.off_o = off;
+    off += ei.A * f.hp + 4;
+    if (n_params != need) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: parameter count does not match the cell, layers and sizes");
+    f.lds_rows = (f.n_layers * (lstm ? 2 : 1) + f.n_layers) * f.hp;
+    // torch order -> per unit blocks, gate-interleaved rows (the kernel reads G consecutive floats per input)
+    std::vector<float> src((size_t)need), pk((size_t)off, 0.f);
+    HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    size_t q = 0;
+    for (int l = 0; l < f.n_layers; ++l) {
+        const int in = l == 0 ? f.n_vis : f.hidden, inp = l == 0 ? RNN_XP : f.hp;
+        auto unit = [&](int row) { return (size_t)f.off[l] + (size_t)(row % f.hidden) * f.blk[l]; };  // row = g H + j of torch
+        for (int r = 0; r < G * f.hidden; ++r)  // weight_ih [G H][in]
+            for (int k = 0; k < in; ++k) pk[unit(r) + (size_t)k * G + r / f.hidden] = src[q++];
+        for (int r = 0; r < G * f.hidden; ++r)  // weight_hh [G H][H]
+            for (int k = 0; k < f.hidden; ++k) pk[unit(r) + (size_t)(inp + k) * G + r / f.hidden] = src[q++];
+        for (int r = 0; r < G * f.hidden; ++r) pk[unit(r) + (size_t)(inp + f.hp) * G + r / f.hidden] = src[q++];      // bias_ih
+        for (int r = 0; r < G * f.hidden; ++r) pk[unit(r) + (size_t)(inp + f.hp) * G + G + r / f.hidden] = src[q++];  // bias_hh
+    }
+    for (int j = 0; j < ei.A; ++j)
+        for (int k = 0; k < f.hidden; ++k) pk[(size_t)f.off_o + (size_t)j * f.hp + k] = src[q++];
+    for (int j = 0; j < ei.A; ++j) pk[(size_t)f.off_o + (size_t)ei.A * f.hp + j] = src[q++];
+    float* dw = nullptr;
+    HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_rnn: upload", e); }
+    f.w = dw;
+    const size_t hb = (size_t)f.hs * h->d.ld * sizeof(float);
+    e = hipMalloc((void**)&f.hid, hb);
+    if (e == hipSuccess) e = hipMemset(f.hid, 0, hb);
+    if (e != hipSuccess) { (void)hipFree(dw); if (f.hid) (void)hipFree(f.hid); return fail(h, VS_ERR_HIP, "vs_set_policy_rnn: hidden state", e); }
+    h->rnn = f;
+    return VS_OK;
+}
+
+int vs_set_policy_hidden_record(vs_handle h, int width) {
+    if (!h || width < 0 || width > 2 * RNN_MAXL * RNN_MAXW * 4) return fail(h, VS_ERR_ARG, "vs_set_policy_hidden_record: bad width");
+    if (width == h->hrec_width) return VS_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->hrec_width = width;
+    return alloc_hrec(h);
+}
+
+int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64_t dim_stride, int row) {
+    if (!h || !hidden) return fail(h, VS_ERR_ARG, "vs_record_hidden: NULL argument");
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &st) != hipSuccess) (void)hipGetLastError();
+    if (st == hipStreamCaptureStatusNone) {
+        if (!is_device_ptr(hidden)) return fail(h, VS_ERR_ARG, "vs_record_hidden: the hidden state must be device memory");
+        HIPCHK(h, hipSetDevice(h->device));
+    }
+    if (!h->d_hrec) return fail(h, VS_ERR_STATE, "vs_record_hidden: set the record capacity and vs_set_policy_hidden_record first");
+    if (row >= h->traj_cap) return fail(h, VS_ERR_STATE, "vs_record_hidden: row exceeds vs_set_traj_capacity");
+    hipLaunchKernelGGL(k_record_hidden, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, hidden, (long)env_stride, (long)dim_stride,
+                       h->d_hrec, (const int*)h->d.rec_row, row, h->traj_cap, h->hrec_width, (size_t)h->d.ld, h->d.n);
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
 int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
     if (!h || k_steps < 1) return fail(h, VS_ERR_ARG, "vs_step_policy: bad argument");
+    if (h->rnn.w) {
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
+        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
+        if (record && h->hrec_width && h->hrec_width != h->rnn.hs)
+            return fail(h, VS_ERR_STATE, "vs_step_policy: the hidden-state record width differs from the policy's hidden size");
+        HIPCHK(h, hipSetDevice(h->device));
+        h->rnn.hrec = h->d_hrec;
+        DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
+        HIPCHK(h, hipGetLastError());
+        return VS_OK;
+    }
     if (!h->fnn.w) return fail(h, VS_ERR_STATE, "vs_step_policy: no network set (vs_set_policy_fnn)");
     if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
     if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
@@ -1040,6 +1202,8 @@ static bool buf_info(vs_handle h, int which, void** p, size_t* bytes) {
         case VS_JAC_STATE: *p = d.jac_s; *bytes = d.jac_s ? (size_t)ei.S * (ei.S + ei.A) * ld * 4 : 0; return true;
         case VS_JAC_REW: *p = d.jac_r; *bytes = d.jac_r ? (size_t)(ei.S + ei.A) * ld * 4 : 0; return true;
         case VS_JAC_OBS: *p = d.jac_o; *bytes = d.jac_o ? (size_t)ei.O * (ei.S + ei.A) * ld * 4 : 0; return true;
+        case VS_POLICY_HIDDEN: *p = h->rnn.hid; *bytes = h->rnn.hid ? (size_t)h->rnn.hs * ld * 4 : 0; return true;
+        case VS_POLICY_HIDDEN_REC: *p = h->d_hrec; *bytes = h->d_hrec ? (size_t)h->traj_cap * h->hrec_width * ld * 4 : 0; return true;
 #ifdef VS_WS_STAMP
         case 99: *p = d.dbg; *bytes = (size_t)(ld / 64) * 12 * 8; return true;
 #endif
@@ -1068,8 +1232,8 @@ int vs_copy_to_host(vs_handle h, int which, void* dst) {
 
 int vs_copy_from_host(vs_handle h, int which, const void* src) {
     if (!h || !src) return fail(h, VS_ERR_ARG, "vs_copy_from_host: NULL argument");
-    if (which != VS_STATE && which != VS_HIDDEN && which != VS_STEPCOUNT)
-        return fail(h, VS_ERR_ARG, "vs_copy_from_host: only VS_STATE / VS_HIDDEN / VS_STEPCOUNT are assignable");
+    if (which != VS_STATE && which != VS_HIDDEN && which != VS_STEPCOUNT && which != VS_POLICY_HIDDEN)
+        return fail(h, VS_ERR_ARG, "vs_copy_from_host: only VS_STATE / VS_HIDDEN / VS_STEPCOUNT / VS_POLICY_HIDDEN are assignable");
     void* p; size_t b;
     buf_info(h, which, &p, &b);
     if (b == 0) return VS_OK;

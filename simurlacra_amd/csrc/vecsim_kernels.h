@@ -1366,6 +1366,258 @@ __global__ __launch_bounds__(64 * fnn_waves(NHID)) void k_rollout_fnn(Task T, De
     d.es_lensum[i] = es.lensum;
 }
 
+// -------------------------------------------------------------------------------------- recurrent policy inside the kernel
+// vs_step_policy with a recurrent policy (vs_set_policy_rnn): torch.nn.RNN / GRU / LSTM of 1 or 2 layers of at most 64 units and a
+// Linear output layer -- RNNPolicy / GRUPolicy / LSTMPolicy of P/policies/recurrent/rnn.py, forward(obs, hidden) -> (act, hidden)
+// called at rollout.py:203-219 -- evaluated INSIDE the fused rollout kernel, with the hidden state of every lane kept on chip
+// across the steps of a launch and in VS_POLICY_HIDDEN between launches.  Per step and lane, with torch's gate order and biases:
+//   RNN   h' = f(W_ih x + b_ih + W_hh h + b_hh)                                  f = tanh | relu
+//   GRU   r, z = sigma(W_i{r,z} x + b_i{r,z} + W_h{r,z} h + b_h{r,z})
+//         n = tanh(W_in x + b_in + r * (W_hn h + b_hn))   h' = (1 - z) n + z h   (the h part of n and its bias stay apart)
+//   LSTM  i, f, o = sigma(..), g = tanh(..)               c' = f c + i g         h' = o tanh(c')
+//   layer 1 takes layer 0's h';  act = W_out h'_top + b_out [output nonlinearity] [+ std * N(0, 1)]
+//   x = the visible observation rows (obs_idx), no featurisation.
+// Shape: one wave of 64 envs per workgroup, lane = env, everything fp32 on the vector ALU.
+//   * The weights are wave-uniform: read through the constant address space, i.e. with scalar loads into SGPRs that every FMA
+//     takes as its uniform operand -- no weight registers per lane, so any hidden size and both layers run the same code.
+//   * The per-lane vectors (hidden state of every layer, LSTM cell state, the layer outputs h') live in LDS as rows [k][64 lanes]:
+//     a runtime hidden size cannot index registers, and row k of lane l is a conflict-free ds_read_b32 / ds_write_b32.  Unit j of
+//     a layer is one pass over its input and hidden rows, G gates at a time (one LDS read feeds G FMAs).
+//   * The env step behind the network is k_rollout_fnn's, statement for statement (same records, auto-reset, freeze-at-done).
+// Hidden rows are padded to a multiple of 4 units (zero weights, rows zeroed once); a lane's state rows are zeroed at its
+// auto-reset (a new rollout starts from init_hidden()), and a frozen lane keeps its state.
+constexpr int RNN_MAXL = 2;   // layers
+constexpr int RNN_MAXW = 64;  // units per layer
+constexpr int RNN_XP = MAXO;  // padded input row of layer 0
+enum RnnCell { RNN_CELL_TANH = 0, RNN_CELL_RELU = 1, RNN_CELL_GRU = 2, RNN_CELL_LSTM = 3 };
+__host__ __device__ constexpr int rnn_gates(int cell) { return cell == RNN_CELL_GRU ? 3 : cell == RNN_CELL_LSTM ? 4 : 1; }
+struct Rnn {
+    const float* w;  // device, packed by vs_set_policy_rnn: unit j of layer l is a block of blk[l] floats at off[l] + j blk[l]:
+                     //   Wi [in_l][G] (in_0 = RNN_XP, in_1 = hp) | Wh [hp][G] | b_ih [G] | b_hh [G] (| pad to 4)
+                     // output layer Wo [A][hp] at off_o, bo [A] at off_o + A hp
+    float* hid;      // VS_POLICY_HIDDEN f32 [hs][ld]: h of layer 0, 1 .. then (LSTM) c of layer 0, 1 ..
+    float* hrec;     // hidden-state record plane f32 [T][hs][ld] (row t: the state before step t); nullptr: not recorded
+    int cell, n_layers, hidden, hp, hs, out_nonlin;
+    int n_vis, ident, noisy;
+    int obs_idx[MAXO];
+    float noise_std[MAXA];
+    int off[RNN_MAXL], blk[RNN_MAXL], off_o;
+    int lds_rows;    // rows of 64 floats of LDS per workgroup: (n_layers (1 + LSTM) + n_layers) hp
+};
+
+template <class E, bool AR, int REC, int G>
+__global__ __launch_bounds__(64) void k_rollout_rnn(Task T, Dev d, Rnn P, int k_steps, uint64_t reset_seed, uint64_t noise_seed) {
+    static_assert(G == 1 || G == 3 || G == 4, "RNN, GRU or LSTM");
+    extern __shared__ float l_rnn[];  // [row][64]: state rows h (n_layers hp), c (LSTM, n_layers hp), then h' rows (n_layers hp)
+    typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
+    constexpr bool UNI = false;
+    const cfp W = (cfp)P.w;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const size_t rec0 = (size_t)d.traj_t0;
+    const bool valid = i < d.n;
+    const int L = P.n_layers, H = P.hidden, hp = P.hp;
+    const int ns = (G == 4 ? 2 : 1) * L;  // state rows (in units of hp)
+    float* const ls = l_rnn + lane;       // this lane's column
+
+    // ---- the lane's hidden state: VS_POLICY_HIDDEN -> LDS (padding rows zero)
+    for (int r = 0; r < P.lds_rows; ++r) ls[r * 64] = 0.f;
+    for (int q = 0, p = 0; q < ns; ++q)
+        for (int j = 0; j < H; ++j, ++p) ls[(q * hp + j) * 64] = P.hid[(size_t)p * ld + i];
+
+    // ---- env state of the lane (k_rollout_fnn's)
+    float c[E::K], s[E::S], h[E::H > 0 ? E::H : 1], a[E::A], ob[E::O];
+    float alo[E::A], ahi[E::A];
+    int step = 0;
+    float ret = 0.f, rew = 0.f;
+    bool yielded = false, frozen = false, done = false, failed = false;
+    EpStat es{0u, 0u, 0.f, 0};
+    DoneBits db;
+    db.w = 0u;
+    load_consts<E, UNI>(d, i, c, 0, E::KS);
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) s[j] = d.state[j * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) h[j] = d.hidden[j * ld + i];
+    step = d.step[i];
+    ret = d.ret[i];
+    yielded = E::FINAL != FINAL_NONE ? d.yielded[i] != 0 : false;
+    frozen = !AR && d.done[i] != 0;
+    rew = d.rew[i];
+    done = d.done[i] != 0, failed = d.failed[i] != 0;
+    es = EpStat{d.ep_idx[i], d.es_count[i], d.es_retsum[i], d.es_lensum[i]};
+    E::act_bounds(c, alo, ahi);
+    E::observe(s, ob);
+    if (REC) db.begin(d, i, rec0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (see rollout_body: nothing pending at the loop header)
+
+    for (int t = 0; t < k_steps; ++t) {
+        // ---- the hidden state before the step into row t of the record plane
+        if (REC && P.hrec) {
+            float* row = P.hrec + (rec0 + (size_t)t) * (size_t)P.hs * ld + i;
+            for (int q = 0, p = 0; q < ns; ++q)
+                for (int j = 0; j < H; ++j, ++p) __builtin_nontemporal_store(ls[(q * hp + j) * 64], row + (size_t)p * ld);
+        }
+        // ---- what the policy sees of obs_t
+        float x[RNN_XP];
+        if (P.ident) {
+#pragma unroll
+            for (int k = 0; k < RNN_XP; ++k) x[k] = k < E::O ? ob[k] : 0.f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < RNN_XP; ++k) {
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                x[k] = v;
+            }
+        }
+        // ---- the recurrent layers, unit by unit, and the output layer behind the last one
+        float out[E::A];
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) out[j] = 0.f;
+        for (int l = 0; l < L; ++l) {
+            const float* hin = ls + (size_t)((ns + l - 1) * hp) * 64;  // l > 0: layer l - 1's h'
+            float* hst = ls + (size_t)(l * hp) * 64;
+            float* cst = ls + (size_t)((L + l) * hp) * 64;
+            float* hnew = ls + (size_t)((ns + l) * hp) * 64;
+            const int inp = l == 0 ? RNN_XP : hp;
+            for (int u = 0; u < H; ++u) {
+                const cfp wu = W + P.off[l] + u * P.blk[l];
+                float ai[G], ah[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g) ai[g] = 0.f, ah[g] = 0.f;
+                if (l == 0) {
+#pragma unroll
+                    for (int k = 0; k < RNN_XP; ++k)
+#pragma unroll
+                        for (int g = 0; g < G; ++g) ai[g] = fmaf(wu[k * G + g], x[k], ai[g]);
+                } else {
+                    for (int k = 0; k < hp; k += 4) {
+                        float v[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[q] = hin[(k + q) * 64];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+#pragma unroll
+                            for (int g = 0; g < G; ++g) ai[g] = fmaf(wu[(k + q) * G + g], v[q], ai[g]);
+                    }
+                }
+                const cfp wh = wu + inp * G;
+                for (int k = 0; k < hp; k += 4) {
+                    float v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = hst[(k + q) * 64];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int g = 0; g < G; ++g) ah[g] = fmaf(wh[(k + q) * G + g], v[q], ah[g]);
+                }
+                const cfp bi = wh + hp * G, bh = bi + G;
+                auto sigm = [](float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); };
+                float hv;
+                if constexpr (G == 1) {
+                    const float v = (ai[0] + bi[0]) + (ah[0] + bh[0]);
+                    hv = P.cell == RNN_CELL_RELU ? fmaxf(v, 0.f) : tanh_fast(v);
+                } else if constexpr (G == 3) {
+                    const float r = sigm((ai[0] + bi[0]) + (ah[0] + bh[0]));
+                    const float z = sigm((ai[1] + bi[1]) + (ah[1] + bh[1]));
+                    const float n = tanh_fast((ai[2] + bi[2]) + r * (ah[2] + bh[2]));
+                    hv = (1.0f - z) * n + z * hst[u * 64];
+                } else {
+                    const float ig = sigm((ai[0] + bi[0]) + (ah[0] + bh[0]));
+                    const float fg = sigm((ai[1] + bi[1]) + (ah[1] + bh[1]));
+                    const float gg = tanh_fast((ai[2] + bi[2]) + (ah[2] + bh[2]));
+                    const float og = sigm((ai[3] + bi[3]) + (ah[3] + bh[3]));
+                    const float cv = fg * cst[u * 64] + ig * gg;
+                    if (!frozen) cst[u * 64] = cv;  // (read by this unit only)
+                    hv = og * tanh_fast(cv);
+                }
+                hnew[u * 64] = hv;
+                if (l == L - 1) {
+#pragma unroll
+                    for (int j = 0; j < E::A; ++j) out[j] = fmaf(W[P.off_o + j * hp + u], hv, out[j]);
+                }
+            }
+        }
+        if (!frozen)  // h' becomes the state (a frozen lane keeps its own)
+            for (int l = 0; l < L; ++l)
+                for (int u = 0; u < H; ++u) ls[(l * hp + u) * 64] = ls[((ns + l) * hp + u) * 64];
+        // ---- the policy's action of this lane's env (+ exploration noise)
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) a[j] = fnn_nonlin(P.out_nonlin, out[j] + W[P.off_o + E::A * hp + j]);
+        if (P.noisy) {
+            // NormalActNoiseExplStrat: + std * N(0, 1), keyed like the wrapper noise by (env, episode, step)
+            uint4 b = Rng::philox(noise_seed, d.idx0 + (uint32_t)i, RNG_POLICY_NOISE, ((uint64_t)es.epi << 32) | (uint32_t)step);
+            float z[2];
+            Rng::box_muller(b.x, b.y, z[0], z[1]);
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) a[j] = fmaf(P.noise_std[j], z[j], a[j]);
+        }
+        // ---- the env step: k_rollout_fnn's, statement for statement
+        float s_pre[E::S], h_pre[E::H > 0 ? E::H : 1], a_app[E::A], ow[E::O];
+#pragma unroll
+        for (int j = 0; j < E::O; ++j) ow[j] = ob[j];
+        if (REC == 2) {
+#pragma unroll
+            for (int j = 0; j < E::S; ++j) s_pre[j] = s[j];
+#pragma unroll
+            for (int j = 0; j < E::H; ++j) h_pre[j] = h[j];
+            applied_action<E>(T, c, alo, ahi, a, a_app);
+        }
+        if (!frozen) {
+            StepOut o = step_one<E, float>(T, c, s, h, a, step, yielded,
+                                           E::TRIG > 0 ? (const float*)(ob + E::TRIG_AT) : (const float*)nullptr);
+            rew = o.rew;
+            done = o.done;
+            failed = o.failed;
+            ret += o.rew;
+            if (o.err && valid) d.err[i] = 1;
+        } else {
+            rew = 0.f;
+        }
+        if (REC) {
+            store_record<E, REC>(d.traj_rec + (rec0 + (size_t)t) * Rec<E, REC>::F * ld, ld, i, ow, a, rew, s_pre, a_app, h_pre);
+            db.put(d, i, rec0 + (size_t)t, done, t == k_steps - 1);
+        }
+        bool fin = done && valid && !frozen;
+        if (AR) {
+            auto_reset<E, UNI>(T, d, fin, i, reset_seed, c, s, h, step, ret, yielded, es);
+            E::act_bounds(c, alo, ahi);
+            if (fin)  // a new rollout starts from init_hidden()
+                for (int r = 0; r < ns * hp; ++r) ls[r * 64] = 0.f;
+        } else {
+            if (fin) {
+                es.count += 1u;
+                es.retsum += ret;
+                es.lensum += step;
+            }
+            if (d.log_episodes) append_episode(d, fin, i, ret, step);
+            frozen |= done;
+        }
+        E::observe(s, ob);
+    }
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) d.state[j * ld + i] = s[j];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) d.hidden[j * ld + i] = h[j];
+#pragma unroll
+    for (int j = 0; j < E::O; ++j) d.obs[j * ld + i] = ob[j];
+    d.step[i] = step;
+    d.ret[i] = ret;
+    d.rew[i] = rew;
+    d.done[i] = done;
+    d.failed[i] = failed;
+    if (E::FINAL != FINAL_NONE) d.yielded[i] = yielded;
+    d.ep_idx[i] = es.epi;
+    d.es_count[i] = es.count;
+    d.es_retsum[i] = es.retsum;
+    d.es_lensum[i] = es.lensum;
+    for (int q = 0, p = 0; q < ns; ++q)
+        for (int j = 0; j < H; ++j, ++p) P.hid[(size_t)p * ld + i] = ls[(q * hp + j) * 64];
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -2346,6 +2598,9 @@ struct vs_env {
     float* d_pbuf = nullptr;      // DomainRandWrapperBuffer parameter sets
     float* d_ring = nullptr;      // ActDelayWrapper ring (Pipe::ring)
     vs::Fnn fnn{};                // vs_set_policy_fnn: the network vs_step_policy evaluates (fnn.w == nullptr: none)
+    vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
+    int hrec_width = 0;           // vs_set_policy_hidden_record: floats per env and step of the hidden-state record plane, 0 off
+    float* d_hrec = nullptr;      // ... the plane, f32 [traj_cap][hrec_width][ld]
     int rollout_variant = -1;     // vs_set_rollout_variant: -1 automatic, 0 k_rollout, 1 k_rollout_ws<256>, 2 k_rollout_ws<64>, 3 / 4 the three-role kernel in 64 / 256-env workgroups
     int policy_shape = -1;        // vs_set_policy_shape: -1 automatic, 0 / 1: k_rollout_fnn in 64- / 256-env workgroups, 2: 256-env + matrix cores
     int n_cu = 256;               // compute units of the device (256 on MI355X)
@@ -2378,6 +2633,7 @@ struct Launch {
     static void step(vs_env* h, const float* act, long es, long ds, int rec = 0, int row = 0);
     static void rollout(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec);
     static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy
+    static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy, recurrent policy
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -2565,6 +2821,28 @@ void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
 #undef LFA
 #undef LFR
 #undef LF
+}
+
+template <class E>
+void Launch<E>::rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
+    // one wave of 64 envs per workgroup; the LDS rows of the lane vectors are the only per-shape resource
+    const size_t lds = (size_t)h->rnn.lds_rows * 64 * sizeof(float);
+    Rnn P = h->rnn;
+    if (!rec || h->hrec_width != P.hs) P.hrec = nullptr;
+#define LR(AR, REC, G)                                                                                                    \
+    {                                                                                                                     \
+        (void)hipFuncSetAttribute((const void*)&k_rollout_rnn<E, AR, REC, G>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                  (int)lds);                                                                              \
+        hipLaunchKernelGGL((k_rollout_rnn<E, AR, REC, G>), dim3((unsigned)(h->d.ld / 64)), dim3(64), lds, h->stream,        \
+                           h->task, h->d, P, k, h->ar_seed, noise_seed);                                                  \
+    }
+#define LRR(AR, G) { if (rec == 0) LR(AR, 0, G) else if (rec == 1) LR(AR, 1, G) else LR(AR, 2, G) }
+#define LRA(G) { if (h->auto_reset) LRR(true, G) else LRR(false, G) }
+    const int g = rnn_gates(P.cell);
+    if (g == 1) LRA(1) else if (g == 3) LRA(3) else LRA(4)
+#undef LRA
+#undef LRR
+#undef LR
 }
 
 template <class E>

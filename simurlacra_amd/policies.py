@@ -143,6 +143,123 @@ class FNNPolicy(Policy):
         return self.net(obs)
 
 
+# ----------------------------------------------------------------------------------------------------- recurrent policies
+class RecurrentPolicy(Policy):
+    """A policy with a hidden state: forward(obs, hidden=None) -> (act, new_hidden) (P/policies/base.py RecurrentPolicy).
+    The hidden state is one flat vector per env -- [H] unbatched, [N, H] batched -- and a rollout starts from init_hidden()."""
+
+    is_recurrent = True
+
+    @property
+    def hidden_size(self) -> int:
+        raise NotImplementedError
+
+    def init_hidden(self, batch_size: int = None) -> torch.Tensor:
+        p0 = next(self.parameters(), None)
+        shape = (self.hidden_size,) if batch_size is None else (int(batch_size), self.hidden_size)
+        return torch.zeros(shape, device=p0.device if p0 is not None else None)
+
+
+class _RNNPolicyBase(RecurrentPolicy):
+    """torch.nn.RNN / GRU / LSTM layers (bias, batch_first=False) and a Linear output layer (P/policies/recurrent/rnn.py).
+
+    Packed hidden layout, Pyrado's: the h of layer 0, 1, .. concatenated, and for the LSTM the c of every layer behind them in
+    the same order -- hidden_size = layers x units (x 2 for the LSTM).  Parameters in torch's order (param_values):
+    rnn_layers.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, [.. _l1], output_layer.weight, output_layer.bias.
+    The parameters keep torch's default initialisation (init_param(None)); Pyrado's init_param draws are not reproduced."""
+
+    _rnn_cls = None
+
+    def __init__(self, spec, hidden_size, num_recurrent_layers, output_nonlin=None, dropout=0.0, init_param_kwargs=None,
+                 use_cuda=False, **rnn_kwargs):
+        super().__init__(spec)
+        self._hidden = int(hidden_size)
+        self.num_recurrent_layers = int(num_recurrent_layers)
+        self.dropout = float(dropout)
+        self.output_nonlin = output_nonlin
+        self.rnn_layers = self._rnn_cls(input_size=spec.obs_space.flat_dim, hidden_size=self._hidden,
+                                        num_layers=self.num_recurrent_layers, bias=True, batch_first=False,
+                                        dropout=self.dropout, **rnn_kwargs)
+        self.output_layer = torch.nn.Linear(self._hidden, spec.act_space.flat_dim)
+        self.init_param(None, **(init_param_kwargs or {}))
+        self.to("cuda" if use_cuda and torch.cuda.is_available() else "cpu")
+
+    @property
+    def hidden_size(self) -> int:
+        return self.num_recurrent_layers * self._hidden * (2 if self._rnn_cls is torch.nn.LSTM else 1)
+
+    @property
+    def param_values(self):
+        return torch.nn.utils.parameters_to_vector(self.parameters())
+
+    @param_values.setter
+    def param_values(self, param):
+        torch.nn.utils.vector_to_parameters(param, self.parameters())
+
+    def init_param(self, init_values=None, **kwargs):
+        if init_values is not None:
+            self.param_values = init_values
+
+    def _unpack(self, hidden):  # [N, hidden_size] -> the module's [layers, N, units] (LSTM: a pair)
+        n, L, u = hidden.shape[0], self.num_recurrent_layers, self._hidden
+        if self._rnn_cls is torch.nn.LSTM:
+            h = hidden[:, :L * u].reshape(n, L, u).transpose(0, 1).contiguous()
+            c = hidden[:, L * u:].reshape(n, L, u).transpose(0, 1).contiguous()
+            return h, c
+        return hidden.reshape(n, L, u).transpose(0, 1).contiguous()
+
+    def _pack(self, hidden):
+        if self._rnn_cls is torch.nn.LSTM:
+            h, c = hidden
+            return torch.cat([h.transpose(0, 1).reshape(h.shape[1], -1), c.transpose(0, 1).reshape(c.shape[1], -1)], dim=1)
+        return hidden.transpose(0, 1).reshape(hidden.shape[1], -1)
+
+    def forward(self, obs, hidden=None):
+        p0 = next(self.parameters())
+        obs = obs.to(device=p0.device, dtype=p0.dtype)
+        batched = obs.dim() == 2
+        x = obs if batched else obs.unsqueeze(0)
+        if hidden is None:
+            hidden = self.init_hidden(x.shape[0])
+        hd = hidden.to(device=p0.device, dtype=p0.dtype)
+        hd = hd if hd.dim() == 2 else hd.unsqueeze(0)
+        out, new = self.rnn_layers(x.unsqueeze(0), self._unpack(hd))  # one time step of a batch
+        act = self.output_layer(out.squeeze(0))
+        if self.output_nonlin is not None:
+            act = self.output_nonlin(act)
+        new = self._pack(new)
+        return (act, new) if batched else (act.squeeze(0), new.squeeze(0))
+
+
+class RNNPolicy(_RNNPolicyBase):
+    """Elman RNN policy (P/policies/recurrent/rnn.py RNNPolicy): hidden_nonlin 'tanh' | 'relu'"""
+
+    name = "rnn"
+    _rnn_cls = torch.nn.RNN
+
+    def __init__(self, spec, hidden_size, num_recurrent_layers, hidden_nonlin="tanh", output_nonlin=None, dropout=0.0,
+                 init_param_kwargs=None, use_cuda=False):
+        if hidden_nonlin not in ("tanh", "relu"):
+            raise ValueError(f"hidden_nonlin must be 'tanh' or 'relu', got {hidden_nonlin!r}")
+        self.hidden_nonlin = hidden_nonlin
+        super().__init__(spec, hidden_size, num_recurrent_layers, output_nonlin, dropout, init_param_kwargs, use_cuda,
+                         nonlinearity=hidden_nonlin)
+
+
+class GRUPolicy(_RNNPolicyBase):
+    """GRU policy (P/policies/recurrent/rnn.py GRUPolicy)"""
+
+    name = "gru"
+    _rnn_cls = torch.nn.GRU
+
+
+class LSTMPolicy(_RNNPolicyBase):
+    """LSTM policy (P/policies/recurrent/rnn.py LSTMPolicy); the packed hidden state is [h of every layer | c of every layer]"""
+
+    name = "lstm"
+    _rnn_cls = torch.nn.LSTM
+
+
 class NormalActNoiseExplStrat(Policy):
     """Gaussian noise on the actions of a wrapped policy (P/exploration/stochastic_action.py:121-180, shallow form: a fixed
     or externally updated diagonal std)"""
@@ -159,10 +276,25 @@ class NormalActNoiseExplStrat(Policy):
     def reset(self, **kwargs):
         self.policy.reset(**kwargs)
 
-    def forward(self, obs):
-        act = self.policy(obs)
+    @property
+    def is_recurrent(self):
+        return bool(getattr(self.policy, "is_recurrent", False))
+
+    @property
+    def hidden_size(self):
+        return self.policy.hidden_size
+
+    def init_hidden(self, batch_size=None):
+        return self.policy.init_hidden(batch_size)
+
+    def forward(self, obs, hidden=None):
+        if self.is_recurrent:  # the noise goes on the action only, never into the hidden state
+            act, hidden = self.policy(obs, hidden)
+        else:
+            act = self.policy(obs)
         std = self.std if self.std.device == act.device else self.std.to(act.device)
-        return act + std.to(act.dtype) * torch.randn_like(act)
+        act = act + std.to(act.dtype) * torch.randn_like(act)
+        return (act, hidden) if self.is_recurrent else act
 
 
 _NONLIN_NAMES = {torch.tanh: "tanh", torch.nn.functional.tanh: "tanh", torch.relu: "relu", torch.nn.functional.relu: "relu",
@@ -208,3 +340,36 @@ def fnn_kernel_spec(policy):
         return None
     return dict(params=torch.nn.utils.parameters_to_vector(net.parameters()).detach().to(torch.float32),
                 hidden_sizes=sizes, hidden_nonlin=hidden_nonlin, output_nonlin=output_nonlin, feat=feat, noise_std=noise_std)
+
+
+_RNN_CELL_NAMES = {torch.nn.GRU: "gru", torch.nn.LSTM: "lstm"}
+
+
+def rnn_kernel_spec(policy):
+    """The arguments of VecSimEnv.set_policy_rnn for a recurrent policy the fused kernel can evaluate itself -- RNNPolicy
+    (tanh / relu), GRUPolicy or LSTMPolicy of 1 or 2 layers of at most 64 units, no dropout, no projection, one direction, an
+    output nonlinearity None / tanh / relu / sigmoid, optionally inside a NormalActNoiseExplStrat -- or None (the sampler then
+    keeps the policy in torch)."""
+    noise_std = None
+    if isinstance(policy, NormalActNoiseExplStrat):
+        noise_std = policy.std.detach().cpu().numpy()
+        policy = policy.policy
+    if not isinstance(policy, _RNNPolicyBase):
+        return None
+    m = policy.rnn_layers
+    if not 1 <= m.num_layers <= 2 or not 1 <= m.hidden_size <= 64 or m.dropout > 0 or m.bidirectional:
+        return None
+    if getattr(m, "proj_size", 0) or not m.bias or m.batch_first:
+        return None
+    if isinstance(m, torch.nn.RNN):
+        cell = m.nonlinearity
+    else:
+        cell = _RNN_CELL_NAMES.get(type(m))
+    if cell not in ("tanh", "relu", "gru", "lstm") or m.input_size > 8:
+        return None
+    try:
+        output_nonlin = _nonlin_name(policy.output_nonlin)
+    except (KeyError, TypeError):
+        return None
+    return dict(params=torch.nn.utils.parameters_to_vector(policy.parameters()).detach().to(torch.float32), cell=cell,
+                n_layers=m.num_layers, hidden_size=m.hidden_size, output_nonlin=output_nonlin, noise_std=noise_std)

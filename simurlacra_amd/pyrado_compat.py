@@ -34,8 +34,8 @@ def to_pyrado_step_sequence(ro):
     if getattr(ro, "states", None) is not None:
         extra["states"] = ro.states
     # the fields rollout() adds besides observations / actions / rewards (P/sampling/rollout.py:305-325): the applied
-    # actions and, in the fork, the cartpole's hidden pole acceleration
-    for field in ("actions_applied", "th_ddot"):
+    # actions, in the fork the cartpole's hidden pole acceleration, and a recurrent policy's hidden state before every step
+    for field in ("actions_applied", "th_ddot", "hidden_states"):
         if getattr(ro, field, None) is not None:
             extra[field] = getattr(ro, field)
     if getattr(ro, "time", None) is not None:

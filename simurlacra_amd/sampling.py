@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from .exceptions import TypeErr, ValueErr
-from .policies import DummyPolicy, fnn_kernel_spec
+from .policies import DummyPolicy, fnn_kernel_spec, rnn_kernel_spec
 from .seeding import derive_seed, get_base_seed, set_seed
 from .wrappers import DomainRandWrapperBuffer, DomainRandWrapperLive, fuse_wrappers, inner_env, typed_env
 
@@ -60,7 +60,7 @@ class StepSequence:
 
     @classmethod
     def _packed(cls, observations, actions, rewards, info_src, done_last, dt, init_state, states=None,
-                actions_applied=None, th_ddot=None):
+                actions_applied=None, th_ddot=None, hidden_states=None):
         """views into the sampler's packed arrays (rewards already float64): no copies, no validation.
         info_src = (env_name, param_names, params_row, rollout_number)"""
         ro = cls.__new__(cls)
@@ -70,6 +70,8 @@ class StepSequence:
             ro.actions_applied = actions_applied  # [T, A]: env.limit_act(act) (rollout.py:244)
         if th_ddot is not None:
             ro.th_ddot = th_ddot  # [T + 1]: the fork's hidden pole acceleration before every step (rollout.py:238, 307)
+        if hidden_states is not None:
+            ro.hidden_states = hidden_states  # [T, H]: a recurrent policy's hidden state before every step (rollout.py:203-219)
         ro.env_infos = ro._time = ro._done = ro._info = None
         ro.complete = True
         ro._info_src = info_src
@@ -133,6 +135,7 @@ class PackedRollouts:
 
       observations [total + n, O]   actions [total + n, A]   rewards [total + n] (float32)
       states [total + n, S] | None  actions_applied [total + n, A] | None   th_ddot [total + n] | None  (full records)
+      hidden_states [total + n, H] | None  (a recurrent policy: its hidden state before every step; 0 in the final entry)
       lengths [n] (int64)   offsets [n + 1] (int64: exclusive cumulative lengths)   total = offsets[n]
       done_last [n] (bool: the rollout ended by done, not by the step limit)
       init_states [n, S]    first_index: rollout number of rollout 0 within the sample() call
@@ -209,7 +212,11 @@ def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, re
     if hasattr(policy, "eval") and hasattr(policy, "train"):
         policy.eval() if eval else policy.train()
     env.render(render_mode, render_step=1)
-    obs_hist, act_hist, act_app_hist, rew_hist, state_hist, t_hist = [], [], [], [], [], [0.0]
+    # a recurrent policy (rollout.py:174-219): forward(obs, hidden) -> (act, hidden), starting from init_hidden(); the hidden
+    # state BEFORE every step is recorded
+    recurrent = bool(getattr(policy, "is_recurrent", False))
+    hidden = policy.init_hidden() if recurrent else None
+    obs_hist, act_hist, act_app_hist, rew_hist, state_hist, t_hist, hid_hist = [], [], [], [], [], [0.0], []
     dts = dict(dts_policy=[], dts_step=[], dts_remainder=[])
     done, t = False, 0.0
     t_post_step = time.time()  # the first remainder sample is meaningless, as in the reference
@@ -219,7 +226,12 @@ def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, re
         if np.isnan(obs).any():
             raise ValueErr(msg="At least one observation value is NaN!")
         with torch.no_grad():
-            act = policy(torch.from_numpy(np.asarray(obs)).to(torch.get_default_dtype()))
+            obs_t = torch.from_numpy(np.asarray(obs)).to(torch.get_default_dtype())
+            if recurrent:
+                hid_hist.append(hidden.detach().cpu().numpy())
+                act, hidden = policy(obs_t, hidden)
+            else:
+                act = policy(obs_t)
         act = act.detach().cpu().numpy()
         if np.isnan(act).any():
             raise ValueErr(msg="At least one action value is NaN!")
@@ -250,6 +262,8 @@ def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, re
         observations = np.empty(len(obs_hist), dtype=object)
         observations[:] = obs_hist
     extra = {k: np.asarray(v) for k, v in dts.items()} if record_dts else {}
+    if recurrent:
+        extra["hidden_states"] = np.stack(hid_hist) if hid_hist else np.zeros((0, policy.hidden_size), dtype=np.float32)
     return StepSequence(observations=observations, actions=np.stack(act_hist), rewards=rew_hist,
                         states=np.stack(state_hist), time=t_hist, rollout_info=info, done_last=bool(done),
                         actions_applied=np.stack(act_app_hist), **extra)
@@ -463,6 +477,14 @@ class ParallelRolloutSampler:
         fnn = fnn_kernel_spec(self.policy) if (self._fuse_policy and plain_chain and not use_fused) else None
         if fnn is not None and base.name == "bob-d":
             fnn = None
+        # a recurrent policy the kernel can evaluate itself (vs_set_policy_rnn): the same fused path, the hidden state kept on the
+        # device from step to step and recorded before every step
+        rnn = rnn_kernel_spec(self.policy) if (self._fuse_policy and plain_chain and not use_fused and fnn is None) else None
+        if rnn is not None and base.name == "bob-d":
+            rnn = None
+        recurrent = bool(getattr(self.policy, "is_recurrent", False)) and not use_fused
+        W = int(self.policy.hidden_size) if recurrent else 0
+        v.set_policy_hidden_record(0)
         state0 = st_t.t().clone()
         T_cap = int(max_steps)
         t = 0
@@ -508,6 +530,23 @@ class ParallelRolloutSampler:
                 if bool(done_t.bool().all()):  # one scalar sync per launch
                     break
             v.set_traj_offset(0)
+        elif rnn is not None:
+            # rollout() with a recurrent policy == vs_step_policy with vs_set_policy_rnn (which zeroes every lane's hidden state):
+            # act, h' = policy(obs, h) -> step -> record inside ONE kernel, h carried from launch to launch
+            if hasattr(self.policy, "reset"):
+                self.policy.reset()
+            v.set_policy_rnn(obs_idx=None if fc.keep.all() else np.flatnonzero(fc.keep), **rnn)
+            v.set_record_mode(2 if full else 1)
+            v.set_traj_capacity(T_cap)
+            v.set_policy_hidden_record(W)
+            while t < T_cap:
+                k = int(min(self._chunk, T_cap - t))
+                v.set_traj_offset(t)
+                v.step_policy(k, record=True, noise_seed=lane_key ^ 0x8CB92BA72F3D8DD7)
+                t += k
+                if bool(done_t.bool().all()):  # one scalar sync per launch
+                    break
+            v.set_traj_offset(0)
         else:
             # policy in the loop: rollout() with the caller's policy (rollout.py:185-258).  One recording step kernel per env
             # step -- vs_step_record writes the observation the policy saw, its action, the reward, the done bit and (full
@@ -521,6 +560,21 @@ class ParallelRolloutSampler:
             v.set_record_mode(2 if full else 1)
             v.set_traj_capacity(T_cap)
             v.set_traj_offset(0)
+            # a recurrent policy: ONE device tensor [n, H] of hidden states, zeroed at the start of the batch, passed through
+            # policy(obs, hidden) and updated in place; the state before every step goes into the record plane (vs_record_hidden,
+            # before the vs_step_record that advances the row counter: a captured graph replays both)
+            hid = torch.zeros(n, W, device=dev) if recurrent else None
+            if recurrent:
+                v.set_policy_hidden_record(W)
+
+            def act_of(obs_now, row):
+                if not recurrent:
+                    return policy(obs_now)
+                v.record_hidden(hid, row=row)
+                act, hid_next = policy(obs_now, hid)
+                hid.copy_(hid_next.reshape(n, W))
+                return act
+
             # rollout() stops stepping an env at done (rollout.py:185): finished lanes are frozen by the step kernel, so
             # nothing the policy makes of their last observation can move them or raise their NaN flag
             v.set_freeze_done(True)
@@ -531,9 +585,11 @@ class ParallelRolloutSampler:
                     SEG = 32
                     v.set_traj_capacity((T_cap + SEG - 1) // SEG * SEG)
 
+                    v.set_policy_hidden_record(W)  # (the capacity grew: a fresh plane)
+
                     def one_step():
                         obs_now = visible(obs_full, 0).t().contiguous()
-                        act = policy(obs_now).to(torch.float32).reshape(n, A).contiguous()
+                        act = act_of(obs_now, None).to(torch.float32).reshape(n, A).contiguous()
                         v.step_record(act, row=None)
 
                     side = torch.cuda.Stream(device=dev)
@@ -548,6 +604,8 @@ class ParallelRolloutSampler:
                             reset_lanes()       # ... undone: the same reset, lane for lane
                             if hasattr(policy, "reset"):
                                 policy.reset()
+                            if recurrent:
+                                hid.zero_()
                             state0 = st_t.t().clone()
                             v.set_record_row(0)
                             side.synchronize()
@@ -566,7 +624,7 @@ class ParallelRolloutSampler:
                 with torch.no_grad():
                     while t < T_cap and not self._graph_policy:
                         obs_now = visible(obs_full, 0).t().contiguous()  # [n, O']: what the policy sees
-                        act = policy(obs_now).to(torch.float32).reshape(n, A).contiguous()
+                        act = act_of(obs_now, t).to(torch.float32).reshape(n, A).contiguous()
                         v.step_record(act, row=t)
                         t += 1
                         if (t % 32 == 0 or t == T_cap) and bool(done_t.bool().all()):  # one scalar sync per 32 steps
@@ -586,17 +644,28 @@ class ParallelRolloutSampler:
         # them: final observation / state / hidden state); every field below is a strided view of it
         rows = pk["rows"]
         fields = v.record_fields()
+        hid_rows = None
+        if recurrent:
+            # the hidden state before every step, from the record plane [T, W, ld]: row r of the packed matrix is step
+            # r - (start[j] + j) of rollout j; the final entries get 0
+            plane = v.hidden_record_tensor()
+            ridx = torch.repeat_interleave(torch.arange(n, device=length.device), length + 1, output_size=total + n)
+            tpos = torch.arange(total + n, device=length.device) - (start + torch.arange(n, device=length.device))[ridx]
+            valid = tpos < length[ridx]
+            hid_rows = plane[tpos.clamp(max=max(T - 1, 0)), :, ridx] * valid[:, None].to(plane.dtype)
         if packed_out:
             qcp_dev = base.name.startswith("qcp") and H and full
             return PackedRollouts(
                 rows=rows, observations=visible(pk["obs"], 1), actions=pk["act"], rewards=pk["rew"],
                 states=pk["state"] if full else None, actions_applied=pk["act_app"] if full else None,
                 th_ddot=pk["hidden"][:, 0] if qcp_dev else None, lengths=length, offsets=torch.cat([start, start[-1:] + length[-1:]]),
-                total=total, done_last=done_last_d, init_states=state0.contiguous(), first_index=first_index,
+                total=total, done_last=done_last_d, init_states=state0.contiguous(), first_index=first_index, hidden_states=hid_rows,
                 env_name=base.name, dt=base.dt, param_names=v.param_names, domain_params=v.tensor(L.VS_PARAMS)[:, :n].t().clone())
         # device -> host: the matrix in one transfer into pinned memory; the rollouts' fields are views of that block (rewards:
         # one conversion to float64 for all rollouts)
-        rows_h, done_h, length_h, state0_h = self._to_host([rows, done_last_d.to(torch.uint8), length, state0.contiguous()])
+        rows_h, done_h, length_h, state0_h, *hid_h = self._to_host([rows, done_last_d.to(torch.uint8), length, state0.contiguous()]
+                                                                   + ([hid_rows] if recurrent else []))
+        hid_h = hid_h[0] if recurrent else None
         c_rew = fields["rew"][0]
         rew_p = self._convert(rows_h[:, c_rew], np.float64)
         col = lambda k: rows_h[:, fields[k][0]:fields[k][0] + fields[k][1]]
@@ -620,7 +689,8 @@ class ParallelRolloutSampler:
                           (name, pnames, params[j], first_index + j), done_last[j], dt, state0_h[j],
                           None if st_p is None else st_p[off_o[j]:off_o[j + 1]],
                           None if app_p is None else app_p[off_o[j]:off_o[j] + lens[j]],
-                          hid_p[off_o[j]:off_o[j + 1], 0] if qcp else None) for j in range(n)]
+                          hid_p[off_o[j]:off_o[j + 1], 0] if qcp else None,
+                          None if hid_h is None else hid_h[off_o[j]:off_o[j] + lens[j]]) for j in range(n)]
         finally:
             if gc_was_on:
                 gc.enable()

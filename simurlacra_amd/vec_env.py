@@ -544,6 +544,7 @@ class VecSimEnv:
         hidden_nonlin: one name or one per hidden layer ('tanh' | 'relu' | 'sigmoid' | None); feat: the fork's FNNPolicy
         featurisation [o_0, sin o_1, cos o_1, o_2 ..]; obs_idx: the observation rows the policy sees (ObsPartialWrapper);
         noise_std: exploration noise per action dimension.  params=None removes the network."""
+        self._rnn_hs = 0  # (a network replaces a recurrent policy)
         if params is None:
             self._check(self._lib.vs_set_policy_fnn(self._h, None, None, 0), "vs_set_policy_fnn")
             return
@@ -572,6 +573,73 @@ class VecSimEnv:
         flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
         self._check(self._lib.vs_set_policy_fnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_fnn")
+
+    _RNN_CELLS = {"tanh": L.VS_RNN_TANH, "relu": L.VS_RNN_RELU, "gru": L.VS_RNN_GRU, "lstm": L.VS_RNN_LSTM}
+
+    def set_policy_rnn(self, params, cell="gru", n_layers=1, hidden_size=None, output_nonlin=None, obs_idx=None,
+                       noise_std=None):
+        """Hand a recurrent policy (RNNPolicy / GRUPolicy / LSTMPolicy, P/policies/recurrent/rnn.py) to the fused kernel of
+        step_policy.  params: parameters_to_vector(policy.parameters()) in torch order; cell: 'tanh' | 'relu' (nn.RNN) | 'gru' |
+        'lstm'; obs_idx / noise_std as in set_policy_fnn.  Zeroes the running hidden state (policy_hidden()).  params=None
+        removes the policy."""
+        if params is None:
+            self._check(self._lib.vs_set_policy_rnn(self._h, None, None, 0), "vs_set_policy_rnn")
+            self._rnn_hs = 0
+            return
+        d = L.RnnDesc()
+        d.cell = self._RNN_CELLS[cell]
+        d.n_layers = int(n_layers)
+        d.hidden = int(hidden_size)
+        d.out_nonlin = self._NONLIN[output_nonlin]
+        if obs_idx is not None:
+            idx = [int(x) for x in obs_idx]
+            if len(idx) > 8:
+                raise ValueErr(msg="at most 8 visible observation rows")
+            d.n_obs = len(idx)
+            for k, x in enumerate(idx):
+                d.obs_idx[k] = x
+        if noise_std is not None:
+            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))[:2]):
+                d.noise_std[k] = float(x)
+        if hasattr(params, "detach"):
+            params = params.detach().to("cpu").numpy()
+        flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+        self._check(self._lib.vs_set_policy_rnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
+                    "vs_set_policy_rnn")
+        self._rnn_hs = d.n_layers * d.hidden * (2 if d.cell == L.VS_RNN_LSTM else 1)
+
+    def set_policy_hidden_record(self, width):
+        """Record the policy's hidden state before every recorded step (width floats per env; 0 = off)"""
+        self._check(self._lib.vs_set_policy_hidden_record(self._h, int(width)), "vs_set_policy_hidden_record")
+        self._hrec_width = int(width)
+
+    def record_hidden(self, hidden, row=None):
+        """The caller's hidden state ([N, W] device float32) into row `row` of the hidden-state record plane; row=None: the
+        device-side row counter of step_record (not advanced: call before the step_record of the same step)"""
+        if not hidden.is_cuda or str(hidden.dtype) != "torch.float32" or hidden.dim() != 2 or hidden.shape[0] != self.n_envs:
+            raise TypeErr(msg="hidden must be an [N, W] float32 tensor on the GPU")
+        self._check(self._lib.vs_record_hidden(self._h, C.c_void_p(hidden.data_ptr()), hidden.stride(0), hidden.stride(1),
+                                               -1 if row is None else int(row)), "vs_record_hidden")
+
+    def policy_hidden(self):
+        """Zero-copy torch view [Hp, ld] of the recurrent policy's running hidden state (VS_POLICY_HIDDEN)"""
+        import torch
+
+        hs = getattr(self, "_rnn_hs", 0)
+        ptr = self._lib.vs_get(self._h, L.VS_POLICY_HIDDEN)
+        if not ptr or not hs:
+            raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
+        return torch.as_tensor(_DevArray(ptr, (hs, self.ld), "<f4", self), device=f"cuda:{self.device}")
+
+    def hidden_record_tensor(self):
+        """Zero-copy torch view [capacity, W, ld] of the hidden-state record plane (VS_POLICY_HIDDEN_REC)"""
+        import torch
+
+        w = getattr(self, "_hrec_width", 0)
+        ptr = self._lib.vs_get(self._h, L.VS_POLICY_HIDDEN_REC)
+        if not ptr or not w:
+            raise ValueErr(msg="no hidden-state record plane (set_policy_hidden_record and set_traj_capacity)")
+        return torch.as_tensor(_DevArray(ptr, (self._traj_cap, w, self.ld), "<f4", self), device=f"cuda:{self.device}")
 
     def step_policy(self, k_steps=1, record=False, noise_seed=0):
         """k_steps env steps in one launch with the network of set_policy_fnn in the loop (rollout() with act = policy(obs))"""
