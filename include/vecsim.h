@@ -328,6 +328,17 @@ int vs_set_policy_hidden_record(vs_handle h, int width);
  * hidden[i * env_stride + j * dim_stride], width units) into row `row` of VS_POLICY_HIDDEN_REC; row < 0: the device-side
  * counter of vs_step_record, NOT advanced -- call it before the vs_step_record of the same step (captured graphs replay it) */
 int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64_t dim_stride, int row);
+/* A population for vs_step_policy: n_sets parameter vectors of the policy last set by vs_set_policy_fnn / vs_set_policy_rnn
+ * (same architecture; vector s at params + s * n_params, each laid out like that call's `params`; host or device memory,
+ * copied and packed on the device).  lane_set[i] (host, n entries) = the set lane i runs, or -1: the lane takes no part.
+ * params == NULL removes the population (the single policy of the last vs_set_policy_* call applies again).
+ * Every aligned group of 64 lanes names one set or is all -1 (VS_ERR_ARG otherwise; also for a wrong n_params or a set id
+ * >= n_sets); without a policy VS_ERR_STATE.  The 256-env shapes of vs_set_policy_shape need every aligned group of 256 lanes
+ * to name one set: the automatic choice falls back to shape 0, a pinned shape 1 or 2 makes vs_step_policy return
+ * VS_ERR_STATE.  With a population vs_step_policy records (record != 0) and runs with auto-reset off (VS_ERR_STATE
+ * otherwise); it leaves the -1 lanes alone -- no step, no record row written -- and vs_rollout_lengths reports 0 for them
+ * (also after a vs_reset).  vs_set_policy_fnn / vs_set_policy_rnn (a NULL desc included) remove the population. */
+int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params, int n_sets, const int32_t* lane_set);
 /* The recorded steps of lanes 0 .. n_lanes - 1 (rows 0 .. of VS_TRAJ_REC, vs_set_record_mode's layout) as ROLLOUTS in one row-major
  * matrix rows[total + n_lanes][F] (F = vs_traj_layout's record width, device memory): rollout j = steps 0 .. lengths[j] - 1 of
  * lane j, the rollouts one after the other, starts[j] = lengths[0] + .. + lengths[j - 1] (both int64, device memory).

@@ -21,7 +21,7 @@ from .vec_env import MixedVecSimEnv, VecSimEnv, env_dims, nominal_params, param_
 from .wrappers import (ActDelayWrapper, ActNormWrapper, DomainRandWrapper, DomainRandWrapperBuffer,  # noqa: F401
                        DomainRandWrapperLive, EnvWrapper, EnvWrapperAct, EnvWrapperObs, FusedChain,
                        GaussianActNoiseWrapper, GaussianObsNoiseWrapper, ObsNormWrapper, ObsPartialWrapper, all_envs,
-                       fuse_wrappers, inner_env, typed_env)
+                       fuse_wrappers, inner_env, remove_all_dr_wrappers, remove_env, typed_env)
 
 inf = float("inf")
 
@@ -32,6 +32,10 @@ def __getattr__(name):
         from . import sampling
 
         return getattr(sampling, name)
+    if name in ("ParameterExploringSampler", "ParameterSample", "ParameterSamplingResult"):
+        from . import parameter_exploration
+
+        return getattr(parameter_exploration, name)
     if name in ("DummyPolicy", "IdlePolicy", "Policy", "FNN", "FNNPolicy", "NormalActNoiseExplStrat", "fnn_kernel_spec",
                 "RecurrentPolicy", "RNNPolicy", "GRUPolicy", "LSTMPolicy", "rnn_kernel_spec"):
         from . import policies

@@ -84,6 +84,7 @@ _SIGNATURES = {
     "vs_set_policy_rnn": (C.c_int, [_P, C.POINTER(RnnDesc), _P, C.c_int64]),
     "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
     "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),
+    "vs_set_policy_population": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "vs_rollout_lengths": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "vs_pack_traj": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vs_rollout_variant": (C.c_int, [_P]),

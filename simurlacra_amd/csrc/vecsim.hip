@@ -23,11 +23,18 @@ __global__ __launch_bounds__(256) void k_zero_hidden(float* __restrict__ hid, in
     for (int j = 0; j < rows; ++j) hid[(size_t)j * ld + i] = 0.f;
 }
 
-// vs_rollout_lengths: per lane, the first recorded step whose done bit is set (words [t / 32][ld], bit t % 32)
+// vs_rollout_lengths: per lane, the first recorded step whose done bit is set (words [t / 32][ld], bit t % 32); a lane of a
+// population's inert group (wg_set[i / 64] < 0) has no rollout: 0
 __global__ __launch_bounds__(256) void k_rollout_lengths(const uint32_t* __restrict__ words, size_t ld, int n, int t_steps,
-                                                         long long* __restrict__ lengths, uint8_t* __restrict__ done_last) {
+                                                         long long* __restrict__ lengths, uint8_t* __restrict__ done_last,
+                                                         const int* __restrict__ wg_set) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (wg_set && wg_set[i >> 6] < 0) {
+        lengths[i] = 0;
+        done_last[i] = 0;
+        return;
+    }
     const int nw = (t_steps + 31) / 32;
     int first = -1;
     for (int w = 0; w < nw && first < 0; ++w) {
@@ -37,6 +44,17 @@ __global__ __launch_bounds__(256) void k_rollout_lengths(const uint32_t* __restr
     }
     lengths[i] = first < 0 ? (long long)t_steps : (long long)first + 1;
     done_last[i] = first >= 0;
+}
+
+// vs_set_policy_population: set s of the caller's vectors (n_params floats each) into the packed layout of the policy's
+// packer, dst[s * stride + q] = map[q] < 0 ? 0 : src[s * n_params + map[q]] for q < stride (map has `slots` <= stride entries)
+__global__ __launch_bounds__(256) void k_pack_population(const float* __restrict__ src, int64_t n_params, int n_sets,
+                                                         const int* __restrict__ map, int slots, float* __restrict__ dst, int64_t stride) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= stride) return;
+    const int m = q < slots ? map[q] : -1;
+    for (int64_t s = blockIdx.y; s < n_sets; s += gridDim.y)
+        dst[s * stride + q] = m < 0 ? 0.f : src[s * n_params + m];
 }
 
 __global__ void k_count_err(const uint8_t* err, int n, unsigned long long* out) {
@@ -447,6 +465,8 @@ int vs_destroy(vs_handle h) {
     if (h->fnn.w) (void)hipFree((void*)h->fnn.w);
     if (h->rnn.w) (void)hipFree((void*)h->rnn.w);
     if (h->rnn.hid) (void)hipFree(h->rnn.hid);
+    if (h->pop.w) (void)hipFree((void*)h->pop.w);
+    if (h->pop.wg_set) (void)hipFree((void*)h->pop.wg_set);
     if (h->d_hrec) (void)hipFree(h->d_hrec);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -845,11 +865,28 @@ int vs_step_random(vs_handle h, uint64_t seed, int k_steps, int record) {
     return VS_OK;
 }
 
+static int drop_pop(vs_handle h) {
+    if (h->pop.w) HIPCHK(h, hipFree((void*)h->pop.w));
+    if (h->pop.wg_set) HIPCHK(h, hipFree((void*)h->pop.wg_set));
+    h->pop = Pop{};
+    h->pop_sets = 0;
+    h->pop_g256 = h->pop_inert = false;
+    return VS_OK;
+}
+
 static int drop_rnn(vs_handle h) {
     if (h->rnn.w) HIPCHK(h, hipFree((void*)h->rnn.w));
     if (h->rnn.hid) HIPCHK(h, hipFree(h->rnn.hid));
     h->rnn = Rnn{};
     return VS_OK;
+}
+
+// the packed vector of one policy from its index map (packed slot -> source index, -1: zero padding)
+static std::vector<float> pack_by_map(const std::vector<int>& map, const std::vector<float>& src) {
+    std::vector<float> pk(map.size(), 0.f);
+    for (size_t q = 0; q < map.size(); ++q)
+        if (map[q] >= 0) pk[q] = src[(size_t)map[q]];
+    return pk;
 }
 
 int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params, int64_t n_params) {
@@ -859,6 +896,9 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }
     h->fnn = Fnn{};
     if (int rc = drop_rnn(h)) return rc;  // one in-kernel policy at a time
+    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
+    h->pol_map.clear();
+    h->pol_n_params = 0;
     if (!desc) return VS_OK;
     const EnvInfo& ei = ENV_INFO[h->type];
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: the discrete-action family takes no network policy");
@@ -905,26 +945,31 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
         if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: noise_std must be >= 0");
         if (f.noise_std[j] > 0.f) f.noisy = 1;
     }
-    // torch layout -> transposed, zero-padded rows: unit j of layer l reads Wt_l[k][j], contiguous over j (scalar-load friendly)
-    std::vector<float> src((size_t)need), pk((size_t)off, 0.f);
+    // torch layout -> transposed, zero-padded rows: unit j of layer l reads Wt_l[k][j], contiguous over j (scalar-load friendly);
+    // built as an index map (packed slot -> source index) that vs_set_policy_population reuses on the device
+    std::vector<float> src((size_t)need);
+    std::vector<int> map((size_t)off, -1);
     HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-    size_t q = 0;
+    int q = 0;
     last = f.in_dim;
     for (int l = 0; l < f.n_hidden; ++l) {
         for (int j = 0; j < f.hidden[l]; ++j)
-            for (int k = 0; k < last; ++k) pk[(size_t)f.off_w[l] + (size_t)k * FNN_W + j] = src[q++];
-        for (int j = 0; j < f.hidden[l]; ++j) pk[(size_t)f.off_b[l] + j] = src[q++];
+            for (int k = 0; k < last; ++k) map[(size_t)f.off_w[l] + (size_t)k * FNN_W + j] = q++;
+        for (int j = 0; j < f.hidden[l]; ++j) map[(size_t)f.off_b[l] + j] = q++;
         last = f.hidden[l];
     }
     for (int j = 0; j < ei.A; ++j)
-        for (int k = 0; k < last; ++k) pk[(size_t)f.off_w[f.n_hidden] + (size_t)j * FNN_W + k] = src[q++];
-    for (int j = 0; j < ei.A; ++j) pk[(size_t)f.off_b[f.n_hidden] + j] = src[q++];
+        for (int k = 0; k < last; ++k) map[(size_t)f.off_w[f.n_hidden] + (size_t)j * FNN_W + k] = q++;
+    for (int j = 0; j < ei.A; ++j) map[(size_t)f.off_b[f.n_hidden] + j] = q++;
+    const std::vector<float> pk = pack_by_map(map, src);
     float* dw = nullptr;
     HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
     hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_fnn: upload", e); }
     f.w = dw;
     h->fnn = f;
+    h->pol_map = std::move(map);
+    h->pol_n_params = need;
     return VS_OK;
 }
 
@@ -935,6 +980,9 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     if (int rc = drop_rnn(h)) return rc;
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
     h->fnn = Fnn{};
+    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
+    h->pol_map.clear();
+    h->pol_n_params = 0;
     if (!desc) return VS_OK;
     const EnvInfo& ei = ENV_INFO[h->type];
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: the discrete-action family takes no network policy");
@@ -979,23 +1027,26 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     off += ei.A * f.hp + 4;
     if (n_params != need) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: parameter count does not match the cell, layers and sizes");
     f.lds_rows = (f.n_layers * (lstm ? 2 : 1) + f.n_layers) * f.hp;
-    // torch order -> per unit blocks, gate-interleaved rows (the kernel reads G consecutive floats per input)
-    std::vector<float> src((size_t)need), pk((size_t)off, 0.f);
+    // torch order -> per unit blocks, gate-interleaved rows (the kernel reads G consecutive floats per input); an index map
+    // as in vs_set_policy_fnn
+    std::vector<float> src((size_t)need);
+    std::vector<int> map((size_t)off, -1);
     HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-    size_t q = 0;
+    int q = 0;
     for (int l = 0; l < f.n_layers; ++l) {
         const int in = l == 0 ? f.n_vis : f.hidden, inp = l == 0 ? RNN_XP : f.hp;
         auto unit = [&](int row) { return (size_t)f.off[l] + (size_t)(row % f.hidden) * f.blk[l]; };  // row = g H + j of torch
         for (int r = 0; r < G * f.hidden; ++r)  // weight_ih [G H][in]
-            for (int k = 0; k < in; ++k) pk[unit(r) + (size_t)k * G + r / f.hidden] = src[q++];
+            for (int k = 0; k < in; ++k) map[unit(r) + (size_t)k * G + r / f.hidden] = q++;
         for (int r = 0; r < G * f.hidden; ++r)  // weight_hh [G H][H]
-            for (int k = 0; k < f.hidden; ++k) pk[unit(r) + (size_t)(inp + k) * G + r / f.hidden] = src[q++];
-        for (int r = 0; r < G * f.hidden; ++r) pk[unit(r) + (size_t)(inp + f.hp) * G + r / f.hidden] = src[q++];      // bias_ih
-        for (int r = 0; r < G * f.hidden; ++r) pk[unit(r) + (size_t)(inp + f.hp) * G + G + r / f.hidden] = src[q++];  // bias_hh
+            for (int k = 0; k < f.hidden; ++k) map[unit(r) + (size_t)(inp + k) * G + r / f.hidden] = q++;
+        for (int r = 0; r < G * f.hidden; ++r) map[unit(r) + (size_t)(inp + f.hp) * G + r / f.hidden] = q++;      // bias_ih
+        for (int r = 0; r < G * f.hidden; ++r) map[unit(r) + (size_t)(inp + f.hp) * G + G + r / f.hidden] = q++;  // bias_hh
     }
     for (int j = 0; j < ei.A; ++j)
-        for (int k = 0; k < f.hidden; ++k) pk[(size_t)f.off_o + (size_t)j * f.hp + k] = src[q++];
-    for (int j = 0; j < ei.A; ++j) pk[(size_t)f.off_o + (size_t)ei.A * f.hp + j] = src[q++];
+        for (int k = 0; k < f.hidden; ++k) map[(size_t)f.off_o + (size_t)j * f.hp + k] = q++;
+    for (int j = 0; j < ei.A; ++j) map[(size_t)f.off_o + (size_t)ei.A * f.hp + j] = q++;
+    const std::vector<float> pk = pack_by_map(map, src);
     float* dw = nullptr;
     HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
     hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -1006,6 +1057,8 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     if (e == hipSuccess) e = hipMemset(f.hid, 0, hb);
     if (e != hipSuccess) { (void)hipFree(dw); if (f.hid) (void)hipFree(f.hid); return fail(h, VS_ERR_HIP, "vs_set_policy_rnn: hidden state", e); }
     h->rnn = f;
+    h->pol_map = std::move(map);
+    h->pol_n_params = need;
     return VS_OK;
 }
 
@@ -1034,8 +1087,78 @@ int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64
     return VS_OK;
 }
 
+int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params, int n_sets, const int32_t* lane_set) {
+    if (!h) return VS_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still read the sets this replaces)
+    if (!params) return drop_pop(h);
+    if (!h->fnn.w && !h->rnn.w) return fail(h, VS_ERR_STATE, "vs_set_policy_population: no policy set (vs_set_policy_fnn / vs_set_policy_rnn)");
+    if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, "vs_set_policy_population: parameter count does not match the policy's");
+    if (n_sets < 1 || !lane_set) return fail(h, VS_ERR_ARG, "vs_set_policy_population: n_sets >= 1 and a lane table");
+    // the set of every aligned group of 64 lanes (groups past n_envs: -1), and whether groups of 256 agree as well
+    const int64_t n = h->d.n, ng = (int64_t)h->d.ld / 64;
+    std::vector<int> wg((size_t)ng, -1);
+    bool inert = false, g256 = true;
+    for (int64_t g = 0; g * 64 < n; ++g) {
+        const int s0 = lane_set[g * 64];
+        for (int64_t i = g * 64; i < std::min(n, g * 64 + 64); ++i) {
+            if (lane_set[i] < -1 || lane_set[i] >= n_sets) return fail(h, VS_ERR_ARG, "vs_set_policy_population: a set id outside -1 .. n_sets - 1");
+            if (lane_set[i] != s0) return fail(h, VS_ERR_ARG, "vs_set_policy_population: every aligned group of 64 lanes must name one set (or be all -1)");
+        }
+        wg[(size_t)g] = s0;
+        inert |= s0 < 0;
+        if ((g & 3) != 0 && s0 != wg[(size_t)(g & ~3)]) g256 = false;  // (groups past n_envs run as invalid lanes of their 256)
+    }
+    if (int rc = drop_pop(h)) return rc;  // (a refused call above leaves the population as it was)
+    // pack on the device: the policy packer's index map, one gather per set into rows of `stride` floats (a multiple of 64:
+    // every set starts on its own 256-byte boundary)
+    const int slots = (int)h->pol_map.size();
+    const int64_t stride = ((int64_t)slots + 63) / 64 * 64;
+    const float* src = params;
+    float *tmp = nullptr, *dw = nullptr;
+    int *dmap = nullptr, *dwg = nullptr;
+    hipError_t e = hipSuccess;
+    auto cleanup = [&]() {
+        if (tmp) (void)hipFree(tmp);
+        if (dmap) (void)hipFree(dmap);
+    };
+    if (!is_device_ptr(params)) {
+        e = hipMalloc((void**)&tmp, (size_t)n_sets * n_params * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(tmp, params, (size_t)n_sets * n_params * sizeof(float), hipMemcpyHostToDevice);
+        src = tmp;
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&dmap, (size_t)slots * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dmap, h->pol_map.data(), (size_t)slots * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&dw, (size_t)n_sets * stride * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dwg, (size_t)ng * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dwg, wg.data(), (size_t)ng * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_pack_population, dim3((unsigned)((stride + 255) / 256), (unsigned)std::min(n_sets, 65535)), dim3(256), 0,
+                           h->stream, src, n_params, n_sets, (const int*)dmap, slots, dw, stride);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (the temporaries go below)
+    cleanup();
+    if (e != hipSuccess) {
+        if (dw) (void)hipFree(dw);
+        if (dwg) (void)hipFree(dwg);
+        return fail(h, VS_ERR_HIP, "vs_set_policy_population: upload / pack", e);
+    }
+    h->pop = Pop{dw, dwg, stride};
+    h->pop_sets = n_sets;
+    h->pop_g256 = g256;
+    h->pop_inert = inert;
+    return VS_OK;
+}
+
 int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
     if (!h || k_steps < 1) return fail(h, VS_ERR_ARG, "vs_step_policy: bad argument");
+    if (h->pop.w) {  // the population kernels exist for sampling runs only: auto-reset off, records on
+        if (h->auto_reset)
+            return fail(h, VS_ERR_STATE, h->pop_inert ? "vs_step_policy: auto-reset with -1 lanes in the population table"
+                                                      : "vs_step_policy: a population runs with auto-reset off");
+        if (!record) return fail(h, VS_ERR_STATE, "vs_step_policy: a population runs with records on");
+    }
     if (h->rnn.w) {
         if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
         if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
@@ -1043,7 +1166,11 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
             return fail(h, VS_ERR_STATE, "vs_step_policy: the hidden-state record width differs from the policy's hidden size");
         HIPCHK(h, hipSetDevice(h->device));
         h->rnn.hrec = h->d_hrec;
-        DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
+        if (h->pop.w) {
+            DISPATCH_ENV(h->type, Launch<E>::rollout_rnn_pop(h, k_steps, h->record_mode, noise_seed));
+        } else {
+            DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
+        }
         HIPCHK(h, hipGetLastError());
         return VS_OK;
     }
@@ -1051,6 +1178,18 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
     if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
     if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->pop.w) {
+        // the 256-env shapes take one set per workgroup of 256 lanes: a table that is uniform in groups of 64 only runs shape 0
+        // when the choice is automatic, and is refused when shape 1 or 2 is pinned
+        int shape = fnn_shape(h);
+        if (shape != 0 && !h->pop_g256) {
+            if (h->policy_shape > 0) return fail(h, VS_ERR_STATE, "vs_step_policy: the pinned 256-env shape needs a population table uniform in groups of 256 lanes");
+            shape = 0;
+        }
+        DISPATCH_ENV(h->type, Launch<E>::rollout_fnn_pop(h, k_steps, h->record_mode, noise_seed, shape));
+        HIPCHK(h, hipGetLastError());
+        return VS_OK;
+    }
     DISPATCH_ENV(h->type, Launch<E>::rollout_fnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
@@ -1062,7 +1201,7 @@ int vs_rollout_lengths(vs_handle h, int n_lanes, int t_steps, int64_t* lengths, 
     if (!h->d.traj_done || t_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_rollout_lengths: more steps than vs_set_traj_capacity holds");
     HIPCHK(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(k_rollout_lengths, dim3((unsigned)((n_lanes + 255) / 256)), dim3(256), 0, h->stream, (const uint32_t*)h->d.traj_done,
-                       (size_t)h->d.ld, n_lanes, t_steps, (long long*)lengths, done_last);
+                       (size_t)h->d.ld, n_lanes, t_steps, (long long*)lengths, done_last, (const int*)h->pop.wg_set);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -999,9 +999,18 @@ __device__ __forceinline__ void wave_lds_fence() {
 //   * output layer: 32 products per lane against the weights in accumulator order, the two half-waves added through LDS.
 // 64 x 64 hidden-to-hidden: 64 MFMAs of 64 cycles per wave and 32 envs instead of 16 broadcast LDS reads + 64 FMAs per env.
 typedef float fnn_acc __attribute__((ext_vector_type(16)));
-template <class E, bool AR, int REC, int NHID, int NE, bool MF = false>
+// A population of parameter vectors of one architecture (vs_set_policy_population): set s at w + s * stride (stride a multiple
+// of 64 floats, every set on its own 256-byte boundary, each packed like the single policy's Fnn::w / Rnn::w), and the set of
+// every aligned group of 64 lanes (-1: the group takes no part).  The POP instantiations of k_rollout_fnn / k_rollout_rnn read
+// their workgroup's entry once and take that set's vector as the base of every weight read; the others never look at it.
+struct Pop {
+    const float* w;
+    const int* wg_set;  // [ld / 64]
+    int64_t stride;
+};
+template <class E, bool AR, int REC, int NHID, int NE, bool MF = false, bool POP = false>
 __global__ __launch_bounds__(64 * fnn_waves(NHID)) void k_rollout_fnn(Task T, Dev d, Fnn P, int k_steps, uint64_t reset_seed,
-                                                                      uint64_t noise_seed) {
+                                                                      uint64_t noise_seed, Pop pop) {
     static_assert(NHID >= 1 && NHID <= FNN_MAXH, "hidden layers");
     static_assert(NE == 64 || NE == 256, "envs per workgroup");
     static_assert(NE / 64 <= fnn_waves(NHID), "one wave per 64 envs owns them");
@@ -1022,6 +1031,11 @@ __global__ __launch_bounds__(64 * fnn_waves(NHID)) void k_rollout_fnn(Task T, De
     const size_t ld = d.ld;
     const size_t rec0 = (size_t)d.traj_t0;
     const bool valid = i < d.n;
+    if constexpr (POP) {  // the workgroup's parameter set: every read of P.w below takes it as its base; -1: nothing to do
+        const int set = __builtin_amdgcn_readfirstlane(pop.wg_set[blockIdx.x * (NE / 64)]);  // (uniform by construction)
+        if (set < 0) return;
+        P.w = pop.w + (size_t)set * (size_t)pop.stride;
+    }
 
     // ---- unit `lane` of every layer: its weight rows, for the whole launch
     float w1[FNN_XS], wh[NHID > 1 ? NHID - 1 : 1][FNN_W], bh[NHID], wo[E::A];
@@ -1405,13 +1419,21 @@ struct Rnn {
     int lds_rows;    // rows of 64 floats of LDS per workgroup: (n_layers (1 + LSTM) + n_layers) hp
 };
 
-template <class E, bool AR, int REC, int G>
-__global__ __launch_bounds__(64) void k_rollout_rnn(Task T, Dev d, Rnn P, int k_steps, uint64_t reset_seed, uint64_t noise_seed) {
+template <class E, bool AR, int REC, int G, bool POP = false>
+__global__ __launch_bounds__(64) void k_rollout_rnn(Task T, Dev d, Rnn P, int k_steps, uint64_t reset_seed, uint64_t noise_seed,
+                                                    Pop pop) {
     static_assert(G == 1 || G == 3 || G == 4, "RNN, GRU or LSTM");
     extern __shared__ float l_rnn[];  // [row][64]: state rows h (n_layers hp), c (LSTM, n_layers hp), then h' rows (n_layers hp)
     typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
     constexpr bool UNI = false;
-    const cfp W = (cfp)P.w;
+    const float* w0 = P.w;
+    if constexpr (POP) {  // the workgroup's parameter set moves the scalar-load base (P itself stays the kernel argument: its
+                          // per-layer tables are indexed at run time); -1: nothing to do
+        const int set = __builtin_amdgcn_readfirstlane(pop.wg_set[blockIdx.x]);  // (uniform by construction)
+        if (set < 0) return;
+        w0 = pop.w + (size_t)set * (size_t)pop.stride;
+    }
+    const cfp W = (cfp)w0;
     const int lane = threadIdx.x;
     const int i = blockIdx.x * 64 + lane;
     const size_t ld = d.ld;
@@ -2602,6 +2624,12 @@ struct vs_env {
     int hrec_width = 0;           // vs_set_policy_hidden_record: floats per env and step of the hidden-state record plane, 0 off
     float* d_hrec = nullptr;      // ... the plane, f32 [traj_cap][hrec_width][ld]
     int rollout_variant = -1;     // vs_set_rollout_variant: -1 automatic, 0 k_rollout, 1 k_rollout_ws<256>, 2 k_rollout_ws<64>, 3 / 4 the three-role kernel in 64 / 256-env workgroups
+    vs::Pop pop{};                // vs_set_policy_population: the packed sets and the per-64-lane set table (pop.w == nullptr: none)
+    int pop_sets = 0;             // ... number of sets
+    bool pop_g256 = false;        // ... every aligned group of 256 lanes names one set (the 256-env shapes are allowed)
+    bool pop_inert = false;       // ... some lane of the table is -1
+    std::vector<int> pol_map;     // the policy packer's index map: packed slot -> source index of the parameter vector, -1 zero
+    int64_t pol_n_params = 0;     // ... and the parameter count of the policy of the last vs_set_policy_fnn / vs_set_policy_rnn
     int policy_shape = -1;        // vs_set_policy_shape: -1 automatic, 0 / 1: k_rollout_fnn in 64- / 256-env workgroups, 2: 256-env + matrix cores
     int n_cu = 256;               // compute units of the device (256 on MI355X)
     bool auto_reset = false;
@@ -2634,6 +2662,8 @@ struct Launch {
     static void rollout(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec);
     static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy
     static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy, recurrent policy
+    static void rollout_fnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed, int shape);  // ... with a population (POP):
+    static void rollout_rnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed);             //     auto-reset off, rec 1 | 2
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -2795,11 +2825,10 @@ void Launch<E>::rollout(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec) {
     }
 }
 
-template <class E>
-void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
-#define LF(AR, REC, NH, NE, MF) hipLaunchKernelGGL((k_rollout_fnn<E, AR, REC, NH, NE, MF>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)), 0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed)
-#define LFR(AR, NH, NE, MF) { if (rec == 0) LF(AR, 0, NH, NE, MF); else if (rec == 1) LF(AR, 1, NH, NE, MF); else LF(AR, 2, NH, NE, MF); }
-#define LFA(NH, NE, MF) { if (h->auto_reset) LFR(true, NH, NE, MF) else LFR(false, NH, NE, MF) }
+#endif  // VS_TU_FAMILY
+
+// the shape vs_step_policy evaluates a feed-forward network in (vs_set_policy_shape; the C-ABI checks it against a population)
+static inline int fnn_shape(const vs_env* h) {
     // 256-env workgroups beyond 128 envs per compute unit, with the hidden layers on the matrix cores (one and two hidden layers;
     // measured: 65 536 QQube envs, 64 x 64 tanh).  VS_FNN_SHAPE=64|256|mfma pins the shape (experiments, tests).
     static const char* force = getenv("VS_FNN_SHAPE");
@@ -2812,6 +2841,16 @@ void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
     if (force) shape = force[0] == 'm' ? 2 : force[0] == '2' ? 1 : 0;
     if (h->policy_shape >= 0) shape = h->policy_shape;
     if (h->fnn.n_hidden > 2) shape = 0;
+    return shape;
+}
+#ifdef VS_TU_FAMILY
+
+template <class E>
+void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
+#define LF(AR, REC, NH, NE, MF) hipLaunchKernelGGL((k_rollout_fnn<E, AR, REC, NH, NE, MF>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)), 0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed, Pop{})
+#define LFR(AR, NH, NE, MF) { if (rec == 0) LF(AR, 0, NH, NE, MF); else if (rec == 1) LF(AR, 1, NH, NE, MF); else LF(AR, 2, NH, NE, MF); }
+#define LFA(NH, NE, MF) { if (h->auto_reset) LFR(true, NH, NE, MF) else LFR(false, NH, NE, MF) }
+    const int shape = fnn_shape(h);
     switch (h->fnn.n_hidden) {
         case 1: if (shape == 2) LFA(1, 256, true) else if (shape == 1) LFA(1, 256, false) else LFA(1, 64, false) break;
         case 2: if (shape == 2) LFA(2, 256, true) else if (shape == 1) LFA(2, 256, false) else LFA(2, 64, false) break;
@@ -2820,6 +2859,22 @@ void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
     }
 #undef LFA
 #undef LFR
+#undef LF
+}
+
+// the population: the same kernels with POP (every workgroup its set of h->pop), auto-reset off and records on only; `shape` is
+// fnn_shape(h) as vs_step_policy admitted it for the set table
+template <class E>
+void Launch<E>::rollout_fnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed, int shape) {
+#define LF(REC, NH, NE, MF) hipLaunchKernelGGL((k_rollout_fnn<E, false, REC, NH, NE, MF, true>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)), 0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed, h->pop)
+#define LFA(NH, NE, MF) { if (rec == 1) LF(1, NH, NE, MF); else LF(2, NH, NE, MF); }
+    switch (h->fnn.n_hidden) {
+        case 1: if (shape == 2) LFA(1, 256, true) else if (shape == 1) LFA(1, 256, false) else LFA(1, 64, false) break;
+        case 2: if (shape == 2) LFA(2, 256, true) else if (shape == 1) LFA(2, 256, false) else LFA(2, 64, false) break;
+        case 3: LFA(3, 64, false) break;
+        default: LFA(4, 64, false) break;
+    }
+#undef LFA
 #undef LF
 }
 
@@ -2834,13 +2889,32 @@ void Launch<E>::rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
         (void)hipFuncSetAttribute((const void*)&k_rollout_rnn<E, AR, REC, G>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                   (int)lds);                                                                              \
         hipLaunchKernelGGL((k_rollout_rnn<E, AR, REC, G>), dim3((unsigned)(h->d.ld / 64)), dim3(64), lds, h->stream,        \
-                           h->task, h->d, P, k, h->ar_seed, noise_seed);                                                  \
+                           h->task, h->d, P, k, h->ar_seed, noise_seed, Pop{});                                           \
     }
 #define LRR(AR, G) { if (rec == 0) LR(AR, 0, G) else if (rec == 1) LR(AR, 1, G) else LR(AR, 2, G) }
 #define LRA(G) { if (h->auto_reset) LRR(true, G) else LRR(false, G) }
     const int g = rnn_gates(P.cell);
     if (g == 1) LRA(1) else if (g == 3) LRA(3) else LRA(4)
 #undef LRA
+#undef LRR
+#undef LR
+}
+
+template <class E>
+void Launch<E>::rollout_rnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed) {
+    const size_t lds = (size_t)h->rnn.lds_rows * 64 * sizeof(float);
+    Rnn P = h->rnn;
+    if (h->hrec_width != P.hs) P.hrec = nullptr;
+#define LR(REC, G)                                                                                                        \
+    {                                                                                                                     \
+        (void)hipFuncSetAttribute((const void*)&k_rollout_rnn<E, false, REC, G, true>,                                    \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
+        hipLaunchKernelGGL((k_rollout_rnn<E, false, REC, G, true>), dim3((unsigned)(h->d.ld / 64)), dim3(64), lds,          \
+                           h->stream, h->task, h->d, P, k, h->ar_seed, noise_seed, h->pop);                               \
+    }
+#define LRR(G) { if (rec == 1) LR(1, G) else LR(2, G) }
+    const int g = rnn_gates(P.cell);
+    if (g == 1) LRR(1) else if (g == 3) LRR(3) else LRR(4)
 #undef LRR
 #undef LR
 }

@@ -269,6 +269,21 @@ def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, re
                         actions_applied=np.stack(act_app_hist), **extra)
 
 
+def fused_policy_specs(policy, fc, env_name):
+    """(fnn, rnn): the arguments of VecSimEnv.set_policy_fnn / set_policy_rnn when the fused kernel evaluates `policy` itself
+    (at most one of them), or (None, None).
+    A feed-forward network policy the kernel can evaluate itself (vs_step_policy): rollout() with act = policy(obs) fused like
+    the DummyPolicy path -- unless a wrapper pipeline (noise / delay / observation normalisation, FusedChain `fc`) is on.
+    A recurrent policy likewise (vs_set_policy_rnn): the hidden state kept on the device from step to step and recorded
+    before every step.  Not for the discrete-action family."""
+    plain_chain = (fc.delay == 0 and not np.any(fc.noise_std) and not np.any(fc.noise_mean) and not np.any(fc.var)
+                   and np.all(fc.scale == 1) and not np.any(fc.shift))
+    if not plain_chain or env_name == "bob-d":
+        return None, None
+    fnn = fnn_kernel_spec(policy)
+    return fnn, (rnn_kernel_spec(policy) if fnn is None else None)
+
+
 class ParallelRolloutSampler:
     """Drop-in for P/sampling/parallel_rollout_sampler.py:182-323 with the rollouts batched on the GPU.
 
@@ -390,8 +405,11 @@ class ParallelRolloutSampler:
         self._fc = fuse_wrappers(self.env)  # ActNorm / act noise / act delay / obs norm / obs noise / partial obs
         return v
 
-    def _run_batch(self, work, first_index, eval, packed_out=False, plain=False):
-        """run len(work) rollouts as lanes; returns List[StepSequence] in order (packed_out: one PackedRollouts)"""
+    def _run_batch(self, work, first_index, eval, packed_out=False, plain=False, population=None):
+        """run len(work) rollouts as lanes; returns List[StepSequence] in order (packed_out: one PackedRollouts).
+        population (ParameterExploringSampler): dict(params=[P, n_params], lane_set=[len(work)] int32, real=lane indices) --
+        the fused policy kernel runs set lane_set[j] in lane j (-1: an inert lane, no rollout); only the `real` lanes become
+        rollouts, in that order"""
         import torch
 
         n = len(work)
@@ -400,11 +418,11 @@ class ParallelRolloutSampler:
         # current stream for the duration of the batch (pointer 0 = the legacy default stream)
         v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
         try:
-            return self._run_batch_on_stream(v, work, first_index, eval, packed_out, plain)
+            return self._run_batch_on_stream(v, work, first_index, eval, packed_out, plain, population)
         finally:
             v.use_stream(None)
 
-    def _run_batch_on_stream(self, v, work, first_index, eval, packed_out=False, plain=False):
+    def _run_batch_on_stream(self, v, work, first_index, eval, packed_out=False, plain=False, population=None):
         import torch
 
         n = len(work)
@@ -469,20 +487,16 @@ class ParallelRolloutSampler:
         H = v.dims["H"]
         hid_t = v.tensor(L.VS_HIDDEN)[:, :n] if H else None
         use_fused = isinstance(self.policy, DummyPolicy)
-        # a feed-forward network policy the kernel can evaluate itself (vs_step_policy): rollout() with act = policy(obs)
-        # fused like the DummyPolicy path -- unless a wrapper pipeline (noise / delay / observation normalisation) is on
         fc = self._fc
-        plain_chain = (fc.delay == 0 and not np.any(fc.noise_std) and not np.any(fc.noise_mean) and not np.any(fc.var)
-                       and np.all(fc.scale == 1) and not np.any(fc.shift))
-        fnn = fnn_kernel_spec(self.policy) if (self._fuse_policy and plain_chain and not use_fused) else None
-        if fnn is not None and base.name == "bob-d":
-            fnn = None
-        # a recurrent policy the kernel can evaluate itself (vs_set_policy_rnn): the same fused path, the hidden state kept on the
-        # device from step to step and recorded before every step
-        rnn = rnn_kernel_spec(self.policy) if (self._fuse_policy and plain_chain and not use_fused and fnn is None) else None
-        if rnn is not None and base.name == "bob-d":
-            rnn = None
+        fnn, rnn = fused_policy_specs(self.policy, fc, base.name) if (self._fuse_policy and not use_fused) else (None, None)
         recurrent = bool(getattr(self.policy, "is_recurrent", False)) and not use_fused
+        if population is not None and fnn is None and rnn is None:
+            raise ValueErr(msg="a policy population needs a policy the fused kernel evaluates (fnn_kernel_spec / rnn_kernel_spec)")
+        # the lanes whose done flags end the launch loop: all of them, or a population's real lanes (inert lanes never step)
+        real_t = None if population is None else torch.as_tensor(np.asarray(population["real"], dtype=np.int64), device=dev)
+
+        def all_done():
+            return bool((done_t if real_t is None else done_t.index_select(0, real_t)).bool().all())
         W = int(self.policy.hidden_size) if recurrent else 0
         v.set_policy_hidden_record(0)
         state0 = st_t.t().clone()
@@ -520,6 +534,8 @@ class ParallelRolloutSampler:
             # policy.eval(), and StochasticActionExplStrat.forward samples action_dist_at(act).rsample() whatever the mode,
             # P/exploration/stochastic_action.py:80-96)
             v.set_policy_fnn(obs_idx=None if fc.keep.all() else np.flatnonzero(fc.keep), **fnn)
+            if population is not None:
+                v.set_policy_population(population["params"], population["lane_set"])
             v.set_record_mode(2 if full else 1)
             v.set_traj_capacity(T_cap)
             while t < T_cap:
@@ -527,7 +543,7 @@ class ParallelRolloutSampler:
                 v.set_traj_offset(t)
                 v.step_policy(k, record=True, noise_seed=lane_key ^ 0x8CB92BA72F3D8DD7)
                 t += k
-                if bool(done_t.bool().all()):  # one scalar sync per launch
+                if all_done():  # one scalar sync per launch
                     break
             v.set_traj_offset(0)
         elif rnn is not None:
@@ -536,6 +552,8 @@ class ParallelRolloutSampler:
             if hasattr(self.policy, "reset"):
                 self.policy.reset()
             v.set_policy_rnn(obs_idx=None if fc.keep.all() else np.flatnonzero(fc.keep), **rnn)
+            if population is not None:
+                v.set_policy_population(population["params"], population["lane_set"])
             v.set_record_mode(2 if full else 1)
             v.set_traj_capacity(T_cap)
             v.set_policy_hidden_record(W)
@@ -544,7 +562,7 @@ class ParallelRolloutSampler:
                 v.set_traj_offset(t)
                 v.step_policy(k, record=True, noise_seed=lane_key ^ 0x8CB92BA72F3D8DD7)
                 t += k
-                if bool(done_t.bool().all()):  # one scalar sync per launch
+                if all_done():  # one scalar sync per launch
                     break
             v.set_traj_offset(0)
         else:
@@ -684,13 +702,14 @@ class ParallelRolloutSampler:
         # generation of it, a third of this loop at 65 536 rollouts, and nothing built here is garbage)
         gc_was_on = gc.isenabled()
         gc.disable()
+        lanes = range(n) if population is None else np.asarray(population["real"]).tolist()  # (a population's inert lanes: none)
         try:
             ros = [packed(obs_p[off_o[j]:off_o[j + 1]], act_p[off_o[j]:off_o[j] + lens[j]], rew_p[off_o[j]:off_o[j] + lens[j]],
                           (name, pnames, params[j], first_index + j), done_last[j], dt, state0_h[j],
                           None if st_p is None else st_p[off_o[j]:off_o[j + 1]],
                           None if app_p is None else app_p[off_o[j]:off_o[j] + lens[j]],
                           hid_p[off_o[j]:off_o[j + 1], 0] if qcp else None,
-                          None if hid_h is None else hid_h[off_o[j]:off_o[j] + lens[j]]) for j in range(n)]
+                          None if hid_h is None else hid_h[off_o[j]:off_o[j] + lens[j]]) for j in lanes]
         finally:
             if gc_was_on:
                 gc.enable()

@@ -608,6 +608,36 @@ class VecSimEnv:
                     "vs_set_policy_rnn")
         self._rnn_hs = d.n_layers * d.hidden * (2 if d.cell == L.VS_RNN_LSTM else 1)
 
+    def set_policy_population(self, params, lane_set=None):
+        """A population of parameter vectors for step_policy (vs_set_policy_population): params [P, n_params] -- P vectors of the
+        policy of the last set_policy_fnn / set_policy_rnn, each in that call's torch order; a torch tensor (host or device) or
+        an array -- and lane_set [n_envs] the set every lane runs (-1: the lane takes no part; every aligned group of 64 lanes
+        names one set).  params=None removes the population."""
+        if params is None:
+            self._check(self._lib.vs_set_policy_population(self._h, None, 0, 0, None), "vs_set_policy_population")
+            return
+        keep = None
+        if hasattr(params, "detach"):
+            import torch
+
+            t = params.detach()
+            if t.is_cuda:
+                t = t.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+                torch.cuda.current_stream(self.device).synchronize()  # (the library packs it on its own stream)
+                keep, ptr, shape = t, t.data_ptr(), tuple(t.shape)
+            else:
+                params = t.numpy()
+        if keep is None:
+            keep = np.ascontiguousarray(np.asarray(params, dtype=np.float32))
+            ptr, shape = keep.ctypes.data, keep.shape
+        if len(shape) != 2:
+            raise ShapeErr(msg=f"params must be [n_sets, n_params], got shape {tuple(shape)}")
+        ls = np.ascontiguousarray(np.asarray(lane_set, dtype=np.int32).reshape(-1))
+        if ls.size != self.n_envs:
+            raise ShapeErr(msg=f"lane_set needs one entry per env ({self.n_envs}), got {ls.size}")
+        self._check(self._lib.vs_set_policy_population(self._h, C.c_void_p(ptr), int(shape[1]), int(shape[0]),
+                                                       ls.ctypes.data_as(C.c_void_p)), "vs_set_policy_population")
+
     def set_policy_hidden_record(self, width):
         """Record the policy's hidden state before every recorded step (width floats per env; 0 = off)"""
         self._check(self._lib.vs_set_policy_hidden_record(self._h, int(width)), "vs_set_policy_hidden_record")

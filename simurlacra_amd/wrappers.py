@@ -277,6 +277,32 @@ class DomainRandWrapperBuffer(DomainRandWrapper):
         self.vec.set_param_buffer(buf if on else None, self._selection)
 
 
+def remove_env(env, tp):
+    """The chain without its outermost wrapper of type `tp` (P/environment_wrappers/utils.py remove_env).  The wrappers
+    above the removed one are shallow copies: the caller's chain stays as it is."""
+    import copy
+
+    if not isinstance(env, EnvWrapper):
+        return env
+    if isinstance(env, tp):
+        return env.wrapped_env
+    inner = remove_env(env.wrapped_env, tp)
+    if inner is env.wrapped_env:
+        return env
+    outer = copy.copy(env)
+    outer._wrapped_env = inner
+    return outer
+
+
+def remove_all_dr_wrappers(env, verbose: bool = False):
+    """The chain without any DomainRandWrapper (P/environment_wrappers/utils.py remove_all_dr_wrappers)"""
+    while typed_env(env, DomainRandWrapper) is not None:
+        if verbose:
+            print(f"Removed {type(typed_env(env, DomainRandWrapper)).__name__} from the environment chain.")
+        env = remove_env(env, DomainRandWrapper)
+    return env
+
+
 class EnvWrapperAct(EnvWrapper):
     """Base of the wrappers that modify the action (P/environment_wrappers/base.py:288-330)."""
 
