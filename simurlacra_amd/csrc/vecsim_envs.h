@@ -92,25 +92,36 @@ __device__ __forceinline__ Dual<N> exp_neg_fast(const Dual<N>& x) {
 // Rounds 1-3 (kept behind -DVS_POLY_SINCOS): 3-term Cody-Waite reduction by pi/2 with FMAs (exact products), then the Cephes
 // minimax polynomials on [-pi/4, pi/4] -- 28 VALU instructions for both values against ~150 for the general-range library
 // sincosf (Payne-Hanek branch included), max error against fp64 over |x| <= 100: 9e-8 abs.  Shipped since the end of round 3:
-// the hardware's transcendental unit behind an exact reduction (below), 3.5e-7 abs (tests/test_gpu_parity.py).
+// the hardware's transcendental unit behind an exact reduction (below); since library 305 a reduction by pi, which holds sin(x)
+// near every k pi to a few ulp RELATIVE, <= 4e-7 abs overall (tests/test_gpu_near_equilibrium.py, tests/test_gpu_parity.py).
 // NaN / inf inputs give NaN in both forms (the error flag relies on that).
 __device__ __forceinline__ void sincos_fast(float x, float* sn, float* cs) {
 #ifndef VS_POLY_SINCOS
-    // The hardware's v_sin_f32 / v_cos_f32 (argument in revolutions) behind an EXACT two-term reduction to [-pi, pi]: 5 vector + 2
-    // transcendental instructions (~52 issue cycles) where the Cody-Waite reduction + two polynomials + quadrant selects below are 28
-    // (~112).  Maximum absolute error 3.8e-7 over |x| <= 70 rad against the polynomials' 9e-8 (scratch/ubench/hw_sincos_err.hip; the
-    // multiply by 1 / 2 pi alone, without the reduction, would add |x| x 6e-8) -- three ulp of a value near 1, a thirtieth of the
-    // 1e-5 relative the state trajectories are held to; every golden-vector and oracle parity test holds at its old tolerance.
-    // What it bought (end of round 3, same box): headline 1.67e11 -> 1.84e11, BASELINE config 4 (four sincos per step) 6.6e10 ->
-    // 9.1e10, config 3 1.04e11 -> 1.09e11, config 2 1.69e10 -> 1.79e10.  -DVS_POLY_SINCOS keeps the polynomial form (diagnostics).
+    // The hardware's v_sin_f32 / v_cos_f32 (argument in revolutions) behind an EXACT three-term reduction by pi to r in [-pi/2, pi/2]
+    // and a sign flip for odd quotients: 9 vector + 2 transcendental instructions where the Cody-Waite reduction + two polynomials +
+    // quadrant selects below are 28.  q = rint(x / pi) comes out of one FMA against 1.5 * 2^23, which leaves q's parity in the last
+    // mantissa bit of t (|x| < 2^22 pi).  Library 304 reduced by 2 pi to [-pi, pi] instead: next to x = +-pi, +-3pi (the upright
+    // equilibria of qq / qcp / pend) r / 2pi sat next to +-0.5, where one fp32 ulp of it is 6e-8 revolutions, so sin(x) had an
+    // absolute error floor of ~2e-7 however small it was -- 100 % relative at the fp32 neighbours of pi, a few percent on the
+    // first step from rest.  Here |rev| <= 1/4 and r is exact to an ulp of itself, so sin(x) near every k pi is held to the unit's
+    // own relative error (tests/test_gpu_near_equilibrium.py).  A pi/2 reduction with quadrant selects (cos near pi/2 + k pi
+    // relative too) cost the headline 10 % (1.88e11 -> 1.69e11, same box); no equilibrium of these environments sits there.
+    // What the unit bought at the end of round 3 (same box): headline 1.67e11 -> 1.84e11, BASELINE config 4 (four sincos per
+    // step) 6.6e10 -> 9.1e10.  -DVS_POLY_SINCOS keeps the polynomial form (diagnostics).
     {
-        const float TWOPI_HI = 6.28318548202514648f, TWOPI_LO = -1.74845553146951715e-07f, INV_2PI = 0.159154943091895336f;
-        float q = rintf(x * INV_2PI);
-        float r = fmaf(-q, TWOPI_HI, x);
-        r = fmaf(-q, TWOPI_LO, r);
-        float rev = r * INV_2PI;
-        *sn = __builtin_amdgcn_sinf(rev);
-        *cs = __builtin_amdgcn_cosf(rev);
+        // pi = PI_HI + PI_MID + PI_LO (twice the pi/2 terms below): the third term keeps r exact to an ulp of itself next to
+        // fp32(3 pi), 2.4e-8 from 3 pi, where two terms leave 5e-7 relative
+        const float PI_HI = 3.14159274101257324f, PI_MID = -8.74227765734758577e-08f, PI_LO = -3.43024902016399824e-15f;
+        const float INV_PI = 0.318309886183790672f, RND = 12582912.0f;  // RND = 1.5 * 2^23: t's ulp is 1
+        float t = fmaf(x, INV_PI, RND);
+        float q = t - RND;
+        float r = fmaf(-q, PI_HI, x);
+        r = fmaf(-q, PI_MID, r);
+        r = fmaf(-q, PI_LO, r);
+        float rev = r * 0.159154943091895336f;  // r / 2pi
+        unsigned flip = __float_as_uint(t) << 31;  // sign bit = parity of q: sin, cos (x) = (-1)^q sin, cos (r)
+        *sn = __uint_as_float(__float_as_uint(__builtin_amdgcn_sinf(rev)) ^ flip);
+        *cs = __uint_as_float(__float_as_uint(__builtin_amdgcn_cosf(rev)) ^ flip);
         return;
     }
 #endif
