@@ -1,14 +1,17 @@
-"""Compare the instruction streams of the fused rollout kernels between two builds of libvecsim (no GPU needed).
+"""Compare the instruction streams of the kernels of two builds of libvecsim (no GPU needed).
 
     python profiles/compare_isa.py OLD_OBJ_DIR NEW_OBJ_DIR [REGEX]
 
 OLD_OBJ_DIR / NEW_OBJ_DIR are the `build/` object directories of two in-tree builds (simurlacra_amd/csrc/build), e.g. one of
-the parent commit and one of the working tree.  Every kernel of the old build whose name matches REGEX (default: the
-k_rollout_fnn, k_rollout_rnn and k_rollout_ws families) must exist in the new build with the same instructions.  Addresses,
-encodings and branch-target labels are dropped (the kernels may sit elsewhere in the code object); branch offsets stay.
-Names are compared demangled, without the parameter list.  The POP template flag of k_rollout_fnn / k_rollout_rnn (the
-population kernels of vs_set_policy_population, default false) is dropped from the new names, so `k_rollout_fnn<.., MF, false>`
-of the new build is `k_rollout_fnn<.., MF>` of the old one.  Exits 1 on any difference.
+the parent commit and one of the working tree.  Every kernel whose name matches REGEX (default: every kernel) must exist in
+both builds with the same instructions: a kernel of the old build that the new one lacks is MISSING, one that only the new
+build has is NEW.  Addresses, encodings and branch-target labels are dropped (the kernels may sit elsewhere in the code
+object); branch offsets stay.  Names are compared demangled, without the parameter list.  Exits 1 on any difference.
+A kernel that differs is listed with its registers in both builds (VGPRs of which AGPRs -- vgpr_count of a gfx950 code object
+is the unified total --, SGPRs, VGPR / SGPR spills, scratch and LDS bytes, waves per SIMD = 512 / (VGPRs rounded up to 8), at
+most 8) and marked WORSE if it spills more, gained scratch or lost a wave per SIMD.  The waves are what the registers alone
+allow: LDS and the workgroup size may allow fewer in both builds, so WORSE errs on the strict side.  A translation unit that
+only one of the two directories holds is reported and counted like a kernel (MISSING / NEW).
 """
 import os
 import re
@@ -19,11 +22,11 @@ import tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from simurlacra_amd.csrc import codeobj  # noqa: E402
 
-DEFAULT = r"^k_rollout_(fnn|rnn|ws)<"
+DEFAULT = r"^k_"
 
 
 def kernels(obj_path):
-    """{demangled name without parameters: [instructions]} of one translation unit"""
+    """{demangled name without parameters: (mangled name, [instructions])} of one translation unit"""
     with tempfile.TemporaryDirectory() as tmp:
         co = codeobj.device_code_object(obj_path, os.path.join(tmp, "dev.co"))
         text = subprocess.run([codeobj._tool("llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True,
@@ -44,49 +47,52 @@ def kernels(obj_path):
     for n, d in zip(names, dm):
         d = d.replace("void ", "").replace("vs::", "")
         d = re.sub(r"\(.*$", "", d)
-        res[d] = out[n]
+        res[d] = (n, out[n])
     return res
 
 
-def normalise(name):
-    """the new build's name of a pre-existing instantiation -> the old build's name (POP = false dropped)"""
-    m = re.match(r"^(k_rollout_(fnn|rnn))<(.*)>$", name)
-    if not m:
-        return name
-    args = [a.strip() for a in re.split(r",(?![^<]*>)", m.group(3))]
-    want = 7 if m.group(2) == "fnn" else 5
-    if len(args) == want and args[-1] == "false":
-        args = args[:-1]
-    elif len(args) == want:
-        return None  # a POP = true instantiation: new
-    return f"{m.group(1)}<{', '.join(args)}>"
+def registers(row):
+    return dict(row, waves=min(8, 512 // max(8, (row["vgpr_count"] + 7) // 8 * 8)))
+
+
+def show(r):
+    return (f"{r['vgpr_count']} v ({r['agpr_count']} a), {r['sgpr_count']} s, spills {r['vgpr_spill_count']}/{r['sgpr_spill_count']}, "
+            f"scratch {r['private_segment_fixed_size']}, lds {r['group_segment_fixed_size']}, {r['waves']} waves")
 
 
 def main():
     old_dir, new_dir = sys.argv[1], sys.argv[2]
     pat = re.compile(sys.argv[3] if len(sys.argv) > 3 else DEFAULT)
-    units = sorted(f for f in os.listdir(old_dir) if f.endswith(".o"))
-    checked = differ = missing = 0
-    for u in units:
+    objs = [{f for f in os.listdir(d) if f.endswith(".o")} for d in (old_dir, new_dir)]
+    checked = differ = missing = added = worse = 0
+    for u in sorted(objs[0] ^ objs[1]):
+        print(f"{'MISSING' if u in objs[0] else 'NEW'} unit {u}")
+        missing += u in objs[0]
+        added += u in objs[1]
+    for u in sorted(objs[0] & objs[1]):
         old = {k: v for k, v in kernels(os.path.join(old_dir, u)).items() if pat.search(k)}
-        new = {}
-        for k, v in kernels(os.path.join(new_dir, u)).items():
-            if pat.search(k):
-                nk = normalise(k)
-                if nk is not None:
-                    new[nk] = v
-        for k, ins in sorted(old.items()):
+        new = {k: v for k, v in kernels(os.path.join(new_dir, u)).items() if pat.search(k)}
+        regs = None
+        for k, (sym, ins) in sorted(old.items()):
             checked += 1
             if k not in new:
                 missing += 1
                 print(f"MISSING {u}: {k}")
-            elif new[k] != ins:
+            elif new[k][1] != ins:
                 differ += 1
-                first = next((i for i, (a, b) in enumerate(zip(ins, new[k])) if a != b), min(len(ins), len(new[k])))
-                print(f"DIFFERS {u}: {k} ({len(ins)} -> {len(new[k])} instructions, first difference at {first})")
+                if regs is None:
+                    regs = [{r["name"]: registers(r) for r in codeobj.kernels_of(os.path.join(d, u))} for d in (old_dir, new_dir)]
+                ro, rn = regs[0][sym], regs[1][new[k][0]]
+                bad = (rn["vgpr_spill_count"] > ro["vgpr_spill_count"] or rn["sgpr_spill_count"] > ro["sgpr_spill_count"]
+                       or (rn["private_segment_fixed_size"] and not ro["private_segment_fixed_size"]) or rn["waves"] < ro["waves"])
+                worse += bad
+                print(f"{'WORSE  ' if bad else 'DIFFERS'} {u}: {k}  {len(ins)} -> {len(new[k][1])} instructions | {show(ro)} -> {show(rn)}")
+        for k in sorted(set(new) - set(old)):
+            added += 1
+            print(f"NEW {u}: {k}")
         print(f"{u}: {len(old)} kernels compared", flush=True)
-    print(f"{checked} kernels, {differ} differ, {missing} missing")
-    sys.exit(1 if differ or missing else 0)
+    print(f"{checked} kernels, {differ} differ ({worse} worse), {missing} missing, {added} new")
+    sys.exit(1 if differ or missing or added else 0)
 
 
 if __name__ == "__main__":

@@ -1166,11 +1166,7 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
             return fail(h, VS_ERR_STATE, "vs_step_policy: the hidden-state record width differs from the policy's hidden size");
         HIPCHK(h, hipSetDevice(h->device));
         h->rnn.hrec = h->d_hrec;
-        if (h->pop.w) {
-            DISPATCH_ENV(h->type, Launch<E>::rollout_rnn_pop(h, k_steps, h->record_mode, noise_seed));
-        } else {
-            DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
-        }
+        DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
         HIPCHK(h, hipGetLastError());
         return VS_OK;
     }
@@ -1178,19 +1174,14 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
     if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
     if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->pop.w) {
+    int shape = fnn_shape(h);
+    if (h->pop.w && shape != 0 && !h->pop_g256) {
         // the 256-env shapes take one set per workgroup of 256 lanes: a table that is uniform in groups of 64 only runs shape 0
         // when the choice is automatic, and is refused when shape 1 or 2 is pinned
-        int shape = fnn_shape(h);
-        if (shape != 0 && !h->pop_g256) {
-            if (h->policy_shape > 0) return fail(h, VS_ERR_STATE, "vs_step_policy: the pinned 256-env shape needs a population table uniform in groups of 256 lanes");
-            shape = 0;
-        }
-        DISPATCH_ENV(h->type, Launch<E>::rollout_fnn_pop(h, k_steps, h->record_mode, noise_seed, shape));
-        HIPCHK(h, hipGetLastError());
-        return VS_OK;
+        if (h->policy_shape > 0) return fail(h, VS_ERR_STATE, "vs_step_policy: the pinned 256-env shape needs a population table uniform in groups of 256 lanes");
+        shape = 0;
     }
-    DISPATCH_ENV(h->type, Launch<E>::rollout_fnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
+    DISPATCH_ENV(h->type, Launch<E>::rollout_fnn(h, k_steps, record ? h->record_mode : 0, noise_seed, shape));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

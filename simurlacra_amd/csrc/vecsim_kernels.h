@@ -2660,10 +2660,9 @@ template <class E>
 struct Launch {
     static void step(vs_env* h, const float* act, long es, long ds, int rec = 0, int row = 0);
     static void rollout(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec);
-    static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy
-    static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // vs_step_policy, recurrent policy
-    static void rollout_fnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed, int shape);  // ... with a population (POP):
-    static void rollout_rnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed);             //     auto-reset off, rec 1 | 2
+    // vs_step_policy (shape: fnn_shape(h) as admitted there); with a population on the handle (POP): auto-reset off, rec 1 | 2
+    static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed, int shape);
+    static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... recurrent policy
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -2678,6 +2677,33 @@ void launch_rollout_mixed(const Segs* dev_segs, int total_blocks, hipStream_t st
 void launch_step_mixed(const Segs* dev_segs, int total_blocks, hipStream_t st, bool ar, bool drk);
 
 #ifdef VS_TU_FAMILY
+// Run-time handle fields as template arguments: f is a generic lambda and receives every bool / the int as a
+// std::integral_constant.  `if constexpr` in the lambda keeps a combination that has no kernel from being instantiated; its
+// `else` is no_kernel(): the run-time arguments of a launcher never form such a combination, and if a change makes them, the
+// call must not return as if it had launched.  The lambdas are always_inline: as functions of their own every instantiation
+// would be an exported weak symbol of the library (they sit in member functions of Launch<E>), names and unwind tables included.
+template <class... Cs>
+struct Consts {};
+template <class F, class... Cs>
+__attribute__((always_inline)) static inline void with_bools(F&& f, Consts<Cs...>) { f(Cs{}...); }
+template <class F, class... Cs, class... Bs>
+__attribute__((always_inline)) static inline void with_bools(F&& f, Consts<Cs...>, bool v, Bs... rest) {
+    if (v) with_bools(f, Consts<Cs..., std::true_type>{}, rest...);
+    else with_bools(f, Consts<Cs..., std::false_type>{}, rest...);
+}
+template <class F, class... Bs>
+__attribute__((always_inline)) static inline void with_bools(F&& f, bool v, Bs... rest) { with_bools(f, Consts<>{}, v, rest...); }
+template <int V0, int... Vs, class F>
+__attribute__((always_inline)) static inline void with_int(int v, F&& f) {  // one of V0, Vs...; the last stands for every other value
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_int<Vs...>(v, f);
+}
+[[noreturn]] static inline void no_kernel(const char* launcher) {
+    fprintf(stderr, "libvecsim: %s: no kernel for this combination of handle settings (a bug in the launcher)\n", launcher);
+    abort();
+}
+
 // Which fused kernel for a batch (measured on MI355X, profiles/r02_table_variants.txt; 256 compute units):
 //   * the wave-specialised kernel pays while k_rollout would leave a SIMD with a single wave, for the families whose step
 //     splits into two comparable halves, and needs constants its reward wave reads not to change inside the launch;
@@ -2729,26 +2755,20 @@ constexpr int64_t STEP_NT_MIN_ENVS = 4 << 20;
 template <class E, int REC>
 static void launch_step_rec(vs_env* h, const float* act, long es, long ds, int row) {
     dim3 g = grid_for(h->d.ld), b(BLOCK);
-    bool uni = h->uniform && h->dr.n == 0 && h->d.pbuf_n == 0;
+    const bool pipe = h->d.pipe.act_on || h->d.pipe.obs_on;  // the wrapper pipeline: per-env-constant variant only
+    const bool uni = h->uniform && h->dr.n == 0 && h->d.pbuf_n == 0 && !pipe;
     const bool drk = h->d.dr_n > 0 || h->d.pbuf_n > 0;  // a reset inside the launch redraws domain parameters
+    bool nt = false;
     if constexpr (REC == 0) {
         // large batches: the non-temporal instantiation (see ld_nt); VS_STEP_NT=0|1 overrides (experiments)
         static const char* nt_env = getenv("VS_STEP_NT");
-        const bool nt = nt_env ? nt_env[0] == '1' : (int64_t)h->d.ld >= STEP_NT_MIN_ENVS;
-        if (nt && !(h->d.pipe.act_on || h->d.pipe.obs_on) && !drk) {
-#define LN(U, AR) hipLaunchKernelGGL((k_step<E, U, AR, false, 0, false, true>), g, b, 0, h->stream, h->task, h->d, act, es, ds, h->ar_seed, row)
-            if (h->auto_reset) { if (uni) LN(true, true); else LN(false, true); }
-            else { if (uni) LN(true, false); else LN(false, false); }
-#undef LN
-            return;
-        }
+        nt = (nt_env ? nt_env[0] == '1' : (int64_t)h->d.ld >= STEP_NT_MIN_ENVS) && !pipe && !drk;
     }
-#define LS(U, AR, PI, DK) hipLaunchKernelGGL((k_step<E, U, AR, PI, REC, DK>), g, b, 0, h->stream, h->task, h->d, act, es, ds, h->ar_seed, row)
-    if (h->d.pipe.act_on || h->d.pipe.obs_on) {  // the wrapper pipeline: per-env-constant variant only
-        if (h->auto_reset) { if (drk) LS(false, true, true, true); else LS(false, true, true, false); } else LS(false, false, true, false);
-    } else if (h->auto_reset) { if (uni) LS(true, true, false, false); else if (drk) LS(false, true, false, true); else LS(false, true, false, false); }
-    else { if (uni) LS(true, false, false, false); else LS(false, false, false, false); }
-#undef LS
+    with_bools([&](auto U, auto AR, auto PI, auto DK, auto NT) __attribute__((always_inline)) {
+        if constexpr (!(U && PI) && (!DK || (!U && AR)) && (!NT || (REC == 0 && !PI && !DK)))
+            hipLaunchKernelGGL((k_step<E, U, AR, PI, REC, DK, NT>), g, b, 0, h->stream, h->task, h->d, act, es, ds, h->ar_seed, row);
+        else no_kernel("step");
+    }, uni, h->auto_reset, pipe, !uni && h->auto_reset && drk, nt);
 }
 
 template <class E>
@@ -2767,24 +2787,19 @@ static void launch_ws(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec) {
         // the instantiation with the redraw compiled in only for a handle that has a randomizer or a parameter buffer
         const int drk = (!U && AR) ? (h->d.pbuf_n > 0 ? 2 : (h->d.dr_n > 0 ? 1 : 0)) : 0;
         // R = 4 steps per exchange (measured on the headline config: R = 1 / 2 / 4 -> 68.7 / 64.8 / 62.0 us per 100 steps)
-#define LWK(REC, DRKV)                                                                                                     \
-    {                                                                                                                      \
-        auto kern = k_rollout_ws<E, U, AR, REC, 4, NE, (NR == 2 && E::WS_DRAW_P && REC != 0), NR, DRKV>;                    \
-        static unsigned char attr_set[64] = {}; /* once per kernel and device */                                           \
-        if (dyn && !attr_set[h->device & 63]) {                                                                            \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);            \
-            attr_set[h->device & 63] = 1;                                                                                  \
-        }                                                                                                                  \
-        hipLaunchKernelGGL(kern, g, b, dyn, h->stream, h->task, h->d, k, seed, h->ar_seed, ep);                            \
-    }
-#define LW(REC)                                                                                                            \
-    {                                                                                                                      \
-        if constexpr (!U && AR) { if (drk == 2) LWK(REC, 2) else if (drk == 1) LWK(REC, 1) else LWK(REC, 0) }               \
-        else LWK(REC, 0)                                                                                                   \
-    }
-        if (rec == 0) LW(0) else if (rec == 1) LW(1) else LW(2)
-#undef LW
-#undef LWK
+        with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+            with_int<2, 1, 0>(drk, [&](auto DRKV) __attribute__((always_inline)) {
+                if constexpr (DRKV == 0 || (!U && AR)) {
+                    auto kern = k_rollout_ws<E, U, AR, REC, 4, NE, (NR == 2 && E::WS_DRAW_P && REC != 0), NR, DRKV>;
+                    static unsigned char attr_set[64] = {};  // once per kernel and device
+                    if (dyn && !attr_set[h->device & 63]) {
+                        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+                        attr_set[h->device & 63] = 1;
+                    }
+                    hipLaunchKernelGGL(kern, g, b, dyn, h->stream, h->task, h->d, k, seed, h->ar_seed, ep);
+                } else no_kernel("rollout (wave-specialised)");
+            });
+        });
     }
 }
 
@@ -2792,37 +2807,32 @@ template <class E, bool U, bool AR, bool PI>
 static void launch_plain(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec) {
     dim3 g = grid_for(h->d.ld), b(BLOCK);
     const bool drk = h->d.dr_n > 0 || h->d.pbuf_n > 0;  // a reset inside the launch redraws domain parameters
-#define LRK(REC, DK) hipLaunchKernelGGL((k_rollout<E, U, AR, REC, PI, DK>), g, b, 0, h->stream, h->task, h->d, k, seed, h->ar_seed, ep)
-#define LR(REC) { if constexpr (!U && AR) { if (drk) LRK(REC, true); else LRK(REC, false); } else LRK(REC, false); }
-    if (rec == 0) LR(0) else if (rec == 1) LR(1) else LR(2)
-#undef LR
-#undef LRK
+    with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+        with_bools([&](auto DK) __attribute__((always_inline)) {
+            if constexpr (!DK || (!U && AR))
+                hipLaunchKernelGGL((k_rollout<E, U, AR, REC, PI, DK>), g, b, 0, h->stream, h->task, h->d, k, seed, h->ar_seed, ep);
+            else no_kernel("rollout");
+        }, !U && AR && drk);
+    });
 }
 
 template <class E>
 void Launch<E>::rollout(vs_env* h, int k, uint64_t seed, uint64_t ep, int rec) {
-    const bool uni = h->uniform && h->dr.n == 0;
-    const bool ar = h->auto_reset;
-    const int var = variant(h);
-    if (var != RV_PLAIN) {
-#define WS(NE, NR)                                                                                     \
-    if (uni) { if (ar) launch_ws<E, true, true, NE, NR>(h, k, seed, ep, rec); else launch_ws<E, true, false, NE, NR>(h, k, seed, ep, rec); } \
-    else { if (ar) launch_ws<E, false, true, NE, NR>(h, k, seed, ep, rec); else launch_ws<E, false, false, NE, NR>(h, k, seed, ep, rec); }
-        if constexpr (E::WS_G3) {
-            if (var == RV_WS64G) { WS(64, 3) return; }
-            if (var == RV_WS256G) { WS(256, 3) return; }
-        }
-        if (var == RV_WS64 || var == RV_WS64G) { WS(64, 2) } else { WS(256, 2) }
-#undef WS
-        return;
-    }
-    if (h->d.pipe.act_on || h->d.pipe.obs_on) {
-        if (ar) launch_plain<E, false, true, true>(h, k, seed, ep, rec); else launch_plain<E, false, false, true>(h, k, seed, ep, rec);
-    } else if (uni) {
-        if (ar) launch_plain<E, true, true, false>(h, k, seed, ep, rec); else launch_plain<E, true, false, false>(h, k, seed, ep, rec);
-    } else {
-        if (ar) launch_plain<E, false, true, false>(h, k, seed, ep, rec); else launch_plain<E, false, false, false>(h, k, seed, ep, rec);
-    }
+    const int var = variant(h);  // (RV_PLAIN whenever the wrapper pipeline is on)
+    const bool pipe = h->d.pipe.act_on || h->d.pipe.obs_on;
+    with_bools([&](auto U, auto AR, auto PI) __attribute__((always_inline)) {
+        if constexpr (!(U && PI)) {
+            if (var == RV_PLAIN) return launch_plain<E, U, AR, PI>(h, k, seed, ep, rec);
+            if constexpr (!PI) {
+                if constexpr (E::WS_G3) {
+                    if (var == RV_WS64G) return launch_ws<E, U, AR, 64, 3>(h, k, seed, ep, rec);
+                    if (var == RV_WS256G) return launch_ws<E, U, AR, 256, 3>(h, k, seed, ep, rec);
+                }
+                if (var == RV_WS64 || var == RV_WS64G) launch_ws<E, U, AR, 64, 2>(h, k, seed, ep, rec);
+                else launch_ws<E, U, AR, 256, 2>(h, k, seed, ep, rec);
+            } else no_kernel("rollout (pipeline)");
+        } else no_kernel("rollout");
+    }, h->uniform && h->dr.n == 0 && !pipe, h->auto_reset, pipe);
 }
 
 #endif  // VS_TU_FAMILY
@@ -2845,37 +2855,22 @@ static inline int fnn_shape(const vs_env* h) {
 }
 #ifdef VS_TU_FAMILY
 
+// with a population on the handle the same kernels with POP (every workgroup its set of h->pop): auto-reset off and records on only
 template <class E>
-void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
-#define LF(AR, REC, NH, NE, MF) hipLaunchKernelGGL((k_rollout_fnn<E, AR, REC, NH, NE, MF>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)), 0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed, Pop{})
-#define LFR(AR, NH, NE, MF) { if (rec == 0) LF(AR, 0, NH, NE, MF); else if (rec == 1) LF(AR, 1, NH, NE, MF); else LF(AR, 2, NH, NE, MF); }
-#define LFA(NH, NE, MF) { if (h->auto_reset) LFR(true, NH, NE, MF) else LFR(false, NH, NE, MF) }
-    const int shape = fnn_shape(h);
-    switch (h->fnn.n_hidden) {
-        case 1: if (shape == 2) LFA(1, 256, true) else if (shape == 1) LFA(1, 256, false) else LFA(1, 64, false) break;
-        case 2: if (shape == 2) LFA(2, 256, true) else if (shape == 1) LFA(2, 256, false) else LFA(2, 64, false) break;
-        case 3: LFA(3, 64, false) break;
-        default: LFA(4, 64, false) break;
-    }
-#undef LFA
-#undef LFR
-#undef LF
-}
-
-// the population: the same kernels with POP (every workgroup its set of h->pop), auto-reset off and records on only; `shape` is
-// fnn_shape(h) as vs_step_policy admitted it for the set table
-template <class E>
-void Launch<E>::rollout_fnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed, int shape) {
-#define LF(REC, NH, NE, MF) hipLaunchKernelGGL((k_rollout_fnn<E, false, REC, NH, NE, MF, true>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)), 0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed, h->pop)
-#define LFA(NH, NE, MF) { if (rec == 1) LF(1, NH, NE, MF); else LF(2, NH, NE, MF); }
-    switch (h->fnn.n_hidden) {
-        case 1: if (shape == 2) LFA(1, 256, true) else if (shape == 1) LFA(1, 256, false) else LFA(1, 64, false) break;
-        case 2: if (shape == 2) LFA(2, 256, true) else if (shape == 1) LFA(2, 256, false) else LFA(2, 64, false) break;
-        case 3: LFA(3, 64, false) break;
-        default: LFA(4, 64, false) break;
-    }
-#undef LFA
-#undef LF
+void Launch<E>::rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed, int shape) {
+    with_int<1, 2, 3, 4>(h->fnn.n_hidden, [&](auto NH) __attribute__((always_inline)) {
+        with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+            with_bools([&](auto AR, auto G256, auto MF, auto POP) __attribute__((always_inline)) {
+                constexpr int NE = G256 ? 256 : 64;
+                // shapes: one or two hidden layers in 64- or 256-env workgroups, the latter also on the matrix cores (MF); three
+                // and four in 64-env workgroups only.  A population: auto-reset off, records on (vs_step_policy refuses the rest)
+                if constexpr ((NH <= 2 ? !MF || G256 : !G256 && !MF) && (!POP || (!AR && REC != 0)))
+                    hipLaunchKernelGGL((k_rollout_fnn<E, AR, REC, NH, NE, MF, POP>), dim3((unsigned)(h->d.ld / NE)), dim3(64 * fnn_waves(NH)),
+                                       0, h->stream, h->task, h->d, h->fnn, k, h->ar_seed, noise_seed, POP ? h->pop : Pop{});
+                else no_kernel("rollout_fnn");
+            }, h->auto_reset, NH <= 2 && shape != 0, NH <= 2 && shape == 2, h->pop.w != nullptr);
+        });
+    });
 }
 
 template <class E>
@@ -2884,39 +2879,18 @@ void Launch<E>::rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
     const size_t lds = (size_t)h->rnn.lds_rows * 64 * sizeof(float);
     Rnn P = h->rnn;
     if (!rec || h->hrec_width != P.hs) P.hrec = nullptr;
-#define LR(AR, REC, G)                                                                                                    \
-    {                                                                                                                     \
-        (void)hipFuncSetAttribute((const void*)&k_rollout_rnn<E, AR, REC, G>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                  (int)lds);                                                                              \
-        hipLaunchKernelGGL((k_rollout_rnn<E, AR, REC, G>), dim3((unsigned)(h->d.ld / 64)), dim3(64), lds, h->stream,        \
-                           h->task, h->d, P, k, h->ar_seed, noise_seed, Pop{});                                           \
-    }
-#define LRR(AR, G) { if (rec == 0) LR(AR, 0, G) else if (rec == 1) LR(AR, 1, G) else LR(AR, 2, G) }
-#define LRA(G) { if (h->auto_reset) LRR(true, G) else LRR(false, G) }
-    const int g = rnn_gates(P.cell);
-    if (g == 1) LRA(1) else if (g == 3) LRA(3) else LRA(4)
-#undef LRA
-#undef LRR
-#undef LR
-}
-
-template <class E>
-void Launch<E>::rollout_rnn_pop(vs_env* h, int k, int rec, uint64_t noise_seed) {
-    const size_t lds = (size_t)h->rnn.lds_rows * 64 * sizeof(float);
-    Rnn P = h->rnn;
-    if (h->hrec_width != P.hs) P.hrec = nullptr;
-#define LR(REC, G)                                                                                                        \
-    {                                                                                                                     \
-        (void)hipFuncSetAttribute((const void*)&k_rollout_rnn<E, false, REC, G, true>,                                    \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-        hipLaunchKernelGGL((k_rollout_rnn<E, false, REC, G, true>), dim3((unsigned)(h->d.ld / 64)), dim3(64), lds,          \
-                           h->stream, h->task, h->d, P, k, h->ar_seed, noise_seed, h->pop);                               \
-    }
-#define LRR(G) { if (rec == 1) LR(1, G) else LR(2, G) }
-    const int g = rnn_gates(P.cell);
-    if (g == 1) LRR(1) else if (g == 3) LRR(3) else LRR(4)
-#undef LRR
-#undef LR
+    with_int<1, 3, 4>(rnn_gates(P.cell), [&](auto G) __attribute__((always_inline)) {
+        with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+            with_bools([&](auto AR, auto POP) __attribute__((always_inline)) {
+                if constexpr (!POP || (!AR && REC != 0)) {
+                    auto kern = k_rollout_rnn<E, AR, REC, G, POP>;
+                    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    hipLaunchKernelGGL(kern, dim3((unsigned)(h->d.ld / 64)), dim3(64), lds, h->stream, h->task, h->d, P, k, h->ar_seed,
+                                       noise_seed, POP ? h->pop : Pop{});
+                } else no_kernel("rollout_rnn");
+            }, h->auto_reset, h->pop.w != nullptr);
+        });
+    });
 }
 
 template <class E>
