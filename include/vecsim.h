@@ -355,6 +355,36 @@ int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params,
  * (`while not done and env.curr_step < env.max_steps`, P/sampling/rollout.py:185) and StepSequence.done[-1].  Device memory. */
 int vs_rollout_lengths(vs_handle h, int n_lanes, int t_steps, int64_t* lengths, uint8_t* done_last);
 int vs_pack_traj(vs_handle h, int n_lanes, int t_steps, const int64_t* lengths, const int64_t* starts, float* rows);
+/* Discounted reward-to-go and GAE advantages of packed rollouts: inside every rollout the recurrence y_t = x_t + c y_{t+1}, backwards
+ * in time, as one segmented scan over the packed rows (three launches, no host synchronisation).  No handle: the packed rows belong
+ * to the caller.  device_id / hip_stream: where to launch, a hipStream_t in vs_set_stream's convention (hipStreamLegacy = (hipStream_t)1
+ * or NULL: the legacy default stream).  Everything else is device memory:
+ *   n, lengths[n], starts[n]    as for vs_pack_traj (int64): rollout j has L = lengths[j] steps and base row b = starts[j] + j; the rows
+ *                               b .. b + L - 1 are its steps, row b + L its final entry.  (A sub-range j0 .. of a batch: pass
+ *                               lengths + j0, starts + j0 and the row pointers advanced by j0 rows.)
+ *   rew, rew_stride             reward of step t of rollout j = rew[(b + t) * rew_stride] (the reward column of rows[total + n][F] where
+ *                               it lies: rew_stride = F)
+ *   values, values_stride       NULL, or a value estimate per packed row: row b + t = the value of the observation before step t, row
+ *                               b + L that of the final observation (the rows of the packed observations)
+ *   done_last[n]                NULL, or u8: the final value of the rollout does not bootstrap (it ended by failure; note that an
+ *                               env's done flag is also set at the step limit -- VS_FAILED tells the two apart)
+ *   out[total + n]              dense, on the same rows;  out_first[n] or NULL
+ * With keep_j = done_last && done_last[j] ? 0 : 1, for t = L - 1 .. 0:
+ *   VS_RETURNS_RETURN  y_L = values ? values[b + L] * keep_j : 0;   y_t = rew[b + t] + gamma * y_{t+1}
+ *   VS_RETURNS_GAE     (values required)  V_L = values[b + L] * keep_j, V_t = values[b + t];  delta_t = rew[b + t] + gamma * V_{t+1} - V_t;
+ *                      y_L = 0;   y_t = delta_t + gamma * lam * y_{t+1}      (Schulman et al. 2016, eq. 16)
+ *   out[b + t] = y_t, out[b + L] = y_L, out_first[j] = y_0 (= y_L for L = 0: the inert lanes of a population).
+ * A zero multiplier cuts: nothing behind a final-entry row reaches the rollout before it, a non-finite value stays in its rollout.
+ * fp32 throughout; the summation order is fixed (two calls give the same bits) but is a tree, not the sequential order.
+ * VS_ERR_ARG (before any device call; vs_last_error(NULL) names the reason): n <= 0, NULL lengths / starts / rew / out, VS_RETURNS_GAE
+ * without values, an unknown mode, a stride < 1, gamma or lam outside [0, 1].  lengths must be >= 0 and starts their exclusive running sum.
+ * Replaces: StepSequence.discounted_return, discounted_reverse_cumsum and gae_returns of P/sampling/step_sequence.py, over a
+ * concatenation of rollouts. */
+#define VS_RETURNS_RETURN 0
+#define VS_RETURNS_GAE 1
+int vs_returns_scan(int device_id, void* hip_stream, int64_t n, const int64_t* lengths, const int64_t* starts, const float* rew,
+                    int64_t rew_stride, const float* values, int64_t values_stride, const uint8_t* done_last, float gamma, float lam,
+                    int mode, float* out, float* out_first);
 /* The action stream of vs_step_random is Philox(seed; global env index, absolute step index); the handle counts the
  * steps it has taken.  vs_seek_random repositions that counter (0 = start of a fresh batch of rollouts). */
 int vs_seek_random(vs_handle h, uint64_t step_index);

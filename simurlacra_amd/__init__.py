@@ -32,7 +32,7 @@ def __getattr__(name):
         from . import sampling
 
         return getattr(sampling, name)
-    if name in ("ParameterExploringSampler", "ParameterSample", "ParameterSamplingResult"):
+    if name in ("ParameterExploringSampler", "ParameterSample", "ParameterSamplingResult", "PopulationReturns"):
         from . import parameter_exploration
 
         return getattr(parameter_exploration, name)

@@ -19,6 +19,7 @@ VS_RNN_TANH, VS_RNN_RELU, VS_RNN_GRU, VS_RNN_LSTM = 0, 1, 2, 3  # vs_rnn_desc ce
 VS_RNN_MAX_LAYERS, VS_RNN_MAX_HIDDEN = 2, 64
 VS_DP_NORMAL, VS_DP_UNIFORM, VS_DP_BERNOULLI = 0, 1, 2
 VS_MAX_ACT_DELAY = 64
+VS_RETURNS_RETURN, VS_RETURNS_GAE = 0, 1  # vs_returns_scan modes
 
 
 class TaskCfg(C.Structure):
@@ -87,6 +88,8 @@ _SIGNATURES = {
     "vs_set_policy_population": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "vs_rollout_lengths": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "vs_pack_traj": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "vs_returns_scan": (C.c_int, [C.c_int, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, C.c_float, C.c_int, _P,
+                                  _P]),
     "vs_rollout_variant": (C.c_int, [_P]),
     "vs_set_rollout_variant": (C.c_int, [_P, C.c_int]),
     "vs_set_traj_capacity": (C.c_int, [_P, C.c_int]),

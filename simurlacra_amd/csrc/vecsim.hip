@@ -57,6 +57,163 @@ __global__ __launch_bounds__(256) void k_pack_population(const float* __restrict
         dst[s * stride + q] = m < 0 ? 0.f : src[s * n_params + m];
 }
 
+// ---- vs_returns_scan: y_t = x_t + c y_{t+1} backwards inside every rollout of the packed rows (discounted reward-to-go, GAE).
+// A flat segmented scan over ROWS in three launches; a row is the affine map y -> a + m y (step rows: m = c, the final-entry
+// row of a rollout: a = y_L, m = 0 -- it cuts the carry), and maps compose as (a1, m1) o (a2, m2) = (a1 + m1 a2, m1 m2).
+//   k_returns_scan   a workgroup takes tiles of RT_TILE consecutive rows, whatever rollouts they cut: a wave owns 256 of them as
+//                    four 64-row chunks (lane = row: coalesced), scans each chunk backwards with cross-lane moves, chains its
+//                    chunks in registers and the four waves through LDS; writes y as if nothing followed the tile
+//   k_returns_carry  one thread per rollout: the rows of it that start a tile (at most lengths / RT_TILE) get their true value,
+//                    last tile first, then the rollout's first row and out_first
+//   k_returns_apply  per tile, the rows of the rollout that runs on into the next tile add c^(distance) times that tile's first row
+// Tiles sit at multiples of RT_TILE of the row index in all three, so no launch waits on another workgroup of its own grid.
+constexpr int RT_TILE = 1024;
+
+// the rollout of row r: the largest j in [lo, hi] with starts[j] + j <= r (which holds for lo)
+__device__ inline int rt_find(const long long* __restrict__ starts, int lo, int hi, long long r) {
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (starts[mid] + mid <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// c^k by squaring, k < 2^BITS: at most k - 1 roundings, as many as the k multiplications of the sequential recurrence
+template <int BITS>
+__device__ inline float rt_pow(float c, int k) {
+    float r = 1.f, b = c;
+#pragma unroll
+    for (int s = 0; s < BITS; ++s) {
+        r = ((k >> s) & 1) ? r * b : r;
+        b = b * b;
+    }
+    return r;
+}
+
+// a + m y, where m == 0 CUTS: what lies behind a rollout's final-entry row never reaches it, not even as 0 * NaN or 0 * Inf -- a
+// non-finite reward or value stays inside its own rollout, as in the sequential recurrence (m == 0 also for gamma = 0 and when
+// c^k underflows: there the rows behind contribute nothing either)
+__device__ inline float rt_apply(float a, float m, float y) { return m == 0.f ? a : a + m * y; }
+
+__device__ inline long long rt_end(int n, const long long* __restrict__ lengths, const long long* __restrict__ starts) {
+    return starts[n - 1] + (n - 1) + lengths[n - 1] + 1;
+}
+
+__global__ __launch_bounds__(256) void k_returns_scan(int n, const long long* __restrict__ lengths, const long long* __restrict__ starts,
+                                                      const float* __restrict__ rew, long long rs, const float* __restrict__ values,
+                                                      long long vst, const uint8_t* __restrict__ done_last, float gamma, float c, int gae,
+                                                      float* __restrict__ out) {
+    __shared__ float s_a[4], s_m[4];
+    const long long r_first = starts[0], r_end = rt_end(n, lengths, starts);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (long long tile = r_first / RT_TILE + blockIdx.x; tile * RT_TILE < r_end; tile += gridDim.x) {
+        const long long S = tile * RT_TILE;
+        const long long first = S > r_first ? S : r_first, last = (S + RT_TILE < r_end ? S + RT_TILE : r_end) - 1;
+        // the rollouts of the tile: every one owns at least a row, so there are at most last - first + 1 of them
+        const int j_lo = rt_find(starts, 0, n - 1, first);
+        const long long cap = (long long)j_lo + (last - first);
+        const int j_hi = rt_find(starts, j_lo, cap < n - 1 ? (int)cap : n - 1, last);
+        float a[4], m[4];
+        int jl = j_lo;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long r = S + w * 256 + i * 64 + lane;
+            a[i] = 0.f;  // rows outside the batch: the identity map
+            m[i] = 1.f;
+            if (r >= first && r <= last) {
+                const long long span = i ? 64 : r - first;  // rows since the row jl was found for
+                const int j = rt_find(starts, jl, (long long)jl + span < j_hi ? (int)(jl + span) : j_hi, r);
+                jl = j;
+                const long long fin = starts[j] + j + lengths[j];
+                const float keep = (done_last && done_last[j]) ? 0.f : 1.f;  // the bootstrap value survives a time-out only
+                if (r == fin) {
+                    a[i] = (values && !gae) ? values[r * vst] * keep : 0.f;
+                    m[i] = 0.f;
+                } else {
+                    float x = rew[r * rs];
+                    if (gae) {
+                        float vn = values[(r + 1) * vst];
+                        if (r + 1 == fin) vn = vn * keep;
+                        x = x + gamma * vn - values[r * vst];
+                    }
+                    a[i] = x;
+                    m[i] = c;
+                }
+            }
+        }
+        float ac = 0.f, mc = 1.f;  // the map of the wave's rows behind chunk i
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+            float ai = a[i], mi = m[i];
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const float a2 = __shfl_down(ai, s), m2 = __shfl_down(mi, s);
+                if (lane + s < 64) {
+                    ai = rt_apply(ai, mi, a2);
+                    mi = mi * m2;
+                }
+            }
+            ai = rt_apply(ai, mi, ac);
+            mi = mi * mc;
+            a[i] = ai;
+            m[i] = mi;
+            ac = __shfl(ai, 0);
+            mc = __shfl(mi, 0);
+        }
+        if (lane == 0) {
+            s_a[w] = ac;
+            s_m[w] = mc;
+        }
+        __syncthreads();
+        float carry = 0.f;  // y of the first row of the next wave, as if nothing followed the tile
+        for (int k = 3; k > w; --k) carry = rt_apply(s_a[k], s_m[k], carry);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long r = S + w * 256 + i * 64 + lane;
+            if (r >= first && r <= last) out[r] = rt_apply(a[i], m[i], carry);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_returns_carry(int n, const long long* __restrict__ lengths, const long long* __restrict__ starts,
+                                                       float c, float* __restrict__ out, float* __restrict__ out_first) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const long long base = starts[j] + j, fin = base + lengths[j];
+    const long long e_first = (base / RT_TILE + 1) * RT_TILE;  // the first tile edge behind the rollout's first row
+    float y0 = out[base];
+    if (e_first <= fin) {
+        const long long e_last = fin / RT_TILE * RT_TILE;  // the rollout ends in the tile that starts here: out[e_last] is final
+        float carry = out[e_last];
+        if (e_last > e_first) {
+            const float ct = rt_pow<11>(c, RT_TILE);
+            for (long long e = e_last - RT_TILE; e >= e_first; e -= RT_TILE) {
+                carry = out[e] + ct * carry;
+                out[e] = carry;
+            }
+        }
+        y0 = y0 + rt_pow<11>(c, (int)(e_first - base)) * carry;
+        out[base] = y0;
+    }
+    if (out_first) out_first[j] = y0;
+}
+
+__global__ __launch_bounds__(256) void k_returns_apply(int n, const long long* __restrict__ lengths, const long long* __restrict__ starts,
+                                                       float c, float* __restrict__ out) {
+    const long long r_first = starts[0], r_end = rt_end(n, lengths, starts);
+    for (long long tile = r_first / RT_TILE + blockIdx.x; (tile + 1) * RT_TILE < r_end; tile += gridDim.x) {
+        const long long S = tile * RT_TILE, E = S + RT_TILE;
+        const int j = rt_find(starts, 0, n - 1, E - 1);  // the rollout of the tile's last row ...
+        const long long base = starts[j] + j;
+        if (base + lengths[j] < E) continue;  // ... ends with it: nothing to carry in
+        const float carry = out[E];           // (k_returns_carry's; no workgroup of this launch writes a row that starts a tile)
+        for (long long r = (S > base ? S : base) + 1 + threadIdx.x; r < E; r += 256)
+            out[r] = out[r] + rt_pow<10>(c, (int)(E - r)) * carry;
+    }
+}
+
 __global__ void k_count_err(const uint8_t* err, int n, unsigned long long* out) {
     int i = blockIdx.x * BLOCK + threadIdx.x;
     bool e = i < n && err[i] != 0;
@@ -318,7 +475,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 extern "C" {
 
-int vs_version(void) { return 305; }
+int vs_version(void) { return 306; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1205,6 +1362,34 @@ int vs_pack_traj(vs_handle h, int n_lanes, int t_steps, const int64_t* lengths, 
     HIPCHK(h, hipSetDevice(h->device));
     DISPATCH_ENV(h->type, Launch<E>::pack_traj(h, n_lanes, t_steps, (const long long*)lengths, (const long long*)starts, rows));
     HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_returns_scan(int device_id, void* hip_stream, int64_t n, const int64_t* lengths, const int64_t* starts, const float* rew,
+                    int64_t rew_stride, const float* values, int64_t values_stride, const uint8_t* done_last, float gamma, float lam,
+                    int mode, float* out, float* out_first) {
+    // every refusal comes before the first device call
+    if (n <= 0 || n > INT32_MAX) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: n must be in 1 .. 2^31 - 1");
+    if (!lengths || !starts || !rew || !out) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: lengths, starts, rew and out must not be NULL");
+    if (mode != VS_RETURNS_RETURN && mode != VS_RETURNS_GAE) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: unknown mode");
+    if (mode == VS_RETURNS_GAE && !values) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: VS_RETURNS_GAE needs values");
+    if (rew_stride < 1 || (values && values_stride < 1)) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: a row stride below 1");
+    if (!(gamma >= 0.f && gamma <= 1.f)) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: gamma outside [0, 1]");
+    if (!(lam >= 0.f && lam <= 1.f)) return fail(nullptr, VS_ERR_ARG, "vs_returns_scan: lam outside [0, 1]");
+    HIPCHK(nullptr, hipSetDevice(device_id));
+    int cus = 0;
+    HIPCHK(nullptr, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id));
+    // the number of rows is device data (starts[n - 1] + lengths[n - 1] + n): a grid that fills the chip walks the tiles
+    const dim3 tiles((unsigned)(cus > 0 ? cus * 8 : 2048)), blk(256);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int gae = mode == VS_RETURNS_GAE;
+    const float c = gae ? (float)((double)gamma * (double)lam) : gamma;  // one rounding
+    const long long *len = (const long long*)lengths, *sta = (const long long*)starts;
+    hipLaunchKernelGGL(k_returns_scan, tiles, blk, 0, st, (int)n, len, sta, rew, (long long)rew_stride, values, (long long)values_stride,
+                       done_last, gamma, c, gae, out);
+    hipLaunchKernelGGL(k_returns_carry, dim3((unsigned)((n + 255) / 256)), blk, 0, st, (int)n, len, sta, c, out, out_first);
+    hipLaunchKernelGGL(k_returns_apply, tiles, blk, 0, st, (int)n, len, sta, c, out);
+    HIPCHK(nullptr, hipGetLastError());
     return VS_OK;
 }
 

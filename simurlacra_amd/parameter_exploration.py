@@ -77,6 +77,22 @@ class ParameterSamplingResult(Sequence[ParameterSample]):
         return sum(s.num_rollouts for s in self._samples)
 
 
+class PopulationReturns:
+    """What sample_returns() hands the episodic algorithms, all on the device: `parameters` [P, n_params], `returns` [P, R]
+    (float32: the discounted return of rollout r of set s), `lengths` [P, R] (int64), `mean_returns` [P] and `packed`, the
+    PackedRollouts of every batch (padding lanes included, see population_lane_layout)"""
+
+    def __init__(self, parameters, returns, lengths, packed):
+        self.parameters, self.returns, self.lengths, self.packed = parameters, returns, lengths, packed
+
+    @property
+    def mean_returns(self) -> torch.Tensor:
+        return self.returns.mean(dim=1)
+
+    def __len__(self) -> int:
+        return int(self.returns.shape[0])
+
+
 # ------------------------------------------------------------------------------------------------ pure functions
 def draw_domain_params(dr_wrapper, num_domains: int) -> list:
     """`num_domains` domain parameter sets for one sample() call: a live randomizer's draws, random entries of a buffer
@@ -220,6 +236,39 @@ class ParameterExploringSampler:
                                            population=dict(params=params[s0:s0 + nb], lane_set=lane_set, real=real))
             out += [ros[k * R:(k + 1) * R] for k in range(nb)]
         return out
+
+    def sample_returns(self, param_sets, init_states: Optional[List[np.ndarray]] = None, gamma: float = 1.0) -> PopulationReturns:
+        """sample() for the algorithms that consume the returns per parameter set only (HC, PEPG, NES, CEM, REPS): the same draws,
+        work list, lanes, batches and Philox keys, but every batch stays on the device as a PackedRollouts and its discounted
+        returns come from vs_returns_scan -- no StepSequence is built and nothing is copied to the host.  Needs a policy the fused
+        kernel evaluates (ValueErr otherwise)."""
+        # (sample()'s own preamble, statement for statement: sample() itself stays as it is)
+        params = torch.as_tensor(param_sets).detach()
+        if params.dim() == 1:
+            params = params.unsqueeze(0)
+        if params.dim() != 2 or params.shape[0] < 1:
+            raise ValueErr(msg=f"param_sets must be [num_sets, num_params], got shape {tuple(params.shape)}")
+        params = params.to(torch.float32)
+        dps = draw_domain_params(self._dr_wrapper, self.num_domains)
+        inits = draw_init_states(inner_env(self.env).init_space, self.num_init_states_per_domain, init_states)
+        work = param_work_list(dps, inits)
+        self._sampler._sample_count += 1
+        R = len(work)
+        stride, batches = population_lane_layout(params.shape[0], R, self._batch_lanes)
+        rets, lens, packed = [], [], []
+        for s0, nb in batches:
+            work_b = [_PAD] * (nb * stride)
+            for k in range(nb):
+                work_b[k * stride:k * stride + R] = work
+            real = population_real_lanes(nb, R, stride)
+            p = self._sampler._run_batch(work_b, lane_of(s0, 0, stride), True, packed_out=True,
+                                         population=dict(params=params[s0:s0 + nb], lane_set=population_lane_set(nb, stride),
+                                                         real=real))
+            real_t = torch.as_tensor(real, dtype=torch.int64, device=p.lengths.device)  # the padding lanes drop out by index
+            rets.append(p.discounted_returns(gamma).index_select(0, real_t).view(nb, R))
+            lens.append(p.lengths.index_select(0, real_t).view(nb, R))
+            packed.append(p)
+        return PopulationReturns(params.to(rets[0].device), torch.cat(rets), torch.cat(lens), packed)
 
     def _sample_loop(self, params, work, stride):
         """the sets one after the other through ParallelRolloutSampler's path: policy.param_values = the set's vector (the

@@ -137,7 +137,10 @@ class PackedRollouts:
       states [total + n, S] | None  actions_applied [total + n, A] | None   th_ddot [total + n] | None  (full records)
       hidden_states [total + n, H] | None  (a recurrent policy: its hidden state before every step; 0 in the final entry)
       lengths [n] (int64)   offsets [n + 1] (int64: exclusive cumulative lengths)   total = offsets[n]
-      done_last [n] (bool: the rollout ended by done, not by the step limit)
+      done_last [n] (bool: StepSequence.done[-1] -- the env's done flag of the last step, which the step limit sets too, as in the
+                     reference: True for a failure AND for a time-out)
+      failed_last [n] (bool: the last step left the task's state space (Task.has_failed, VS_FAILED): the rollout ended by failure,
+                     not by the step limit -- the rollouts whose final value must NOT bootstrap)
       init_states [n, S]    first_index: rollout number of rollout 0 within the sample() call
 
     `step_slice(j)` are the rows of rollout j's steps, `obs_slice(j)` those plus the final entry; `step_rows()` the row indices of
@@ -187,6 +190,97 @@ class PackedRollouts:
 
         out = torch.zeros(len(self), device=self.rewards.device, dtype=self.rewards.dtype)
         return out.index_add_(0, self.row_rollout_index(), self.rewards)
+
+    # ---- per-step and per-rollout returns: vs_returns_scan on torch's current stream, no host loop and no synchronisation
+    def _values_arg(self, values):
+        import torch
+
+        rows = self.total_steps + len(self)
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.float32:
+            raise ValueErr(msg="values must be a float32 torch tensor")
+        if values.device != self.rewards.device:
+            raise ValueErr(msg=f"values live on {values.device}, the rollouts on {self.rewards.device}")
+        if values.numel() != rows:
+            raise ValueErr(msg=f"values need one entry per packed row ({rows}), got {values.numel()}")
+        values = values.reshape(-1)  # (a view wherever the strides allow one)
+        return values if values.stride(0) >= 1 else values.contiguous()
+
+    def _scan(self, mode, gamma, lam=1.0, values=None, want_first=False):
+        # vs_returns_scan's `done_last` argument is "this rollout's final value does not bootstrap": the failures.  (The env's done
+        # flag, self.done_last, is set at the step limit too and would zero every bootstrap.)
+        return returns_scan(self.lengths, self.offsets[:-1], self.rewards, self.total_steps + len(self), mode, gamma, lam,
+                            None if values is None else self._values_arg(values), None if values is None else self.failed_last,
+                            want_first)
+
+    def discounted_returns(self, gamma: float):
+        """[n] float32 on the device: sum_t gamma^t r_t of every rollout (StepSequence.discounted_return)"""
+        return self._scan(L.VS_RETURNS_RETURN, gamma, want_first=True)[1]
+
+    def rewards_to_go(self, gamma: float, values=None):
+        """[total + n] float32 on the packed rows: the discounted reward-to-go of every step.  With `values` (one per packed row,
+        the value of `observations[row]`) a rollout that ended by the step limit (`~failed_last`) bootstraps with the value of its
+        final observation; the final-entry rows hold that bootstrap value (0 without values and after a failure)."""
+        return self._scan(L.VS_RETURNS_RETURN, gamma, values=values)[0]
+
+    def gae(self, values, gamma: float, lam: float):
+        """[total + n] float32 on the packed rows: the generalised advantage estimate of every step from `values` (one per packed
+        row, the value of `observations[row]`; the final value of a rollout that ended by failure, `failed_last`, counts 0, that of
+        a time-out bootstraps); 0 in the final-entry rows"""
+        if values is None:
+            raise ValueErr(msg="gae() needs values")
+        return self._scan(L.VS_RETURNS_GAE, gamma, lam, values=values)[0]
+
+    def select_cvar(self, epsilon: float, gamma: float = 1.0):
+        """int64 indices of the round(n * epsilon) rollouts with the lowest discounted return, lowest first (ties in rollout
+        order): select_cvar() on the device"""
+        import torch
+
+        keep = round(len(self) * epsilon)
+        if keep == 0:
+            raise ValueErr(given=keep, g_constraint="0")
+        return torch.sort(self.discounted_returns(gamma), stable=True).indices[:keep]
+
+
+def packed_row_layout(lengths):
+    """(starts, base rows, final-entry rows, number of rows) of rollouts packed as PackedRollouts / vs_pack_traj pack them: rollout
+    j owns rows base[j] .. final[j] = base[j] + lengths[j], base[j] = starts[j] + j, starts = the exclusive running sum"""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    starts = np.cumsum(lengths) - lengths
+    base = starts + np.arange(len(lengths), dtype=np.int64)
+    return starts, base, base + lengths, int(lengths.sum()) + len(lengths)
+
+
+def returns_scan(lengths, starts, rew, rows, mode, gamma, lam=1.0, values=None, done_last=None, want_first=False):
+    """vs_returns_scan on torch's current stream.  lengths / starts: int64 device tensors [n]; rew / values: 1-D float32 device
+    tensors over the packed rows (any stride >= 1); done_last: bool / uint8 [n] or None; rows = total + n.
+    Returns (out [rows], out_first [n] | None)."""
+    import ctypes as C
+
+    import torch
+
+    lib = L.load()
+    dev = rew.device
+    n = int(lengths.shape[0])
+    lengths, starts = lengths.to(torch.int64).contiguous(), starts.to(torch.int64).contiguous()
+    out = torch.empty(int(rows), dtype=torch.float32, device=dev)
+    first = torch.empty(n, dtype=torch.float32, device=dev) if want_first else None
+    if done_last is not None:
+        if done_last.shape != (n,) or done_last.device != dev:
+            raise ValueErr(msg=f"done_last needs one entry per rollout ({n}) on {dev}")
+        done_last = done_last.contiguous()
+        done_last = done_last.view(torch.uint8) if done_last.dtype == torch.bool else done_last.to(torch.uint8)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(dev).cuda_stream or 1  # (0 = the legacy default stream = hipStreamLegacy)
+    rc = lib.vs_returns_scan(index, C.c_void_p(stream), n, ptr(lengths), ptr(starts), ptr(rew), int(rew.stride(0)), ptr(values),
+                             1 if values is None else int(values.stride(0)), ptr(done_last), float(gamma), float(lam), int(mode),
+                             ptr(out), ptr(first))
+    if rc != L.VS_OK:
+        msg = lib.vs_last_error(None).decode()
+        if rc == L.VS_ERR_ARG:
+            raise ValueErr(msg=msg)
+        raise RuntimeError(f"vs_returns_scan failed ({rc}): {msg}")
+    return out, first
 
 
 def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, reset_kwargs: Optional[dict] = None,
@@ -677,7 +771,8 @@ class ParallelRolloutSampler:
                 rows=rows, observations=visible(pk["obs"], 1), actions=pk["act"], rewards=pk["rew"],
                 states=pk["state"] if full else None, actions_applied=pk["act_app"] if full else None,
                 th_ddot=pk["hidden"][:, 0] if qcp_dev else None, lengths=length, offsets=torch.cat([start, start[-1:] + length[-1:]]),
-                total=total, done_last=done_last_d, init_states=state0.contiguous(), first_index=first_index, hidden_states=hid_rows,
+                total=total, done_last=done_last_d, failed_last=v.tensor(L.VS_FAILED)[0, :n].bool(), init_states=state0.contiguous(),
+                first_index=first_index, hidden_states=hid_rows,
                 env_name=base.name, dt=base.dt, param_names=v.param_names, domain_params=v.tensor(L.VS_PARAMS)[:, :n].t().clone())
         # device -> host: the matrix in one transfer into pinned memory; the rollouts' fields are views of that block (rewards:
         # one conversion to float64 for all rollouts)
