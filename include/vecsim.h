@@ -180,6 +180,44 @@ typedef struct vs_rnn_desc {
     float noise_std[2];    /* exploration: + std * N(0, 1) per action dimension (NormalActNoiseExplStrat); 0 = none */
 } vs_rnn_desc;
 
+/* A linear policy on a stack of feature functions for vs_step_policy: LinearPolicy(spec, feats=FeatureStack(...)) of
+ * P/policies/feed_forward/linear.py over P/policies/features.py -- act = W phi(obs), W [A][F] without a bias.  The descriptor lists
+ * the stack's terms in stack order.  An elementwise kind (VS_FEAT_IDENTITY .. VS_FEAT_SINCOS) maps every visible observation row
+ * and so contributes n_obs features; VS_FEAT_CONST (the constant 1), VS_FEAT_MULT (MultFeat: the product of 2 .. 4 rows) and
+ * VS_FEAT_ATAN2 (ATan2Feat: atan2(row idx[0], row idx[1])) contribute one each.  Their indices count the VISIBLE rows.
+ * Limits: every elementwise kind and VS_FEAT_CONST at most once, at most VS_LIN_MAX_XTERMS MultFeat / ATan2Feat terms and at
+ * most VS_LIN_MAX_FEAT features in all.  sin and cos come from the library's bounded-angle sincos: the fused linear policy is
+ * valid for observations |obs| < ~1e3 (RBFFeat is not supported). */
+#define VS_FEAT_IDENTITY 0 /* x */
+#define VS_FEAT_SIGN 1     /* sign x */
+#define VS_FEAT_ABS 2      /* |x| */
+#define VS_FEAT_SQUARED 3  /* x^2 */
+#define VS_FEAT_CUBIC 4    /* x^3 */
+#define VS_FEAT_SIG 5      /* 1 / (1 + exp(-x)) */
+#define VS_FEAT_BELL 6     /* exp(-x^2 / 2) */
+#define VS_FEAT_SIN 7      /* sin x */
+#define VS_FEAT_COS 8      /* cos x */
+#define VS_FEAT_SINSIN 9   /* sin^2 x */
+#define VS_FEAT_SINCOS 10  /* sin x cos x */
+#define VS_FEAT_CONST 11   /* 1 (one feature) */
+#define VS_FEAT_MULT 12    /* MultFeat(idcs): prod_r obs[idx[r]], n_idx = 2 .. 4 (one feature) */
+#define VS_FEAT_ATAN2 13   /* ATan2Feat(idx_sin, idx_cos): atan2(obs[idx[0]], obs[idx[1]]), n_idx = 2 (one feature) */
+#define VS_LIN_MAX_XTERMS 39
+#define VS_LIN_MAX_TERMS 51 /* 12 + VS_LIN_MAX_XTERMS */
+#define VS_LIN_MAX_FEAT 128
+typedef struct vs_lin_term {
+    int32_t kind;   /* VS_FEAT_* */
+    int32_t n_idx;  /* VS_FEAT_MULT: 2 .. 4, VS_FEAT_ATAN2: 2, ignored otherwise */
+    int32_t idx[4]; /* indices into the visible observation rows */
+} vs_lin_term;
+typedef struct vs_lin_desc {
+    int32_t n_terms;                     /* 1 .. VS_LIN_MAX_TERMS */
+    vs_lin_term terms[VS_LIN_MAX_TERMS]; /* the stack, in order */
+    int32_t n_obs;                       /* number of observation rows the policy sees; 0 = all of them, in order */
+    int32_t obs_idx[8];                  /* ... and which (as vs_fnn_desc) */
+    float noise_std[2];                  /* exploration: + std * N(0, 1) per action dimension (NormalActNoiseExplStrat); 0 = none */
+} vs_lin_desc;
+
 typedef struct vs_env* vs_handle;
 
 /* ---- static information (no GPU needed) ---- */
@@ -321,6 +359,16 @@ int vs_set_policy_shape(vs_handle h, int shape);
  * launch.  desc == NULL removes the policy; setting one removes a network of vs_set_policy_fnn and the other way round.
  * Refused like vs_set_policy_fnn (wrapper pipeline VS_ERR_STATE, discrete family / sizes / limits VS_ERR_ARG). */
 int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params, int64_t n_params);
+/* vs_step_policy with a linear policy on a feature stack (vs_lin_desc).  `params` is the policy's flat parameter vector in torch
+ * order -- net.weight [A][F] row-major, F features in stack order -- host or device memory, copied (n_params = A * F).
+ * desc == NULL removes the policy; setting a linear policy removes a policy of vs_set_policy_fnn / vs_set_policy_rnn and any
+ * population, and the other way round.  vs_set_policy_population then takes sets of A * F floats each.  Records, auto-reset,
+ * freeze-at-done and launch cuts as for vs_set_policy_fnn; vs_set_policy_shape has no meaning for a linear policy and is ignored.
+ * Refused with the previous policy (and population) left in place: a wrapper pipeline on the handle (VS_ERR_STATE); the
+ * discrete-action family, an unknown kind, an elementwise kind or VS_FEAT_CONST twice, an index outside the visible rows, a
+ * MultFeat of fewer than 2 or more than 4 rows, more than VS_LIN_MAX_XTERMS / VS_LIN_MAX_FEAT terms / features, a negative or NaN
+ * noise_std, n_params != A * F (VS_ERR_ARG). */
+int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* params, int64_t n_params);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);
@@ -328,7 +376,8 @@ int vs_set_policy_hidden_record(vs_handle h, int width);
  * hidden[i * env_stride + j * dim_stride], width units) into row `row` of VS_POLICY_HIDDEN_REC; row < 0: the device-side
  * counter of vs_step_record, NOT advanced -- call it before the vs_step_record of the same step (captured graphs replay it) */
 int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64_t dim_stride, int row);
-/* A population for vs_step_policy: n_sets parameter vectors of the policy last set by vs_set_policy_fnn / vs_set_policy_rnn
+/* A population for vs_step_policy: n_sets parameter vectors of the policy last set by vs_set_policy_fnn / vs_set_policy_rnn /
+ * vs_set_policy_linear
  * (same architecture; vector s at params + s * n_params, each laid out like that call's `params`; host or device memory,
  * copied and packed on the device).  lane_set[i] (host, n entries) = the set lane i runs, or -1: the lane takes no part.
  * params == NULL removes the population (the single policy of the last vs_set_policy_* call applies again).
@@ -337,7 +386,7 @@ int vs_record_hidden(vs_handle h, const float* hidden, int64_t env_stride, int64
  * to name one set: the automatic choice falls back to shape 0, a pinned shape 1 or 2 makes vs_step_policy return
  * VS_ERR_STATE.  With a population vs_step_policy records (record != 0) and runs with auto-reset off (VS_ERR_STATE
  * otherwise); it leaves the -1 lanes alone -- no step, no record row written -- and vs_rollout_lengths reports 0 for them
- * (also after a vs_reset).  vs_set_policy_fnn / vs_set_policy_rnn (a NULL desc included) remove the population. */
+ * (also after a vs_reset).  vs_set_policy_fnn / vs_set_policy_rnn / vs_set_policy_linear (a NULL desc included) remove the population. */
 int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params, int n_sets, const int32_t* lane_set);
 /* The recorded steps of lanes 0 .. n_lanes - 1 (rows 0 .. of VS_TRAJ_REC, vs_set_record_mode's layout) as ROLLOUTS in one row-major
  * matrix rows[total + n_lanes][F] (F = vs_traj_layout's record width, device memory): rollout j = steps 0 .. lengths[j] - 1 of

@@ -37,8 +37,14 @@ def __getattr__(name):
 
         return getattr(parameter_exploration, name)
     if name in ("DummyPolicy", "IdlePolicy", "Policy", "FNN", "FNNPolicy", "NormalActNoiseExplStrat", "fnn_kernel_spec",
-                "RecurrentPolicy", "RNNPolicy", "GRUPolicy", "LSTMPolicy", "rnn_kernel_spec"):
+                "RecurrentPolicy", "RNNPolicy", "GRUPolicy", "LSTMPolicy", "rnn_kernel_spec", "LinearPolicy",
+                "linear_kernel_spec"):
         from . import policies
 
         return getattr(policies, name)
+    if name in ("FeatureStack", "MultFeat", "ATan2Feat", "const_feat", "identity_feat", "sign_feat", "abs_feat", "squared_feat",
+                "cubic_feat", "sig_feat", "bell_feat", "sin_feat", "cos_feat", "sinsin_feat", "sincos_feat"):
+        from . import features
+
+        return getattr(features, name)
     raise AttributeError(name)

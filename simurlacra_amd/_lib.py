@@ -17,6 +17,10 @@ VS_NL_NONE, VS_NL_TANH, VS_NL_RELU, VS_NL_SIGMOID = 0, 1, 2, 3  # vs_fnn_desc no
 VS_FNN_MAX_HIDDEN, VS_FNN_MAX_WIDTH = 4, 64
 VS_RNN_TANH, VS_RNN_RELU, VS_RNN_GRU, VS_RNN_LSTM = 0, 1, 2, 3  # vs_rnn_desc cells
 VS_RNN_MAX_LAYERS, VS_RNN_MAX_HIDDEN = 2, 64
+# vs_lin_desc feature kinds (the elementwise ones first), and its limits
+(VS_FEAT_IDENTITY, VS_FEAT_SIGN, VS_FEAT_ABS, VS_FEAT_SQUARED, VS_FEAT_CUBIC, VS_FEAT_SIG, VS_FEAT_BELL, VS_FEAT_SIN, VS_FEAT_COS,
+ VS_FEAT_SINSIN, VS_FEAT_SINCOS, VS_FEAT_CONST, VS_FEAT_MULT, VS_FEAT_ATAN2) = range(14)
+VS_LIN_MAX_XTERMS, VS_LIN_MAX_TERMS, VS_LIN_MAX_FEAT = 39, 51, 128
 VS_DP_NORMAL, VS_DP_UNIFORM, VS_DP_BERNOULLI = 0, 1, 2
 VS_MAX_ACT_DELAY = 64
 VS_RETURNS_RETURN, VS_RETURNS_GAE = 0, 1  # vs_returns_scan modes
@@ -42,6 +46,15 @@ class FnnDesc(C.Structure):
 class RnnDesc(C.Structure):
     _fields_ = [("cell", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32), ("out_nonlin", C.c_int32),
                 ("n_obs", C.c_int32), ("obs_idx", C.c_int32 * 8), ("noise_std", C.c_float * 2)]
+
+
+class LinTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_idx", C.c_int32), ("idx", C.c_int32 * 4)]
+
+
+class LinDesc(C.Structure):
+    _fields_ = [("n_terms", C.c_int32), ("terms", LinTerm * VS_LIN_MAX_TERMS), ("n_obs", C.c_int32), ("obs_idx", C.c_int32 * 8),
+                ("noise_std", C.c_float * 2)]
 
 
 _P = C.c_void_p
@@ -83,6 +96,7 @@ _SIGNATURES = {
     "vs_step_policy": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64]),
     "vs_set_policy_shape": (C.c_int, [_P, C.c_int]),
     "vs_set_policy_rnn": (C.c_int, [_P, C.POINTER(RnnDesc), _P, C.c_int64]),
+    "vs_set_policy_linear": (C.c_int, [_P, C.POINTER(LinDesc), _P, C.c_int64]),
     "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
     "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),
     "vs_set_policy_population": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),

@@ -475,7 +475,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 extern "C" {
 
-int vs_version(void) { return 306; }
+int vs_version(void) { return 307; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -621,6 +621,7 @@ int vs_destroy(vs_handle h) {
     if (h->d_ring) (void)hipFree(h->d_ring);
     if (h->fnn.w) (void)hipFree((void*)h->fnn.w);
     if (h->rnn.w) (void)hipFree((void*)h->rnn.w);
+    if (h->lin.w) (void)hipFree((void*)h->lin.w);
     if (h->rnn.hid) (void)hipFree(h->rnn.hid);
     if (h->pop.w) (void)hipFree((void*)h->pop.w);
     if (h->pop.wg_set) (void)hipFree((void*)h->pop.wg_set);
@@ -1038,6 +1039,12 @@ static int drop_rnn(vs_handle h) {
     return VS_OK;
 }
 
+static int drop_lin(vs_handle h) {
+    if (h->lin.w) HIPCHK(h, hipFree((void*)h->lin.w));
+    h->lin = Lin{};
+    return VS_OK;
+}
+
 // the packed vector of one policy from its index map (packed slot -> source index, -1: zero padding)
 static std::vector<float> pack_by_map(const std::vector<int>& map, const std::vector<float>& src) {
     std::vector<float> pk(map.size(), 0.f);
@@ -1053,6 +1060,7 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }
     h->fnn = Fnn{};
     if (int rc = drop_rnn(h)) return rc;  // one in-kernel policy at a time
+    if (int rc = drop_lin(h)) return rc;
     if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
     h->pol_map.clear();
     h->pol_n_params = 0;
@@ -1137,6 +1145,7 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     if (int rc = drop_rnn(h)) return rc;
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
     h->fnn = Fnn{};
+    if (int rc = drop_lin(h)) return rc;
     if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
     h->pol_map.clear();
     h->pol_n_params = 0;
@@ -1219,6 +1228,86 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     return VS_OK;
 }
 
+int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* params, int64_t n_params) {
+    if (!h) return VS_ERR_ARG;
+    Lin f{};
+    std::vector<int> map;
+    int64_t need = 0;
+    if (desc) {  // every check before anything is dropped: a refused call leaves the previous policy and population in place
+        const EnvInfo& ei = ENV_INFO[h->type];
+        if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: the discrete-action family takes no in-kernel policy");
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_policy_linear: not available with a wrapper pipeline on the handle");
+        if (!params || desc->n_terms < 1 || desc->n_terms > VS_LIN_MAX_TERMS) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: 1 .. 51 terms and a parameter vector");
+        f.n_vis = desc->n_obs > 0 ? desc->n_obs : ei.O;
+        if (f.n_vis > ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: more visible observation rows than the env has");
+        f.ident = f.n_vis == ei.O;
+        for (int k = 0; k < f.n_vis; ++k) {
+            f.obs_idx[k] = desc->n_obs > 0 ? desc->obs_idx[k] : k;
+            if (f.obs_idx[k] < 0 || f.obs_idx[k] >= ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: obs_idx out of range");
+            if (f.obs_idx[k] != k) f.ident = 0;
+        }
+        for (int j = 0; j < ei.A; ++j) {
+            f.noise_std[j] = desc->noise_std[j];
+            if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: noise_std must be >= 0");
+            if (f.noise_std[j] > 0.f) f.noisy = 1;
+        }
+        // feature q of the stack -> slot of a packed weight row (see k_rollout_lin)
+        std::vector<int> slot;
+        for (int t = 0; t < desc->n_terms; ++t) {
+            const vs_lin_term& tm = desc->terms[t];
+            if (tm.kind < 0 || tm.kind > VS_FEAT_ATAN2) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: unknown feature kind");
+            if (tm.kind <= VS_FEAT_CONST) {
+                if (f.kinds & (1u << tm.kind)) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: an elementwise kind (or the constant) appears twice in the stack");
+                f.kinds |= 1u << tm.kind;
+                if (tm.kind == VS_FEAT_CONST) slot.push_back(LIN_CONST_SLOT);
+                else for (int k = 0; k < f.n_vis; ++k) slot.push_back(tm.kind * MAXO + k);
+                continue;
+            }
+            const bool at = tm.kind == VS_FEAT_ATAN2;
+            if (at ? tm.n_idx != 2 : (tm.n_idx < 2 || tm.n_idx > 4)) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: MultFeat takes 2 .. 4 rows, ATan2Feat 2");
+            if (f.n_x >= LIN_MAXX) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: more than 39 MultFeat / ATan2Feat terms");
+            unsigned xt = at ? 0x80000000u : ((unsigned)(tm.n_idx - 2) << 12);
+            for (int r = 0; r < tm.n_idx; ++r) {
+                if (tm.idx[r] < 0 || tm.idx[r] >= f.n_vis) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: a feature index outside the visible observation rows");
+                xt |= (unsigned)f.obs_idx[tm.idx[r]] << (3 * r);
+            }
+            slot.push_back(LIN_CONST_SLOT + 1 + f.n_x);
+            f.xterm[f.n_x++] = xt;
+        }
+        const int F = (int)slot.size();
+        if (F > VS_LIN_MAX_FEAT) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: more than 128 features");
+        need = (int64_t)ei.A * F;
+        if (n_params != need) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: parameter count is not (action dimensions) x (features)");
+        map.assign((size_t)ei.A * LIN_SLOTS, -1);
+        for (int j = 0; j < ei.A; ++j)
+            for (int q = 0; q < F; ++q) map[(size_t)j * LIN_SLOTS + slot[q]] = j * F + q;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float* dw = nullptr;
+    if (desc) {
+        std::vector<float> src((size_t)need);
+        HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+        const std::vector<float> pk = pack_by_map(map, src);
+        HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
+        hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_linear: upload", e); }
+    }
+    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
+    h->fnn = Fnn{};
+    if (int rc = drop_rnn(h)) return rc;
+    if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
+    h->pol_map.clear();
+    h->pol_n_params = 0;
+    if (!desc) return VS_OK;
+    f.w = dw;
+    h->lin = f;
+    h->pol_map = std::move(map);
+    h->pol_n_params = need;
+    return VS_OK;
+}
+
 int vs_set_policy_hidden_record(vs_handle h, int width) {
     if (!h || width < 0 || width > 2 * RNN_MAXL * RNN_MAXW * 4) return fail(h, VS_ERR_ARG, "vs_set_policy_hidden_record: bad width");
     if (width == h->hrec_width) return VS_OK;
@@ -1249,7 +1338,7 @@ int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params,
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still read the sets this replaces)
     if (!params) return drop_pop(h);
-    if (!h->fnn.w && !h->rnn.w) return fail(h, VS_ERR_STATE, "vs_set_policy_population: no policy set (vs_set_policy_fnn / vs_set_policy_rnn)");
+    if (!h->fnn.w && !h->rnn.w && !h->lin.w) return fail(h, VS_ERR_STATE, "vs_set_policy_population: no policy set (vs_set_policy_fnn / vs_set_policy_rnn / vs_set_policy_linear)");
     if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, "vs_set_policy_population: parameter count does not match the policy's");
     if (n_sets < 1 || !lane_set) return fail(h, VS_ERR_ARG, "vs_set_policy_population: n_sets >= 1 and a lane table");
     // the set of every aligned group of 64 lanes (groups past n_envs: -1), and whether groups of 256 agree as well
@@ -1324,6 +1413,14 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
         HIPCHK(h, hipSetDevice(h->device));
         h->rnn.hrec = h->d_hrec;
         DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
+        HIPCHK(h, hipGetLastError());
+        return VS_OK;
+    }
+    if (h->lin.w) {
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
+        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
+        HIPCHK(h, hipSetDevice(h->device));
+        DISPATCH_ENV(h->type, Launch<E>::rollout_lin(h, k_steps, record ? h->record_mode : 0, noise_seed));
         HIPCHK(h, hipGetLastError());
         return VS_OK;
     }

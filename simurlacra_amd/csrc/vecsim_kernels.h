@@ -1640,6 +1640,238 @@ __global__ __launch_bounds__(64) void k_rollout_rnn(Task T, Dev d, Rnn P, int k_
         for (int j = 0; j < H; ++j, ++p) P.hid[(size_t)p * ld + i] = ls[(q * hp + j) * 64];
 }
 
+// ---------------------------------------------------------------------------------- linear policy on a feature stack
+// vs_step_policy with a linear policy (vs_set_policy_linear): LinearPolicy(spec, feats=FeatureStack(...)) of
+// P/policies/feed_forward/linear.py over the feature functions of P/policies/features.py -- act = W phi(obs), no bias -- evaluated
+// INSIDE the fused rollout kernel.  Nothing here is matrix-shaped: one env per lane, one wave of 64 envs per workgroup (the
+// population granularity of the other two policy kernels), no LDS, no barrier.
+//   * The weights are wave-uniform: read through the constant address space (scalar loads), every FMA takes its weight as the
+//     uniform operand.  They sit in a FIXED slot order, whatever the stack's order (vs_set_policy_linear packs through an index
+//     map; slots the stack does not use hold 0):
+//       row j of W = LIN_SLOTS floats:  [kind q < 11][visible row k < 8] at 8 q + k | const at 88 | extra term e at 89 + e
+//   * Which kinds the stack holds is wave-uniform too: one bit per kind in Lin::kinds, so a kind that is not there costs a scalar
+//     branch.  Inside a kind the loop over the observation rows has compile-time length E::O; a row the policy does not see
+//     (k >= n_vis) is 0 with weight 0 (every feature of 0 is finite).
+//   * sin / cos / sin^2 / sin cos of a row share one sincos_fast (valid for |obs| < ~1e3, its stated range); sigmoid and the
+//     bell through v_exp_f32 as in fnn_nonlin -- with the bare v_rcp_f32 (1 ulp): rcp_fast's Newton step makes NaN of 1 / inf,
+//     which sigmoid reaches at obs < -88; atan2 is the device library's.
+//   * MultFeat / ATan2Feat terms are a uniform run-time loop; their observation rows come out of the lane's registers through
+//     uniform selects (the host has already mapped the stack's indices, which count visible rows, to observation rows).
+//   * The env step behind the policy is k_rollout_fnn's, statement for statement (same records, auto-reset, freeze-at-done).
+constexpr int LIN_ELEM = 11;                       // elementwise kinds, VS_FEAT_IDENTITY .. VS_FEAT_SINCOS
+constexpr int LIN_MAXX = 39;                       // MultFeat / ATan2Feat terms
+constexpr int LIN_CONST_SLOT = LIN_ELEM * MAXO;    // 88
+constexpr int LIN_SLOTS = LIN_CONST_SLOT + 1 + LIN_MAXX;  // 128 floats per action dimension
+enum LinKind { LIN_ID = 0, LIN_SIGN = 1, LIN_ABS = 2, LIN_SQ = 3, LIN_CUBIC = 4, LIN_SIG = 5, LIN_BELL = 6, LIN_SIN = 7, LIN_COS = 8,
+               LIN_SINSIN = 9, LIN_SINCOS = 10, LIN_CONST = 11, LIN_MULT = 12, LIN_ATAN2 = 13 };
+struct Lin {
+    const float* w;  // device, packed by vs_set_policy_linear: [A][LIN_SLOTS] (see above)
+    unsigned kinds;  // bit q: the stack holds kind q (q <= LIN_CONST)
+    int n_x;         // MultFeat / ATan2Feat terms
+    int n_vis, ident, noisy;
+    int obs_idx[MAXO];
+    float noise_std[MAXA];
+    // extra term e: bit 31 = ATan2Feat (rows: sin, cos), else MultFeat of 2 + (bits 12 .. 13) rows; OBSERVATION row r in bits 3 r .. 3 r + 2
+    unsigned xterm[LIN_MAXX];
+};
+
+template <class E, bool AR, int REC, bool POP = false>
+__global__ __launch_bounds__(64) void k_rollout_lin(Task T, Dev d, Lin P, int k_steps, uint64_t reset_seed, uint64_t noise_seed,
+                                                    Pop pop) {
+    typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
+    constexpr bool UNI = false;
+    const float* w0 = P.w;
+    if constexpr (POP) {  // the workgroup's parameter set moves the scalar-load base; -1: nothing to do
+        const int set = __builtin_amdgcn_readfirstlane(pop.wg_set[blockIdx.x]);  // (uniform by construction)
+        if (set < 0) return;
+        w0 = pop.w + (size_t)set * (size_t)pop.stride;
+    }
+    const cfp W = (cfp)w0;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const size_t rec0 = (size_t)d.traj_t0;
+    const bool valid = i < d.n;
+    const unsigned kinds = P.kinds;
+
+    // ---- env state of the lane (k_rollout_fnn's)
+    float c[E::K], s[E::S], h[E::H > 0 ? E::H : 1], a[E::A], ob[E::O];
+    float alo[E::A], ahi[E::A];
+    int step = 0;
+    float ret = 0.f, rew = 0.f;
+    bool yielded = false, frozen = false, done = false, failed = false;
+    EpStat es{0u, 0u, 0.f, 0};
+    DoneBits db;
+    db.w = 0u;
+    load_consts<E, UNI>(d, i, c, 0, E::KS);
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) s[j] = d.state[j * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) h[j] = d.hidden[j * ld + i];
+    step = d.step[i];
+    ret = d.ret[i];
+    yielded = E::FINAL != FINAL_NONE ? d.yielded[i] != 0 : false;
+    frozen = !AR && d.done[i] != 0;
+    rew = d.rew[i];
+    done = d.done[i] != 0, failed = d.failed[i] != 0;
+    es = EpStat{d.ep_idx[i], d.es_count[i], d.es_retsum[i], d.es_lensum[i]};
+    E::act_bounds(c, alo, ahi);
+    E::observe(s, ob);
+    if (REC) db.begin(d, i, rec0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (see rollout_body: nothing pending at the loop header)
+
+    for (int t = 0; t < k_steps; ++t) {
+        // ---- what the policy sees of obs_t
+        float x[E::O];
+        if (P.ident) {
+#pragma unroll
+            for (int k = 0; k < E::O; ++k) x[k] = ob[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < E::O; ++k) {
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                x[k] = v;
+            }
+        }
+        // ---- act = W phi(x), kind by kind
+        float out[E::A];
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) out[j] = 0.f;
+        // (f: the feature of row k as an expression of v = x[k])
+#define VS_LIN_KIND(q, f)                                                                             \
+    if (kinds & (1u << (q))) {                                                                        \
+        _Pragma("unroll") for (int k = 0; k < E::O; ++k) {                                            \
+            const float v = x[k];                                                                     \
+            const float ph = (f);                                                                     \
+            _Pragma("unroll") for (int j = 0; j < E::A; ++j)                                          \
+                out[j] = fmaf(W[j * LIN_SLOTS + (q) * MAXO + k], ph, out[j]);                         \
+        }                                                                                             \
+    }
+        VS_LIN_KIND(LIN_ID, v)
+        VS_LIN_KIND(LIN_SIGN, v > 0.f ? 1.0f : (v < 0.f ? -1.0f : v))  // torch.sign: 0 stays 0, NaN stays NaN
+        VS_LIN_KIND(LIN_ABS, fabsf(v))
+        VS_LIN_KIND(LIN_SQ, v * v)
+        VS_LIN_KIND(LIN_CUBIC, v * v * v)
+        VS_LIN_KIND(LIN_SIG, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)))
+        VS_LIN_KIND(LIN_BELL, __builtin_amdgcn_exp2f(-0.7213475204444817f * (v * v)))  // exp(-v^2 / 2)
+        if (kinds & ((1u << LIN_SIN) | (1u << LIN_COS) | (1u << LIN_SINSIN) | (1u << LIN_SINCOS))) {
+            float sn[E::O], cs[E::O];
+#pragma unroll
+            for (int k = 0; k < E::O; ++k) sincos_fast(x[k], &sn[k], &cs[k]);  // one call per row serves the four kinds
+#define VS_LIN_TRIG(q, f)                                                                             \
+    if (kinds & (1u << (q))) {                                                                        \
+        _Pragma("unroll") for (int k = 0; k < E::O; ++k) {                                            \
+            const float ph = (f);                                                                     \
+            _Pragma("unroll") for (int j = 0; j < E::A; ++j)                                          \
+                out[j] = fmaf(W[j * LIN_SLOTS + (q) * MAXO + k], ph, out[j]);                         \
+        }                                                                                             \
+    }
+            VS_LIN_TRIG(LIN_SIN, sn[k])
+            VS_LIN_TRIG(LIN_COS, cs[k])
+            VS_LIN_TRIG(LIN_SINSIN, sn[k] * sn[k])
+            VS_LIN_TRIG(LIN_SINCOS, sn[k] * cs[k])
+#undef VS_LIN_TRIG
+        }
+#undef VS_LIN_KIND
+        if (kinds & (1u << LIN_CONST)) {
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) out[j] += W[j * LIN_SLOTS + LIN_CONST_SLOT];
+        }
+        for (int e = 0; e < P.n_x; ++e) {  // MultFeat / ATan2Feat terms (uniform)
+            const unsigned xt = P.xterm[e];
+            float v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = (int)((xt >> (3 * r)) & 7u);
+                float u = 0.f;
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) u = row == j ? ob[j] : u;  // wave-uniform selects
+                v[r] = u;
+            }
+            float ph;
+            if (xt >> 31) {
+                ph = atan2f(v[0], v[1]);
+            } else {
+                const int more = (int)((xt >> 12) & 3u);  // rows beyond the first two
+                ph = v[0] * v[1];
+                ph = more >= 1 ? ph * v[2] : ph;
+                ph = more >= 2 ? ph * v[3] : ph;
+            }
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) out[j] = fmaf(W[j * LIN_SLOTS + LIN_CONST_SLOT + 1 + e], ph, out[j]);
+        }
+        // ---- the policy's action of this lane's env (+ exploration noise)
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) a[j] = out[j];
+        if (P.noisy) {
+            // NormalActNoiseExplStrat: + std * N(0, 1), keyed like the wrapper noise by (env, episode, step)
+            uint4 b = Rng::philox(noise_seed, d.idx0 + (uint32_t)i, RNG_POLICY_NOISE, ((uint64_t)es.epi << 32) | (uint32_t)step);
+            float z[2];
+            Rng::box_muller(b.x, b.y, z[0], z[1]);
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) a[j] = fmaf(P.noise_std[j], z[j], a[j]);
+        }
+        // ---- the env step: k_rollout_fnn's, statement for statement
+        float s_pre[E::S], h_pre[E::H > 0 ? E::H : 1], a_app[E::A], ow[E::O];
+#pragma unroll
+        for (int j = 0; j < E::O; ++j) ow[j] = ob[j];
+        if (REC == 2) {
+#pragma unroll
+            for (int j = 0; j < E::S; ++j) s_pre[j] = s[j];
+#pragma unroll
+            for (int j = 0; j < E::H; ++j) h_pre[j] = h[j];
+            applied_action<E>(T, c, alo, ahi, a, a_app);
+        }
+        if (!frozen) {
+            StepOut o = step_one<E, float>(T, c, s, h, a, step, yielded,
+                                           E::TRIG > 0 ? (const float*)(ob + E::TRIG_AT) : (const float*)nullptr);
+            rew = o.rew;
+            done = o.done;
+            failed = o.failed;
+            ret += o.rew;
+            if (o.err && valid) d.err[i] = 1;
+        } else {
+            rew = 0.f;
+        }
+        if (REC) {
+            store_record<E, REC>(d.traj_rec + (rec0 + (size_t)t) * Rec<E, REC>::F * ld, ld, i, ow, a, rew, s_pre, a_app, h_pre);
+            db.put(d, i, rec0 + (size_t)t, done, t == k_steps - 1);
+        }
+        bool fin = done && valid && !frozen;
+        if (AR) {
+            auto_reset<E, UNI>(T, d, fin, i, reset_seed, c, s, h, step, ret, yielded, es);
+            E::act_bounds(c, alo, ahi);
+        } else {
+            if (fin) {
+                es.count += 1u;
+                es.retsum += ret;
+                es.lensum += step;
+            }
+            if (d.log_episodes) append_episode(d, fin, i, ret, step);
+            frozen |= done;
+        }
+        E::observe(s, ob);
+    }
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) d.state[j * ld + i] = s[j];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) d.hidden[j * ld + i] = h[j];
+#pragma unroll
+    for (int j = 0; j < E::O; ++j) d.obs[j * ld + i] = ob[j];
+    d.step[i] = step;
+    d.ret[i] = ret;
+    d.rew[i] = rew;
+    d.done[i] = done;
+    d.failed[i] = failed;
+    if (E::FINAL != FINAL_NONE) d.yielded[i] = yielded;
+    d.ep_idx[i] = es.epi;
+    d.es_count[i] = es.count;
+    d.es_retsum[i] = es.retsum;
+    d.es_lensum[i] = es.lensum;
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -2621,6 +2853,7 @@ struct vs_env {
     float* d_ring = nullptr;      // ActDelayWrapper ring (Pipe::ring)
     vs::Fnn fnn{};                // vs_set_policy_fnn: the network vs_step_policy evaluates (fnn.w == nullptr: none)
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
+    vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     int hrec_width = 0;           // vs_set_policy_hidden_record: floats per env and step of the hidden-state record plane, 0 off
     float* d_hrec = nullptr;      // ... the plane, f32 [traj_cap][hrec_width][ld]
     int rollout_variant = -1;     // vs_set_rollout_variant: -1 automatic, 0 k_rollout, 1 k_rollout_ws<256>, 2 k_rollout_ws<64>, 3 / 4 the three-role kernel in 64 / 256-env workgroups
@@ -2663,6 +2896,7 @@ struct Launch {
     // vs_step_policy (shape: fnn_shape(h) as admitted there); with a population on the handle (POP): auto-reset off, rec 1 | 2
     static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed, int shape);
     static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... recurrent policy
+    static void rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... linear policy on a feature stack
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -2890,6 +3124,19 @@ void Launch<E>::rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed) {
                 } else no_kernel("rollout_rnn");
             }, h->auto_reset, h->pop.w != nullptr);
         });
+    });
+}
+
+template <class E>
+void Launch<E>::rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed) {
+    // one wave of 64 envs per workgroup, no LDS
+    with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+        with_bools([&](auto AR, auto POP) __attribute__((always_inline)) {
+            if constexpr (!POP || (!AR && REC != 0))
+                hipLaunchKernelGGL((k_rollout_lin<E, AR, REC, POP>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d,
+                                   h->lin, k, h->ar_seed, noise_seed, POP ? h->pop : Pop{});
+            else no_kernel("rollout_lin");
+        }, h->auto_reset, h->pop.w != nullptr);
     });
 }
 

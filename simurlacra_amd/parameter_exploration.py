@@ -6,7 +6,7 @@ numbers).
 
 The reference hands every (parameter set, domain, init state) triple to a worker process.  Here the whole population is ONE
 batch of lanes of a libvecsim handle when the fused kernel evaluates the policy (FNN / FNNPolicy, RNN / GRU / LSTM policies,
-see fnn_kernel_spec / rnn_kernel_spec): vs_set_policy_population gives every aligned group of 64 lanes its own parameter
+LinearPolicy on a feature stack; see fnn_kernel_spec / rnn_kernel_spec / linear_kernel_spec): vs_set_policy_population gives every aligned group of 64 lanes its own parameter
 vector, and one vs_step_policy launch chain runs all sets at once.
 
 Lane layout (population_lane_layout): set s owns lanes s * stride .. (s + 1) * stride - 1, stride = R (rollouts per set)
@@ -201,8 +201,7 @@ class ParameterExploringSampler:
         """the condition of ParallelRolloutSampler's fused policy path"""
         if not self._fuse_policy:
             return False
-        fnn, rnn = fused_policy_specs(self.policy, fuse_wrappers(self.env), inner_env(self.env).name)
-        return fnn is not None or rnn is not None
+        return any(spec is not None for spec in fused_policy_specs(self.policy, fuse_wrappers(self.env), inner_env(self.env).name))
 
     def sample(self, param_sets, init_states: Optional[List[np.ndarray]] = None) -> ParameterSamplingResult:
         """Every parameter vector (rows of param_sets, [P, n_params]) on the same num_rollouts_per_param rollouts (eval=True)"""

@@ -1,6 +1,9 @@
 """The two trivial policies the reference's tests drive the envs with (P/policies/feed_forward/dummy.py:40-84)."""
 import torch
 
+from .features import (ATan2Feat, FeatureStack, MultFeat, abs_feat, bell_feat, const_feat, cos_feat, cubic_feat,  # noqa: F401
+                       identity_feat, sig_feat, sign_feat, sin_feat, sincos_feat, sinsin_feat, squared_feat)
+
 
 class Policy(torch.nn.Module):
     is_recurrent = False
@@ -141,6 +144,53 @@ class FNNPolicy(Policy):
         if self.featurize:
             obs = torch.cat([obs[..., 0:1], torch.sin(obs[..., 1:2]), torch.cos(obs[..., 1:2]), obs[..., 2:]], dim=-1)
         return self.net(obs)
+
+
+# ------------------------------------------------------------------------------------------- linear policy on features
+class LinearPolicy(Policy):
+    """Linear policy on a stack of feature functions (upstream Pyrado policies/feed_forward/linear.py): act = net(feats(obs))
+    with net = nn.Linear(num_feat, act_dim, bias=False), so param_values is net.weight flattened as [act_dim][num_feat], the
+    features in stack order.  The parameters keep torch's default initialisation (init_param(None)); Pyrado's init_param draws
+    are not reproduced."""
+
+    name = "lin"
+
+    def __init__(self, spec, feats: FeatureStack, init_param_kwargs=None, use_cuda=False):
+        if not isinstance(feats, FeatureStack):
+            from .exceptions import TypeErr
+
+            raise TypeErr(given=feats, expected_type=FeatureStack)
+        super().__init__(spec)
+        self._feats = feats
+        self.num_active_feat = feats.get_num_feat(spec.obs_space.flat_dim)
+        self.net = torch.nn.Linear(self.num_active_feat, spec.act_space.flat_dim, bias=False)
+        self.init_param(None, **(init_param_kwargs or {}))
+        self.to("cuda" if use_cuda and torch.cuda.is_available() else "cpu")
+
+    @property
+    def features(self) -> FeatureStack:
+        return self._feats
+
+    @property
+    def param_values(self):
+        return torch.nn.utils.parameters_to_vector(self.parameters())
+
+    @param_values.setter
+    def param_values(self, param):
+        torch.nn.utils.vector_to_parameters(param, self.parameters())
+
+    def init_param(self, init_values=None, **kwargs):
+        if init_values is None:
+            _init_linear(self.net)
+        else:
+            self.param_values = init_values
+
+    def eval_feats(self, obs: torch.Tensor) -> torch.Tensor:
+        return self._feats(obs)
+
+    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+        w = self.net.weight
+        return self.net(self.eval_feats(obs.to(device=w.device, dtype=w.dtype)))
 
 
 # ----------------------------------------------------------------------------------------------------- recurrent policies
@@ -373,3 +423,71 @@ def rnn_kernel_spec(policy):
         return None
     return dict(params=torch.nn.utils.parameters_to_vector(policy.parameters()).detach().to(torch.float32), cell=cell,
                 n_layers=m.num_layers, hidden_size=m.hidden_size, output_nonlin=output_nonlin, noise_std=noise_std)
+
+
+# feature function -> the kind name VecSimEnv.set_policy_linear takes (every elementwise function and the constant)
+_FEAT_NAMES = {identity_feat: "identity", sign_feat: "sign", abs_feat: "abs", squared_feat: "squared", cubic_feat: "cubic",
+               sig_feat: "sig", bell_feat: "bell", sin_feat: "sin", cos_feat: "cos", sinsin_feat: "sinsin",
+               sincos_feat: "sincos", const_feat: "const"}
+LIN_MAX_FEAT, LIN_MAX_XTERMS = 128, 39  # the fused kernel's caps: features in all, MultFeat / ATan2Feat terms
+
+
+def linear_kernel_spec(policy):
+    """The arguments of VecSimEnv.set_policy_linear for a LinearPolicy whose FeatureStack the fused kernel can take -- every
+    elementwise function and const_feat at most once, MultFeat of 2 .. 4 rows, ATan2Feat, at most 39 of the latter two and 128
+    features in all -- optionally inside a NormalActNoiseExplStrat, or None (the sampler then keeps the policy in torch).
+    terms: [(kind name, indices)] in stack order; the indices count the rows the policy sees."""
+    noise_std = None
+    if isinstance(policy, NormalActNoiseExplStrat):
+        noise_std = policy.std.detach().cpu().numpy()
+        policy = policy.policy
+    if not isinstance(policy, LinearPolicy):
+        return None
+    n_vis = policy.env_spec.obs_space.flat_dim
+    terms, seen, n_x = [], set(), 0
+    for f in policy.features.feat_fcns:
+        if isinstance(f, (MultFeat, ATan2Feat)):
+            idcs = tuple(f.idcs)
+            if len(idcs) > 4 or any(not 0 <= i < n_vis for i in idcs):
+                return None
+            n_x += 1
+            terms.append(("mult" if isinstance(f, MultFeat) else "atan2", idcs))
+            continue
+        try:
+            name = _FEAT_NAMES.get(f)
+        except TypeError:  # (an unhashable callable)
+            name = None
+        if name is None or name in seen:
+            return None
+        seen.add(name)
+        terms.append((name, ()))
+    if n_vis > 8 or n_x > LIN_MAX_XTERMS or not terms or policy.num_active_feat > LIN_MAX_FEAT:
+        return None
+    return dict(params=policy.net.weight.detach().to(torch.float32).reshape(-1), terms=terms, noise_std=noise_std)
+
+
+_LIN_KINDS = ("identity", "sign", "abs", "squared", "cubic", "sig", "bell", "sin", "cos", "sinsin", "sincos", "const", "mult",
+              "atan2")  # the library's kind codes (VS_FEAT_*), in order
+
+
+def linear_slot_map(terms, n_vis, act_dim):
+    """The index map of the library's packer for a linear policy, restated: entry [j * 128 + slot] = the index into the flat
+    torch parameter vector ([act_dim][num_feat]) of the weight the fused kernel reads in that slot of action row j, -1 where
+    the stack has no feature.  Slot order of a row, whatever the stack's order: elementwise kind q (the order of the
+    VS_FEAT_* codes) of visible row k at 8 q + k, the constant at 88, the i-th MultFeat / ATan2Feat term at 89 + i."""
+    slots, n_x = [], 0
+    for name, _ in terms:
+        q = _LIN_KINDS.index(name)
+        if q < 11:
+            slots += [8 * q + k for k in range(n_vis)]
+        elif q == 11:
+            slots.append(88)
+        else:
+            slots.append(89 + n_x)
+            n_x += 1
+    num_feat = len(slots)
+    out = [-1] * (act_dim * 128)
+    for j in range(act_dim):
+        for f, sl in enumerate(slots):
+            out[j * 128 + sl] = j * num_feat + f
+    return out

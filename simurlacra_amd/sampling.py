@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from .exceptions import TypeErr, ValueErr
-from .policies import DummyPolicy, fnn_kernel_spec, rnn_kernel_spec
+from .policies import DummyPolicy, fnn_kernel_spec, linear_kernel_spec, rnn_kernel_spec
 from .seeding import derive_seed, get_base_seed, set_seed
 from .wrappers import DomainRandWrapperBuffer, DomainRandWrapperLive, fuse_wrappers, inner_env, typed_env
 
@@ -364,18 +364,20 @@ def rollout(env, policy, eval: bool = False, max_steps: Optional[int] = None, re
 
 
 def fused_policy_specs(policy, fc, env_name):
-    """(fnn, rnn): the arguments of VecSimEnv.set_policy_fnn / set_policy_rnn when the fused kernel evaluates `policy` itself
-    (at most one of them), or (None, None).
+    """(fnn, rnn, lin): the arguments of VecSimEnv.set_policy_fnn / set_policy_rnn / set_policy_linear when the fused kernel
+    evaluates `policy` itself (at most one of them), or (None, None, None).
     A feed-forward network policy the kernel can evaluate itself (vs_step_policy): rollout() with act = policy(obs) fused like
     the DummyPolicy path -- unless a wrapper pipeline (noise / delay / observation normalisation, FusedChain `fc`) is on.
     A recurrent policy likewise (vs_set_policy_rnn): the hidden state kept on the device from step to step and recorded
-    before every step.  Not for the discrete-action family."""
+    before every step.  A LinearPolicy on a feature stack the kernel takes likewise (vs_set_policy_linear).  Not for the
+    discrete-action family."""
     plain_chain = (fc.delay == 0 and not np.any(fc.noise_std) and not np.any(fc.noise_mean) and not np.any(fc.var)
                    and np.all(fc.scale == 1) and not np.any(fc.shift))
     if not plain_chain or env_name == "bob-d":
-        return None, None
+        return None, None, None
     fnn = fnn_kernel_spec(policy)
-    return fnn, (rnn_kernel_spec(policy) if fnn is None else None)
+    rnn = rnn_kernel_spec(policy) if fnn is None else None
+    return fnn, rnn, (linear_kernel_spec(policy) if fnn is None and rnn is None else None)
 
 
 class ParallelRolloutSampler:
@@ -582,10 +584,12 @@ class ParallelRolloutSampler:
         hid_t = v.tensor(L.VS_HIDDEN)[:, :n] if H else None
         use_fused = isinstance(self.policy, DummyPolicy)
         fc = self._fc
-        fnn, rnn = fused_policy_specs(self.policy, fc, base.name) if (self._fuse_policy and not use_fused) else (None, None)
+        fnn, rnn, lin = (fused_policy_specs(self.policy, fc, base.name) if (self._fuse_policy and not use_fused)
+                         else (None, None, None))
         recurrent = bool(getattr(self.policy, "is_recurrent", False)) and not use_fused
-        if population is not None and fnn is None and rnn is None:
-            raise ValueErr(msg="a policy population needs a policy the fused kernel evaluates (fnn_kernel_spec / rnn_kernel_spec)")
+        if population is not None and fnn is None and rnn is None and lin is None:
+            raise ValueErr(msg="a policy population needs a policy the fused kernel evaluates (fnn_kernel_spec / rnn_kernel_spec / "
+                               "linear_kernel_spec)")
         # the lanes whose done flags end the launch loop: all of them, or a population's real lanes (inert lanes never step)
         real_t = None if population is None else torch.as_tensor(np.asarray(population["real"], dtype=np.int64), device=dev)
 
@@ -651,6 +655,24 @@ class ParallelRolloutSampler:
             v.set_record_mode(2 if full else 1)
             v.set_traj_capacity(T_cap)
             v.set_policy_hidden_record(W)
+            while t < T_cap:
+                k = int(min(self._chunk, T_cap - t))
+                v.set_traj_offset(t)
+                v.step_policy(k, record=True, noise_seed=lane_key ^ 0x8CB92BA72F3D8DD7)
+                t += k
+                if all_done():  # one scalar sync per launch
+                    break
+            v.set_traj_offset(0)
+        elif lin is not None:
+            # rollout() with a linear policy on a feature stack == vs_step_policy with vs_set_policy_linear: observation ->
+            # features -> W phi -> (exploration noise) -> step -> record inside ONE kernel, as for the network above
+            if hasattr(self.policy, "reset"):
+                self.policy.reset()
+            v.set_policy_linear(obs_idx=None if fc.keep.all() else np.flatnonzero(fc.keep), **lin)
+            if population is not None:
+                v.set_policy_population(population["params"], population["lane_set"])
+            v.set_record_mode(2 if full else 1)
+            v.set_traj_capacity(T_cap)
             while t < T_cap:
                 k = int(min(self._chunk, T_cap - t))
                 v.set_traj_offset(t)

@@ -608,9 +608,55 @@ class VecSimEnv:
                     "vs_set_policy_rnn")
         self._rnn_hs = d.n_layers * d.hidden * (2 if d.cell == L.VS_RNN_LSTM else 1)
 
+    _LIN_KINDS = {"identity": L.VS_FEAT_IDENTITY, "sign": L.VS_FEAT_SIGN, "abs": L.VS_FEAT_ABS, "squared": L.VS_FEAT_SQUARED,
+                  "cubic": L.VS_FEAT_CUBIC, "sig": L.VS_FEAT_SIG, "bell": L.VS_FEAT_BELL, "sin": L.VS_FEAT_SIN, "cos": L.VS_FEAT_COS,
+                  "sinsin": L.VS_FEAT_SINSIN, "sincos": L.VS_FEAT_SINCOS, "const": L.VS_FEAT_CONST, "mult": L.VS_FEAT_MULT,
+                  "atan2": L.VS_FEAT_ATAN2}
+
+    def set_policy_linear(self, params, terms, obs_idx=None, noise_std=None):
+        """Hand a linear policy on a feature stack (LinearPolicy / FeatureStack, upstream Pyrado policies/feed_forward/linear.py
+        and policies/features.py) to the fused kernel of step_policy.  params: net.weight flattened, [act_dim][num_feat] in stack
+        order, a torch tensor or array; terms: the stack in order, each a kind name ('identity' | 'sign' | 'abs' | 'squared' |
+        'cubic' | 'sig' | 'bell' | 'sin' | 'cos' | 'sinsin' | 'sincos' | 'const') or a pair (name, indices) -- ('mult', (i, j, ..))
+        for MultFeat, ('atan2', (i_sin, i_cos)) for ATan2Feat, the indices counting the rows the policy sees; obs_idx / noise_std
+        as in set_policy_fnn.  params=None removes the policy."""
+        self._rnn_hs = 0  # (a linear policy replaces a recurrent one)
+        if params is None:
+            self._check(self._lib.vs_set_policy_linear(self._h, None, None, 0), "vs_set_policy_linear")
+            return
+        terms = [(t, ()) if isinstance(t, str) else (t[0], tuple(t[1])) for t in terms]
+        if not 1 <= len(terms) <= L.VS_LIN_MAX_TERMS:
+            raise ValueErr(msg=f"the in-kernel linear policy takes 1..{L.VS_LIN_MAX_TERMS} terms, got {len(terms)}")
+        d = L.LinDesc()
+        d.n_terms = len(terms)
+        for k, (name, idcs) in enumerate(terms):
+            if name not in self._LIN_KINDS:
+                raise ValueErr(msg=f"unknown feature kind {name!r}")
+            if len(idcs) > 4:
+                raise ValueErr(msg="a MultFeat of at most 4 rows")
+            d.terms[k].kind = self._LIN_KINDS[name]
+            d.terms[k].n_idx = len(idcs)
+            for r, x in enumerate(idcs):
+                d.terms[k].idx[r] = int(x)
+        if obs_idx is not None:
+            idx = [int(x) for x in obs_idx]
+            if len(idx) > 8:
+                raise ValueErr(msg="at most 8 visible observation rows")
+            d.n_obs = len(idx)
+            for k, x in enumerate(idx):
+                d.obs_idx[k] = x
+        if noise_std is not None:
+            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))[:2]):
+                d.noise_std[k] = float(x)
+        if hasattr(params, "detach"):
+            params = params.detach().to("cpu").numpy()
+        flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+        self._check(self._lib.vs_set_policy_linear(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
+                    "vs_set_policy_linear")
+
     def set_policy_population(self, params, lane_set=None):
         """A population of parameter vectors for step_policy (vs_set_policy_population): params [P, n_params] -- P vectors of the
-        policy of the last set_policy_fnn / set_policy_rnn, each in that call's torch order; a torch tensor (host or device) or
+        policy of the last set_policy_fnn / set_policy_rnn / set_policy_linear, each in that call's torch order; a torch tensor (host or device) or
         an array -- and lane_set [n_envs] the set every lane runs (-1: the lane takes no part; every aligned group of 64 lanes
         names one set).  params=None removes the population."""
         if params is None:
