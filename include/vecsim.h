@@ -95,7 +95,9 @@ enum vs_buffer {
                                 * zeroed by vs_set_policy_rnn, by vs_reset (the reset lanes) and per lane at every auto-reset */
     VS_POLICY_HIDDEN_REC = 26, /* f32 [T][W][ld] hidden-state record plane (vs_set_policy_hidden_record, W floats per env): row t =
                                 * the policy's hidden state BEFORE recorded step t; same rows as VS_TRAJ_REC (capacity, offset) */
-    VS_BUFFER_COUNT = 27
+    VS_ROLLOUT_LOSS = 27,      /* f32 [ld]  per-lane discrepancy sum of vs_set_rollout_target (NULL / nothing copied without a target):
+                                * zeroed by vs_set_rollout_target and by vs_reset (the reset lanes), accumulated by vs_step_policy */
+    VS_BUFFER_COUNT = 28
 };
 
 /* vs_task_cfg.flags */
@@ -369,6 +371,38 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
  * MultFeat of fewer than 2 or more than 4 rows, more than VS_LIN_MAX_XTERMS / VS_LIN_MAX_FEAT terms / features, a negative or NaN
  * noise_std, n_params != A * F (VS_ERR_ARG). */
 int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* params, int64_t n_params);
+/* vs_step_policy with an open-loop policy that replays recorded actions: PlaybackPolicy (one recording per rollout) and, as a
+ * tabulated function of time, TimePolicy of upstream Pyrado policies/feed_forward/playback.py and time.py.
+ * `actions` is [n_rec][t_len][A] row-major, host or device memory, copied and re-laid on the device ([t_len][A][n_rec rounded up
+ * to 64]); rec_len[n_rec] (host; NULL: every recording has t_len steps) the number of steps of each recording, 0 .. t_len;
+ * lane_rec[n_envs] (host) the recording each lane replays, NULL: lane i replays (first_global_index + i) % n_rec
+ * (vs_set_index_offset).  The action of a step of a lane with recording r, k = the env's curr_step BEFORE the step:
+ *     act[j] = k < rec_len[r] ? actions[r][k][j] : 0
+ * -- k is the env's own counter, so cutting a rollout into several launches does not show, and an auto-reset restarts the
+ * recording with the episode.  The raw table value is what a record holds as the action; VS_FLAG_ACT_NORM, the clip and the dead
+ * zone apply to it inside the step as for every other policy, NaN sets VS_ERRFLAG.  A lane frozen at done reads nothing (its
+ * recorded action is 0).  noise_seed of vs_step_policy is ignored.  Records, auto-reset, freeze-at-done as for vs_set_policy_fnn.
+ * actions == NULL removes the policy.  Setting a playback policy removes a policy of vs_set_policy_fnn / vs_set_policy_rnn /
+ * vs_set_policy_linear, any population and any rollout target, and the other way round; vs_set_policy_population on a playback
+ * policy returns VS_ERR_STATE.
+ * Refused with the previous policy (population, target) left in place: a wrapper pipeline on the handle (VS_ERR_STATE); the
+ * discrete-action family, n_rec < 1, t_len < 1, a rec_len outside [0, t_len], a lane_rec outside [0, n_rec), a table of more
+ * than 2^31 floats (VS_ERR_ARG). */
+int vs_set_policy_playback(vs_handle h, const float* actions, int n_rec, int t_len, const int32_t* rec_len, const int32_t* lane_rec);
+/* The on-device trajectory discrepancy of a playback rollout (the inner loop of system identification: simulate a recorded
+ * segment under candidate domain parameters, compare with the recorded observations) -- replaces recording, packing and
+ * copying every step to evaluate  sum_k sum_d w_d (obs_sim[k][d] - obs_rec[k][d])^2  on the host.
+ * target_obs is [n_rec][t_len + 1][O] row-major (host or device, copied and re-laid), row k = the recorded observation after k
+ * steps (row 0, the initial observation, is not compared); weights[O] (host), NULL: all 1.  Setting a target allocates
+ * VS_ROLLOUT_LOSS and zeroes it; vs_reset zeroes it for the lanes it resets.  vs_step_policy then, after every step a
+ * non-frozen lane with recording r takes, k' = its new curr_step, if k' <= rec_len[r]:  for d = 0 .. O - 1, in that order, in fp32
+ *     e = obs'[d] - target_obs[r][k'][d];   VS_ROLLOUT_LOSS[lane] = fmaf(weights[d] * e, e, VS_ROLLOUT_LOSS[lane])
+ * (obs' the observation of the new state).  The number of steps in a lane's sum is min(VS_STEPCOUNT, rec_len[r]).  With
+ * record == 0 such a launch writes nothing per step.
+ * target_obs == NULL removes the target; replacing or removing the playback policy removes it too.
+ * Refused: no playback policy on the handle (VS_ERR_STATE); n_rec / t_len different from the playback policy's, a negative or
+ * NaN weight (VS_ERR_ARG).  With a target and auto-reset on, vs_step_policy returns VS_ERR_STATE. */
+int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t_len, const float* weights);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

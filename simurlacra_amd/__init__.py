@@ -38,10 +38,14 @@ def __getattr__(name):
         return getattr(parameter_exploration, name)
     if name in ("DummyPolicy", "IdlePolicy", "Policy", "FNN", "FNNPolicy", "NormalActNoiseExplStrat", "fnn_kernel_spec",
                 "RecurrentPolicy", "RNNPolicy", "GRUPolicy", "LSTMPolicy", "rnn_kernel_spec", "LinearPolicy",
-                "linear_kernel_spec"):
+                "linear_kernel_spec", "PlaybackPolicy", "TimePolicy", "playback_kernel_spec"):
         from . import policies
 
         return getattr(policies, name)
+    if name in ("TrajectoryMatchSampler", "TrajectoryMatchResult"):
+        from . import sysid
+
+        return getattr(sysid, name)
     if name in ("FeatureStack", "MultFeat", "ATan2Feat", "const_feat", "identity_feat", "sign_feat", "abs_feat", "squared_feat",
                 "cubic_feat", "sig_feat", "bell_feat", "sin_feat", "cos_feat", "sinsin_feat", "sincos_feat"):
         from . import features

@@ -23,6 +23,24 @@ __global__ __launch_bounds__(256) void k_zero_hidden(float* __restrict__ hid, in
     for (int j = 0; j < rows; ++j) hid[(size_t)j * ld + i] = 0.f;
 }
 
+// vs_reset with a mask: the discrepancy sums (VS_ROLLOUT_LOSS) of the reset lanes
+__global__ __launch_bounds__(256) void k_zero_masked(float* __restrict__ p, const uint8_t* __restrict__ mask, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !mask[i]) return;
+    p[i] = 0.f;
+}
+
+// vs_set_policy_playback / vs_set_rollout_target: the caller's table src [n_rec][rw] (rw = rows x width floats per recording)
+// into the kernel's recording-minor layout dst [rw][n_rec_ld], 0 in the padding columns n_rec .. n_rec_ld - 1
+__global__ __launch_bounds__(256) void k_relay_table(const float* __restrict__ src, int n_rec, int64_t rw, float* __restrict__ dst,
+                                                     int n_rec_ld) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= rw * n_rec_ld) return;
+    const int64_t m = q / n_rec_ld;
+    const int r = (int)(q % n_rec_ld);
+    dst[q] = r < n_rec ? src[(int64_t)r * rw + m] : 0.f;
+}
+
 // vs_rollout_lengths: per lane, the first recorded step whose done bit is set (words [t / 32][ld], bit t % 32); a lane of a
 // population's inert group (wg_set[i / 64] < 0) has no rollout: 0
 __global__ __launch_bounds__(256) void k_rollout_lengths(const uint32_t* __restrict__ words, size_t ld, int n, int t_steps,
@@ -475,7 +493,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 extern "C" {
 
-int vs_version(void) { return 307; }
+int vs_version(void) { return 308; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -622,6 +640,11 @@ int vs_destroy(vs_handle h) {
     if (h->fnn.w) (void)hipFree((void*)h->fnn.w);
     if (h->rnn.w) (void)hipFree((void*)h->rnn.w);
     if (h->lin.w) (void)hipFree((void*)h->lin.w);
+    if (h->play.act) (void)hipFree((void*)h->play.act);
+    if (h->play.tgt) (void)hipFree((void*)h->play.tgt);
+    if (h->play.rec_len) (void)hipFree((void*)h->play.rec_len);
+    if (h->play.lane_rec) (void)hipFree((void*)h->play.lane_rec);
+    if (h->play.loss) (void)hipFree(h->play.loss);
     if (h->rnn.hid) (void)hipFree(h->rnn.hid);
     if (h->pop.w) (void)hipFree((void*)h->pop.w);
     if (h->pop.wg_set) (void)hipFree((void*)h->pop.wg_set);
@@ -817,6 +840,10 @@ int vs_reset(vs_handle h, const float* init_state, int64_t pitch, int full, cons
     if (h->rnn.hid) {  // a new rollout starts from init_hidden()
         if (!m) HIPCHK(h, hipMemsetAsync(h->rnn.hid, 0, (size_t)h->rnn.hs * h->d.ld * sizeof(float), h->stream));
         else hipLaunchKernelGGL(k_zero_hidden, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, h->rnn.hid, h->rnn.hs, (size_t)h->d.ld, m, h->d.n);
+    }
+    if (h->play.loss) {  // a new rollout starts its discrepancy sum at 0
+        if (!m) HIPCHK(h, hipMemsetAsync(h->play.loss, 0, (size_t)h->d.ld * sizeof(float), h->stream));
+        else hipLaunchKernelGGL(k_zero_masked, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, h->play.loss, m, h->d.n);
     }
     HIPCHK(h, hipGetLastError());
     return VS_OK;
@@ -1045,6 +1072,25 @@ static int drop_lin(vs_handle h) {
     return VS_OK;
 }
 
+static int drop_target(vs_handle h) {
+    if (h->play.tgt) HIPCHK(h, hipFree((void*)h->play.tgt));
+    h->play.tgt = nullptr;
+    if (h->play.loss) HIPCHK(h, hipFree(h->play.loss));
+    h->play.loss = nullptr;
+    return VS_OK;
+}
+
+static int drop_play(vs_handle h) {  // the playback policy and the target that belongs to it
+    if (int rc = drop_target(h)) return rc;
+    if (h->play.act) HIPCHK(h, hipFree((void*)h->play.act));
+    h->play.act = nullptr;
+    if (h->play.rec_len) HIPCHK(h, hipFree((void*)h->play.rec_len));
+    h->play.rec_len = nullptr;
+    if (h->play.lane_rec) HIPCHK(h, hipFree((void*)h->play.lane_rec));
+    h->play = Play{};
+    return VS_OK;
+}
+
 // the packed vector of one policy from its index map (packed slot -> source index, -1: zero padding)
 static std::vector<float> pack_by_map(const std::vector<int>& map, const std::vector<float>& src) {
     std::vector<float> pk(map.size(), 0.f);
@@ -1061,6 +1107,7 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     h->fnn = Fnn{};
     if (int rc = drop_rnn(h)) return rc;  // one in-kernel policy at a time
     if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_play(h)) return rc;
     if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
     h->pol_map.clear();
     h->pol_n_params = 0;
@@ -1146,6 +1193,7 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
     h->fnn = Fnn{};
     if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_play(h)) return rc;
     if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
     h->pol_map.clear();
     h->pol_n_params = 0;
@@ -1297,6 +1345,7 @@ int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* para
     h->fnn = Fnn{};
     if (int rc = drop_rnn(h)) return rc;
     if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_play(h)) return rc;
     if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
     h->pol_map.clear();
     h->pol_n_params = 0;
@@ -1305,6 +1354,123 @@ int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* para
     h->lin = f;
     h->pol_map = std::move(map);
     h->pol_n_params = need;
+    return VS_OK;
+}
+
+// the caller's table (host or device) in the kernel's layout: a new device buffer [rw][n_rec rounded up to 64]
+static int relay_table(vs_handle h, const char* who, const float* src, int n_rec, int64_t rw, float** out) {
+    const int nrl = (n_rec + 63) / 64 * 64;
+    const int64_t total = rw * nrl;
+    float *tmp = nullptr, *dst = nullptr;
+    hipError_t e = hipSuccess;
+    if (!is_device_ptr(src)) {
+        const size_t bytes = (size_t)n_rec * (size_t)rw * sizeof(float);
+        e = hipMalloc((void**)&tmp, bytes);
+        if (e == hipSuccess) e = hipMemcpy(tmp, src, bytes, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&dst, (size_t)total * sizeof(float));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_relay_table, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, tmp ? tmp : src, n_rec, rw, dst, nrl);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (the staging copy goes, and the caller's table may change)
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) {
+        if (dst) (void)hipFree(dst);
+        return fail(h, VS_ERR_HIP, who, e);
+    }
+    *out = dst;
+    return VS_OK;
+}
+
+int vs_set_policy_playback(vs_handle h, const float* actions, int n_rec, int t_len, const int32_t* rec_len, const int32_t* lane_rec) {
+    if (!h) return VS_ERR_ARG;
+    const EnvInfo& ei = ENV_INFO[h->type];
+    int nrl = 0;
+    if (actions) {  // every check before anything is dropped: a refused call leaves the previous policy (and target) in place
+        if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_playback: the discrete-action family takes no in-kernel policy");
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_policy_playback: not available with a wrapper pipeline on the handle");
+        if (n_rec < 1 || t_len < 1) return fail(h, VS_ERR_ARG, "vs_set_policy_playback: n_rec >= 1 and t_len >= 1");
+        nrl = (n_rec + 63) / 64 * 64;
+        if (((int64_t)t_len + 1) * MAXO * nrl > (int64_t)INT_MAX) return fail(h, VS_ERR_ARG, "vs_set_policy_playback: the table is too large (2^31 floats)");
+        if (rec_len)
+            for (int r = 0; r < n_rec; ++r)
+                if (rec_len[r] < 0 || rec_len[r] > t_len) return fail(h, VS_ERR_ARG, "vs_set_policy_playback: rec_len outside [0, t_len]");
+        if (lane_rec)
+            for (int i = 0; i < h->d.n; ++i)
+                if (lane_rec[i] < 0 || lane_rec[i] >= n_rec) return fail(h, VS_ERR_ARG, "vs_set_policy_playback: lane_rec outside [0, n_rec)");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still read the tables this replaces)
+    Play p{};
+    if (actions) {
+        float* da = nullptr;
+        int *dl = nullptr, *dm = nullptr;
+        if (int rc = relay_table(h, "vs_set_policy_playback: table upload", actions, n_rec, (int64_t)t_len * ei.A, &da)) return rc;
+        std::vector<int> lens((size_t)nrl, 0);
+        for (int r = 0; r < n_rec; ++r) lens[r] = rec_len ? rec_len[r] : t_len;
+        hipError_t e = hipMalloc((void**)&dl, (size_t)nrl * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(dl, lens.data(), (size_t)nrl * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess && lane_rec) {
+            std::vector<int> map((size_t)h->d.ld, 0);  // (lanes beyond n_envs replay recording 0: every read stays in the table)
+            for (int i = 0; i < h->d.n; ++i) map[i] = lane_rec[i];
+            e = hipMalloc((void**)&dm, map.size() * sizeof(int));
+            if (e == hipSuccess) e = hipMemcpy(dm, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(da);
+            if (dl) (void)hipFree(dl);
+            if (dm) (void)hipFree(dm);
+            return fail(h, VS_ERR_HIP, "vs_set_policy_playback: upload", e);
+        }
+        p.act = da;
+        p.rec_len = dl;
+        p.lane_rec = dm;
+        p.n_rec = n_rec;
+        p.n_rec_ld = nrl;
+        p.t_len = t_len;
+    }
+    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
+    h->fnn = Fnn{};
+    if (int rc = drop_rnn(h)) return rc;
+    if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_play(h)) return rc;  // (with its target)
+    if (int rc = drop_pop(h)) return rc;
+    h->pol_map.clear();
+    h->pol_n_params = 0;
+    h->play = p;
+    return VS_OK;
+}
+
+int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t_len, const float* weights) {
+    if (!h) return VS_ERR_ARG;
+    const EnvInfo& ei = ENV_INFO[h->type];
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!target_obs) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return drop_target(h);
+    }
+    if (!h->play.act) return fail(h, VS_ERR_STATE, "vs_set_rollout_target: no playback policy set (vs_set_policy_playback)");
+    if (n_rec != h->play.n_rec || t_len != h->play.t_len) return fail(h, VS_ERR_ARG, "vs_set_rollout_target: n_rec and t_len must equal the playback policy's");
+    float w[MAXO];
+    for (int q = 0; q < MAXO; ++q) {
+        w[q] = q < ei.O ? (weights ? weights[q] : 1.f) : 0.f;
+        if (!(w[q] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_rollout_target: weights must be >= 0");
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still read the target this replaces)
+    float *dt = nullptr, *dl = nullptr;
+    if (int rc = relay_table(h, "vs_set_rollout_target: table upload", target_obs, n_rec, (int64_t)(t_len + 1) * ei.O, &dt)) return rc;
+    hipError_t e = hipMalloc((void**)&dl, (size_t)h->d.ld * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(dl, 0, (size_t)h->d.ld * sizeof(float), h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(dt);
+        if (dl) (void)hipFree(dl);
+        return fail(h, VS_ERR_HIP, "vs_set_rollout_target: allocation", e);
+    }
+    if (int rc = drop_target(h)) { (void)hipFree(dt); (void)hipFree(dl); return rc; }
+    h->play.tgt = dt;
+    h->play.loss = dl;
+    for (int q = 0; q < MAXO; ++q) h->play.w[q] = w[q];
     return VS_OK;
 }
 
@@ -1338,6 +1504,7 @@ int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params,
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still read the sets this replaces)
     if (!params) return drop_pop(h);
+    if (h->play.act) return fail(h, VS_ERR_STATE, "vs_set_policy_population: a playback policy has no parameters to vary");
     if (!h->fnn.w && !h->rnn.w && !h->lin.w) return fail(h, VS_ERR_STATE, "vs_set_policy_population: no policy set (vs_set_policy_fnn / vs_set_policy_rnn / vs_set_policy_linear)");
     if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, "vs_set_policy_population: parameter count does not match the policy's");
     if (n_sets < 1 || !lane_set) return fail(h, VS_ERR_ARG, "vs_set_policy_population: n_sets >= 1 and a lane table");
@@ -1404,6 +1571,15 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
             return fail(h, VS_ERR_STATE, h->pop_inert ? "vs_step_policy: auto-reset with -1 lanes in the population table"
                                                       : "vs_step_policy: a population runs with auto-reset off");
         if (!record) return fail(h, VS_ERR_STATE, "vs_step_policy: a population runs with records on");
+    }
+    if (h->play.act) {
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
+        if (h->play.tgt && h->auto_reset) return fail(h, VS_ERR_STATE, "vs_step_policy: a rollout target runs with auto-reset off");
+        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
+        HIPCHK(h, hipSetDevice(h->device));
+        DISPATCH_ENV(h->type, Launch<E>::rollout_play(h, k_steps, record ? h->record_mode : 0));
+        HIPCHK(h, hipGetLastError());
+        return VS_OK;
     }
     if (h->rnn.w) {
         if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
@@ -1615,6 +1791,7 @@ static bool buf_info(vs_handle h, int which, void** p, size_t* bytes) {
         case VS_JAC_REW: *p = d.jac_r; *bytes = d.jac_r ? (size_t)(ei.S + ei.A) * ld * 4 : 0; return true;
         case VS_JAC_OBS: *p = d.jac_o; *bytes = d.jac_o ? (size_t)ei.O * (ei.S + ei.A) * ld * 4 : 0; return true;
         case VS_POLICY_HIDDEN: *p = h->rnn.hid; *bytes = h->rnn.hid ? (size_t)h->rnn.hs * ld * 4 : 0; return true;
+        case VS_ROLLOUT_LOSS: *p = h->play.loss; *bytes = h->play.loss ? ld * 4 : 0; return true;
         case VS_POLICY_HIDDEN_REC: *p = h->d_hrec; *bytes = h->d_hrec ? (size_t)h->traj_cap * h->hrec_width * ld * 4 : 0; return true;
 #ifdef VS_WS_STAMP
         case 99: *p = d.dbg; *bytes = (size_t)(ld / 64) * 12 * 8; return true;

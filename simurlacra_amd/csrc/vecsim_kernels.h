@@ -1872,6 +1872,166 @@ __global__ __launch_bounds__(64) void k_rollout_lin(Task T, Dev d, Lin P, int k_
     d.es_lensum[i] = es.lensum;
 }
 
+// ------------------------------------------------------------------------------- open-loop playback of recorded actions
+// vs_step_policy with a playback policy (vs_set_policy_playback): PlaybackPolicy / TimePolicy of upstream Pyrado
+// policies/feed_forward/playback.py and time.py -- the action of a step is a table row, not a function of the observation --
+// and, under TGT, the discrepancy between the simulated and a recorded observation sequence (vs_set_rollout_target), which is
+// what the system-identification loops want of such a rollout: one float per lane instead of a record stream.
+// Shape of k_rollout_lin: one env per lane, one wave of 64 envs per workgroup, no LDS, no barrier.
+//   * Lane i replays recording r: Play::lane_rec[i] when the handle has a map, else (idx0 + i) % n_rec; r and rec_len[r] are
+//     read once in the prologue.
+//   * The tables are recording-minor, act [t_len][A][n_rec_ld] and tgt [t_len + 1][O][n_rec_ld] (n_rec_ld = n_rec rounded up to
+//     64, zero-filled): lanes with consecutive recordings read consecutive floats.  The row is the env's own step counter k --
+//     not the launch's loop index, so launch cuts do not show and an auto-reset restarts the recording with the episode --
+//     clamped into the table BEFORE the address is formed; past rec_len[r] the action is 0 by a select.  A frozen lane loads
+//     nothing (its recorded action is 0).
+//   * The raw table value is what the record holds as `act`; ActNormWrapper's map, the clip and the dead zone act on it inside
+//     step_one, NaN sets the sticky error flag there.
+//   * TGT (AR == false only): acc is loaded from Play::loss and stored back at the end.  After every step a non-frozen lane
+//     takes, with k' the new step counter and k' <= rec_len[r]:  for d = 0 .. O - 1 in that order
+//         e = obs'[d] - tgt[k'][d][r],  acc = fmaf(w[d] * e, e, acc)          (obs' = E::observe of the new state)
+//     With REC == 0 the kernel then stores nothing per step.
+//   * The env step behind the action is k_rollout_fnn's, statement for statement (same records, auto-reset, freeze-at-done).
+struct Play {
+    const float* act;     // device [t_len][A][n_rec_ld]; nullptr: no playback policy on the handle
+    const float* tgt;     // device [t_len + 1][O][n_rec_ld]; nullptr: no target
+    const int* rec_len;   // device [n_rec_ld]: steps of every recording, 0 .. t_len (0 in the padding)
+    const int* lane_rec;  // device [ld]: recording of every lane (0 beyond n); nullptr: (idx0 + lane) % n_rec
+    float* loss;          // VS_ROLLOUT_LOSS, f32 [ld]; allocated with the target
+    int n_rec, n_rec_ld, t_len;
+    float w[MAXO];        // weights of the discrepancy, wave-uniform (scalar operands)
+};
+
+template <class E, bool AR, int REC, bool TGT>
+__global__ __launch_bounds__(64) void k_rollout_play(Task T, Dev d, Play P, int k_steps, uint64_t reset_seed) {
+    static_assert(!(AR && TGT), "the discrepancy belongs to one episode per lane");
+    constexpr bool UNI = false;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const size_t rec0 = (size_t)d.traj_t0;
+    const bool valid = i < d.n;
+    const size_t nrl = (size_t)P.n_rec_ld;
+
+    // ---- env state of the lane (k_rollout_fnn's)
+    float c[E::K], s[E::S], h[E::H > 0 ? E::H : 1], a[E::A], ob[E::O];
+    float alo[E::A], ahi[E::A];
+    int step = 0;
+    float ret = 0.f, rew = 0.f;
+    bool yielded = false, frozen = false, done = false, failed = false;
+    EpStat es{0u, 0u, 0.f, 0};
+    DoneBits db;
+    db.w = 0u;
+    load_consts<E, UNI>(d, i, c, 0, E::KS);
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) s[j] = d.state[j * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) h[j] = d.hidden[j * ld + i];
+    step = d.step[i];
+    ret = d.ret[i];
+    yielded = E::FINAL != FINAL_NONE ? d.yielded[i] != 0 : false;
+    frozen = !AR && d.done[i] != 0;
+    rew = d.rew[i];
+    done = d.done[i] != 0, failed = d.failed[i] != 0;
+    es = EpStat{d.ep_idx[i], d.es_count[i], d.es_retsum[i], d.es_lensum[i]};
+    // ---- the lane's recording (both reads stay inside their arrays: lane_rec has ld entries, r < n_rec <= n_rec_ld)
+    const unsigned r = P.lane_rec ? (unsigned)P.lane_rec[i] : (unsigned)(((uint64_t)d.idx0 + (uint64_t)i) % (uint64_t)P.n_rec);
+    const unsigned rl = (unsigned)P.rec_len[r];
+    const float* const act_r = P.act + r;
+    const float* const tgt_r = TGT ? P.tgt + r : nullptr;
+    float acc = 0.f;
+    if (TGT) acc = P.loss[i];
+    E::act_bounds(c, alo, ahi);
+    E::observe(s, ob);
+    if (REC) db.begin(d, i, rec0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (see rollout_body: nothing pending at the loop header)
+
+    for (int t = 0; t < k_steps; ++t) {
+        // ---- the action of this lane's env: row `step` of its recording, 0 from rec_len on
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) a[j] = 0.f;
+        if (!frozen) {
+            const unsigned k = (unsigned)step;  // (a negative counter clamps to the last row like a large one)
+            const size_t row = (size_t)min(k, (unsigned)(P.t_len - 1));
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) {
+                const float v = act_r[(row * E::A + j) * nrl];
+                a[j] = k < rl ? v : 0.f;
+            }
+        }
+        // ---- the env step: k_rollout_fnn's, statement for statement
+        float s_pre[E::S], h_pre[E::H > 0 ? E::H : 1], a_app[E::A], ow[E::O];
+#pragma unroll
+        for (int j = 0; j < E::O; ++j) ow[j] = ob[j];
+        if (REC == 2) {
+#pragma unroll
+            for (int j = 0; j < E::S; ++j) s_pre[j] = s[j];
+#pragma unroll
+            for (int j = 0; j < E::H; ++j) h_pre[j] = h[j];
+            applied_action<E>(T, c, alo, ahi, a, a_app);
+        }
+        const bool stepped = !frozen;
+        if (!frozen) {
+            StepOut o = step_one<E, float>(T, c, s, h, a, step, yielded,
+                                           E::TRIG > 0 ? (const float*)(ob + E::TRIG_AT) : (const float*)nullptr);
+            rew = o.rew;
+            done = o.done;
+            failed = o.failed;
+            ret += o.rew;
+            if (o.err && valid) d.err[i] = 1;
+        } else {
+            rew = 0.f;
+        }
+        if (REC) {
+            store_record<E, REC>(d.traj_rec + (rec0 + (size_t)t) * Rec<E, REC>::F * ld, ld, i, ow, a, rew, s_pre, a_app, h_pre);
+            db.put(d, i, rec0 + (size_t)t, done, t == k_steps - 1);
+        }
+        bool fin = done && valid && !frozen;
+        if (AR) {
+            auto_reset<E, UNI>(T, d, fin, i, reset_seed, c, s, h, step, ret, yielded, es);
+            E::act_bounds(c, alo, ahi);
+        } else {
+            if (fin) {
+                es.count += 1u;
+                es.retsum += ret;
+                es.lensum += step;
+            }
+            if (d.log_episodes) append_episode(d, fin, i, ret, step);
+            frozen |= done;
+        }
+        E::observe(s, ob);
+        if (TGT) {
+            // ---- the discrepancy against the recorded observation after k' steps (step is k' here: no auto-reset under TGT)
+            const unsigned k1 = (unsigned)step;
+            if (stepped && k1 <= rl) {
+                const size_t row = (size_t)min(k1, (unsigned)P.t_len);
+#pragma unroll
+                for (int q = 0; q < E::O; ++q) {
+                    const float e = ob[q] - tgt_r[(row * E::O + q) * nrl];
+                    acc = fmaf(P.w[q] * e, e, acc);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) d.state[j * ld + i] = s[j];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) d.hidden[j * ld + i] = h[j];
+#pragma unroll
+    for (int j = 0; j < E::O; ++j) d.obs[j * ld + i] = ob[j];
+    d.step[i] = step;
+    d.ret[i] = ret;
+    d.rew[i] = rew;
+    d.done[i] = done;
+    d.failed[i] = failed;
+    if (E::FINAL != FINAL_NONE) d.yielded[i] = yielded;
+    d.ep_idx[i] = es.epi;
+    d.es_count[i] = es.count;
+    d.es_retsum[i] = es.retsum;
+    d.es_lensum[i] = es.lensum;
+    if (TGT) P.loss[i] = acc;
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -2854,6 +3014,7 @@ struct vs_env {
     vs::Fnn fnn{};                // vs_set_policy_fnn: the network vs_step_policy evaluates (fnn.w == nullptr: none)
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
+    vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)
     int hrec_width = 0;           // vs_set_policy_hidden_record: floats per env and step of the hidden-state record plane, 0 off
     float* d_hrec = nullptr;      // ... the plane, f32 [traj_cap][hrec_width][ld]
     int rollout_variant = -1;     // vs_set_rollout_variant: -1 automatic, 0 k_rollout, 1 k_rollout_ws<256>, 2 k_rollout_ws<64>, 3 / 4 the three-role kernel in 64 / 256-env workgroups
@@ -2897,6 +3058,7 @@ struct Launch {
     static void rollout_fnn(vs_env* h, int k, int rec, uint64_t noise_seed, int shape);
     static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... recurrent policy
     static void rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... linear policy on a feature stack
+    static void rollout_play(vs_env* h, int k, int rec);                      // ... playback of recorded actions (+ discrepancy)
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -3137,6 +3299,19 @@ void Launch<E>::rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed) {
                                    h->lin, k, h->ar_seed, noise_seed, POP ? h->pop : Pop{});
             else no_kernel("rollout_lin");
         }, h->auto_reset, h->pop.w != nullptr);
+    });
+}
+
+template <class E>
+void Launch<E>::rollout_play(vs_env* h, int k, int rec) {
+    // one wave of 64 envs per workgroup, no LDS; no kernel for the discrete-action family or for a target under auto-reset
+    with_int<0, 1, 2>(rec, [&](auto REC) __attribute__((always_inline)) {
+        with_bools([&](auto AR, auto TGT) __attribute__((always_inline)) {
+            if constexpr (!std::is_same<E, BobD>::value && !(AR && TGT))
+                hipLaunchKernelGGL((k_rollout_play<E, AR, REC, TGT>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d,
+                                   h->play, k, h->ar_seed);
+            else no_kernel("rollout_play");
+        }, h->auto_reset, h->play.tgt != nullptr);
     });
 }
 

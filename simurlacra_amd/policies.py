@@ -491,3 +491,150 @@ def linear_slot_map(terms, n_vis, act_dim):
         for f, sl in enumerate(slots):
             out[j * 128 + sl] = j * num_feat + f
     return out
+
+
+# ------------------------------------------------------------------------------------------------- open-loop policies
+class PlaybackPolicy(Policy):
+    """Replays recorded actions, whatever the observation (upstream Pyrado policies/feed_forward/playback.py).
+    act_recordings: a list of [T_r, A] arrays.  reset() moves to the next recording, cyclically, and rewinds it -- the first
+    reset() selects recording 0 -- unless no_reset is set; forward() returns the current row and advances, zeros once the
+    recording has ended."""
+
+    name = "pb"
+
+    def __init__(self, spec, act_recordings, no_reset: bool = False, use_cuda=False):
+        import numpy as np
+
+        super().__init__(spec)
+        if not isinstance(act_recordings, (list, tuple)) or len(act_recordings) == 0:
+            from .exceptions import TypeErr
+
+            raise TypeErr(given=act_recordings, expected_type=list)
+        A = spec.act_space.flat_dim
+        self._recs = []
+        for r in act_recordings:
+            arr = np.asarray(r.detach().cpu().numpy() if hasattr(r, "detach") else r, dtype=np.float32)
+            arr = arr.reshape(-1, A) if arr.ndim <= 1 else arr
+            if arr.ndim != 2 or arr.shape[1] != A:
+                from .exceptions import ShapeErr
+
+                raise ShapeErr(given=arr, expected_match=(arr.shape[0], A))
+            self._recs.append(torch.from_numpy(np.ascontiguousarray(arr)))
+        self._no_reset = bool(no_reset)
+        self._curr_rec = -1
+        self._curr_step = 0
+        self._tables = {}
+
+    @property
+    def num_rec(self) -> int:
+        return len(self._recs)
+
+    @property
+    def curr_rec(self) -> int:
+        return self._curr_rec
+
+    @property
+    def curr_step(self) -> int:
+        return self._curr_step
+
+    @property
+    def no_reset(self) -> bool:
+        return self._no_reset
+
+    @no_reset.setter
+    def no_reset(self, value: bool):
+        self._no_reset = bool(value)
+
+    def init_param(self, init_values=None, **kwargs):
+        pass
+
+    def reset(self, **kwargs):
+        if not self._no_reset:
+            self._curr_rec = (self._curr_rec + 1) % len(self._recs)
+            self._curr_step = 0
+
+    def forward(self, obs: torch.Tensor = None) -> torch.Tensor:
+        rec = self._recs[max(self._curr_rec, 0)]  # (before the first reset: recording 0)
+        act = rec[self._curr_step].clone() if self._curr_step < rec.shape[0] else torch.zeros(rec.shape[1])
+        self._curr_step += 1
+        return act
+
+    def table(self):
+        """(actions [n_rec, t_len, A] float32, zero beyond a recording's end, lengths [n_rec] int64), t_len >= 1"""
+        t_len = max(1, max(r.shape[0] for r in self._recs))
+        tab = torch.zeros(len(self._recs), t_len, self._recs[0].shape[1])
+        for k, r in enumerate(self._recs):
+            tab[k, : r.shape[0]] = r
+        return tab, torch.tensor([r.shape[0] for r in self._recs], dtype=torch.int64)
+
+    def actions_at(self, steps, recs) -> torch.Tensor:
+        """The actions [n, A] of n independent replays: entry i is row steps[i] of recording recs[i], zeros from that
+        recording's end on (what forward() returns at that step after the reset that selected that recording).  steps / recs:
+        integer tensors or arrays [n]; the result lives on the device of `steps`."""
+        steps = torch.as_tensor(steps).to(torch.int64).reshape(-1)
+        dev = steps.device
+        recs = torch.as_tensor(recs).to(device=dev, dtype=torch.int64).reshape(-1)
+        if dev not in self._tables:
+            tab, lens = self.table()
+            self._tables[dev] = (tab.to(dev), lens.to(dev))
+        tab, lens = self._tables[dev]
+        inside = (steps >= 0) & (steps < lens[recs])
+        rows = tab[recs, steps.clamp(0, tab.shape[1] - 1)]
+        return torch.where(inside[:, None], rows, torch.zeros_like(rows))
+
+
+class TimePolicy(Policy):
+    """An action that is a function of the time since the last reset (upstream Pyrado policies/feed_forward/time.py):
+    forward() returns fcn_of_time(t) and then advances t by dt; reset() sets t = 0.  t is a Python float, accumulated by
+    repeated addition -- tabulate() accumulates it the same way, so a table holds the floats forward() returns."""
+
+    name = "time"
+
+    def __init__(self, spec, fcn_of_time, dt: float, use_cuda=False):
+        if not callable(fcn_of_time):
+            from .exceptions import TypeErr
+
+            raise TypeErr(given=fcn_of_time, expected_type="callable")
+        super().__init__(spec)
+        self._fcn_of_time = fcn_of_time
+        self._dt = float(dt)
+        self._curr_time = 0.0
+
+    def init_param(self, init_values=None, **kwargs):
+        pass
+
+    def reset(self, **kwargs):
+        self._curr_time = 0.0
+
+    def _eval(self, t: float) -> torch.Tensor:
+        return torch.as_tensor(self._fcn_of_time(t), dtype=torch.float32).reshape(-1)
+
+    def forward(self, obs: torch.Tensor = None) -> torch.Tensor:
+        act = self._eval(self._curr_time)
+        self._curr_time += self._dt
+        return act
+
+    def tabulate(self, num_steps: int) -> torch.Tensor:
+        """[num_steps, A]: what num_steps forward() calls after a reset() return (the policy's own clock is left alone)"""
+        t, rows = 0.0, []
+        for _ in range(int(num_steps)):
+            rows.append(self._eval(t))
+            t += self._dt
+        return torch.stack(rows) if rows else torch.zeros(0, self.env_spec.act_space.flat_dim)
+
+
+def playback_kernel_spec(policy, max_steps=None):
+    """The arguments of VecSimEnv.set_policy_playback for an open-loop policy -- dict(actions=[n_rec, t_len, A] float32 array,
+    zero beyond each recording's end, rec_len=[n_rec] int32) -- or None for every other policy.  A PlaybackPolicy gives one
+    table row per recording; a TimePolicy one recording of max_steps rows (None without max_steps: an unbounded table)."""
+    import numpy as np
+
+    if isinstance(policy, PlaybackPolicy):
+        tab, lens = policy.table()
+        return dict(actions=tab.numpy(), rec_len=lens.numpy().astype(np.int32))
+    if isinstance(policy, TimePolicy):
+        if max_steps is None or not np.isfinite(max_steps) or int(max_steps) < 1:
+            return None
+        tab = policy.tabulate(int(max_steps))
+        return dict(actions=tab.numpy()[None].copy(), rec_len=np.array([int(max_steps)], dtype=np.int32))
+    return None

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from .exceptions import TypeErr, ValueErr
-from .policies import DummyPolicy, fnn_kernel_spec, linear_kernel_spec, rnn_kernel_spec
+from .policies import DummyPolicy, PlaybackPolicy, fnn_kernel_spec, linear_kernel_spec, playback_kernel_spec, rnn_kernel_spec
 from .seeding import derive_seed, get_base_seed, set_seed
 from .wrappers import DomainRandWrapperBuffer, DomainRandWrapperLive, fuse_wrappers, inner_env, typed_env
 
@@ -380,6 +380,19 @@ def fused_policy_specs(policy, fc, env_name):
     return fnn, rnn, (linear_kernel_spec(policy) if fnn is None and rnn is None else None)
 
 
+def fused_playback_spec(policy, fc, env_name, max_steps):
+    """(spec, fused): the arguments of VecSimEnv.set_policy_playback for an open-loop policy (PlaybackPolicy, or a TimePolicy
+    tabulated for max_steps rows; playback_kernel_spec) or None, and whether the fused kernel replays it -- under the
+    conditions of fused_policy_specs: no wrapper pipeline, not the discrete-action family.  With a spec that is not fused the
+    sampler feeds the recorded actions to the recording step kernel, one launch per step (PlaybackPolicy.actions_at)."""
+    spec = playback_kernel_spec(policy, max_steps)
+    if spec is None:
+        return None, False
+    plain_chain = (fc.delay == 0 and not np.any(fc.noise_std) and not np.any(fc.noise_mean) and not np.any(fc.var)
+                   and np.all(fc.scale == 1) and not np.any(fc.shift))
+    return spec, bool(plain_chain and env_name != "bob-d")
+
+
 class ParallelRolloutSampler:
     """Drop-in for P/sampling/parallel_rollout_sampler.py:182-323 with the rollouts batched on the GPU.
 
@@ -587,6 +600,11 @@ class ParallelRolloutSampler:
         fnn, rnn, lin = (fused_policy_specs(self.policy, fc, base.name) if (self._fuse_policy and not use_fused)
                          else (None, None, None))
         recurrent = bool(getattr(self.policy, "is_recurrent", False)) and not use_fused
+        # an open-loop policy: rollout number g = first_index + lane of this sample() call replays recording g % n_rec (the
+        # order ONE worker of the reference produces, calling policy.reset() before every rollout); the policy object's own
+        # position is left alone
+        play, play_fused = (None, False) if use_fused else fused_playback_spec(self.policy, fc, base.name, int(max_steps))
+        play_fused = play_fused and self._fuse_policy
         if population is not None and fnn is None and rnn is None and lin is None:
             raise ValueErr(msg="a policy population needs a policy the fused kernel evaluates (fnn_kernel_spec / rnn_kernel_spec / "
                                "linear_kernel_spec)")
@@ -681,6 +699,20 @@ class ParallelRolloutSampler:
                 if all_done():  # one scalar sync per launch
                     break
             v.set_traj_offset(0)
+        elif play_fused:
+            # rollout() with an open-loop policy == vs_step_policy with vs_set_policy_playback: table row -> step -> record
+            # inside ONE kernel; without a lane map lane i replays recording (first_index + i) % n_rec
+            v.set_policy_playback(play["actions"], play["rec_len"])
+            v.set_record_mode(2 if full else 1)
+            v.set_traj_capacity(T_cap)
+            while t < T_cap:
+                k = int(min(self._chunk, T_cap - t))
+                v.set_traj_offset(t)
+                v.step_policy(k, record=True)
+                t += k
+                if all_done():  # one scalar sync per launch
+                    break
+            v.set_traj_offset(0)
         else:
             # policy in the loop: rollout() with the caller's policy (rollout.py:185-258).  One recording step kernel per env
             # step -- vs_step_record writes the observation the policy saw, its action, the reward, the done bit and (full
@@ -689,11 +721,18 @@ class ParallelRolloutSampler:
             policy = self.policy.to(dev) if hasattr(self.policy, "to") else self.policy
             if hasattr(policy, "eval"):
                 policy.eval() if eval else policy.train()
-            if hasattr(policy, "reset"):
+            if hasattr(policy, "reset") and play is None:
                 policy.reset()
             v.set_record_mode(2 if full else 1)
             v.set_traj_capacity(T_cap)
             v.set_traj_offset(0)
+            graph_policy = self._graph_policy and play is None
+            if play is not None:
+                # an open-loop policy outside the fused kernel (a wrapper pipeline, or fuse_policy=False): the recorded actions
+                # through the recording step path, row = every lane's own step counter
+                pb = policy if isinstance(policy, PlaybackPolicy) else PlaybackPolicy(policy.env_spec, [play["actions"][0]])
+                step_t = v.tensor(L.VS_STEPCOUNT)[0, :n]
+                rec_t = (torch.arange(n, device=dev, dtype=torch.int64) + int(first_index)) % pb.num_rec
             # a recurrent policy: ONE device tensor [n, H] of hidden states, zeroed at the start of the batch, passed through
             # policy(obs, hidden) and updated in place; the state before every step goes into the record plane (vs_record_hidden,
             # before the vs_step_record that advances the row counter: a captured graph replays both)
@@ -702,6 +741,8 @@ class ParallelRolloutSampler:
                 v.set_policy_hidden_record(W)
 
             def act_of(obs_now, row):
+                if play is not None:
+                    return pb.actions_at(step_t, rec_t)
                 if not recurrent:
                     return policy(obs_now)
                 v.record_hidden(hid, row=row)
@@ -713,7 +754,7 @@ class ParallelRolloutSampler:
             # nothing the policy makes of their last observation can move them or raise their NaN flag
             v.set_freeze_done(True)
             try:
-                if self._graph_policy:
+                if graph_policy:
                     # one hipGraph of SEG iterations, replayed until every lane is done: the step kernel takes its record row from a
                     # device-side counter (vs_set_record_row), so a replay continues where the last one stopped
                     SEG = 32
@@ -756,7 +797,7 @@ class ParallelRolloutSampler:
                     finally:
                         v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
                 with torch.no_grad():
-                    while t < T_cap and not self._graph_policy:
+                    while t < T_cap and not graph_policy:
                         obs_now = visible(obs_full, 0).t().contiguous()  # [n, O']: what the policy sees
                         act = act_of(obs_now, t).to(torch.float32).reshape(n, A).contiguous()
                         v.step_record(act, row=t)

@@ -654,6 +654,73 @@ class VecSimEnv:
         self._check(self._lib.vs_set_policy_linear(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_linear")
 
+    def _table_arg(self, x):
+        """a float32 table for the library: a device tensor stays where it is, anything else becomes a host array"""
+        if hasattr(x, "detach"):
+            import torch
+
+            t = x.detach()
+            if t.is_cuda:
+                t = t.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+                torch.cuda.current_stream(self.device).synchronize()  # (the library re-lays it on its own stream)
+                return t, t.data_ptr(), tuple(t.shape)
+            x = t.numpy()
+        keep = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        return keep, keep.ctypes.data, keep.shape
+
+    def set_policy_playback(self, actions, rec_len=None, lane_rec=None):
+        """Replay recorded actions in the fused kernel of step_policy (vs_set_policy_playback; PlaybackPolicy / a tabulated
+        TimePolicy).  actions: [n_rec, t_len, A] (a torch tensor, host or device, or an array); rec_len [n_rec]: the steps of each
+        recording (None: t_len), past which the action is 0; lane_rec [n_envs]: the recording every lane replays (None: lane i
+        replays (index offset + i) % n_rec).  The row is the env's own step counter.  actions=None removes the policy."""
+        self._rnn_hs = 0  # (a playback policy replaces a recurrent one)
+        if actions is None:
+            self._check(self._lib.vs_set_policy_playback(self._h, None, 0, 0, None, None), "vs_set_policy_playback")
+            return
+        keep, ptr, shape = self._table_arg(actions)
+        if len(shape) != 3 or shape[2] != self.dims["A"]:
+            raise ShapeErr(msg=f"actions must be [n_rec, t_len, {self.dims['A']}], got shape {tuple(shape)}")
+        rl = lr = None
+        if rec_len is not None:
+            rl = np.ascontiguousarray(np.asarray(rec_len, dtype=np.int32).reshape(-1))
+            if rl.size != shape[0]:
+                raise ShapeErr(msg=f"rec_len needs one entry per recording ({shape[0]}), got {rl.size}")
+        if lane_rec is not None:
+            lr = np.ascontiguousarray(np.asarray(lane_rec, dtype=np.int32).reshape(-1))
+            if lr.size != self.n_envs:
+                raise ShapeErr(msg=f"lane_rec needs one entry per env ({self.n_envs}), got {lr.size}")
+        self._check(self._lib.vs_set_policy_playback(self._h, C.c_void_p(ptr), int(shape[0]), int(shape[1]),
+                                                     None if rl is None else rl.ctypes.data_as(C.c_void_p),
+                                                     None if lr is None else lr.ctypes.data_as(C.c_void_p)),
+                    "vs_set_policy_playback")
+
+    def set_rollout_target(self, obs, weights=None):
+        """The recorded observations the playback rollouts are compared with (vs_set_rollout_target): obs [n_rec, t_len + 1, O],
+        row k the observation after k steps; weights [O] >= 0 (None: 1).  step_policy then adds w_d (obs'_d - target_d)^2 of every
+        step inside the recording to rollout_loss().  obs=None removes the target."""
+        if obs is None:
+            self._check(self._lib.vs_set_rollout_target(self._h, None, 0, 0, None), "vs_set_rollout_target")
+            return
+        keep, ptr, shape = self._table_arg(obs)
+        if len(shape) != 3 or shape[2] != self.dims["O"] or shape[1] < 2:
+            raise ShapeErr(msg=f"obs must be [n_rec, t_len + 1, {self.dims['O']}], got shape {tuple(shape)}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+            if w.size != self.dims["O"]:
+                raise ShapeErr(msg=f"weights needs one entry per observation row ({self.dims['O']}), got {w.size}")
+        self._check(self._lib.vs_set_rollout_target(self._h, C.c_void_p(ptr), int(shape[0]), int(shape[1]) - 1,
+                                                    None if w is None else w.ctypes.data_as(C.c_void_p)), "vs_set_rollout_target")
+
+    def rollout_loss(self):
+        """Zero-copy torch view [n_envs] of the per-lane discrepancy sums (VS_ROLLOUT_LOSS)"""
+        import torch
+
+        ptr = self._lib.vs_get(self._h, L.VS_ROLLOUT_LOSS)
+        if not ptr:
+            raise ValueErr(msg="no rollout target set (set_rollout_target)")
+        return torch.as_tensor(_DevArray(ptr, (self.ld,), "<f4", self), device=f"cuda:{self.device}")[: self.n_envs]
+
     def set_policy_population(self, params, lane_set=None):
         """A population of parameter vectors for step_policy (vs_set_policy_population): params [P, n_params] -- P vectors of the
         policy of the last set_policy_fnn / set_policy_rnn / set_policy_linear, each in that call's torch order; a torch tensor (host or device) or
