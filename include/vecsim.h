@@ -97,7 +97,13 @@ enum vs_buffer {
                                 * the policy's hidden state BEFORE recorded step t; same rows as VS_TRAJ_REC (capacity, offset) */
     VS_ROLLOUT_LOSS = 27,      /* f32 [ld]  per-lane discrepancy sum of vs_set_rollout_target (NULL / nothing copied without a target):
                                 * zeroed by vs_set_rollout_target and by vs_reset (the reset lanes), accumulated by vs_step_policy */
-    VS_BUFFER_COUNT = 28
+    VS_ROLLOUT_GRAD = 28,      /* f32 [n_params][ld]  d VS_ROLLOUT_LOSS / d (chosen domain parameter j) of vs_set_rollout_sens (NULL /
+                                * nothing copied while sensitivities are off) */
+    VS_ROLLOUT_GN = 29,        /* f32 [n_params (n_params + 1) / 2][ld]  Gauss-Newton matrix sum w J^T J of the same sum: the upper
+                                * triangle, row-major ((0,0) (0,1) .. (0,n-1) (1,1) ..) */
+    VS_ROLLOUT_SENS = 30,      /* f32 [(S + H) * NP][ld]  the carried tangents d (state, hidden state) / d parameter, row
+                                * (state row, then hidden row) * NP + tangent; NP = 1, 2 or 4 >= n_params */
+    VS_BUFFER_COUNT = 31
 };
 
 /* vs_task_cfg.flags */
@@ -403,6 +409,28 @@ int vs_set_policy_playback(vs_handle h, const float* actions, int n_rec, int t_l
  * Refused: no playback policy on the handle (VS_ERR_STATE); n_rec / t_len different from the playback policy's, a negative or
  * NaN weight (VS_ERR_ARG).  With a target and auto-reset on, vs_step_policy returns VS_ERR_STATE. */
 int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t_len, const float* weights);
+/* Sensitivities of the trajectory discrepancy with respect to domain parameters (gradient-based identification: Gauss-Newton,
+ * Levenberg-Marquardt): vs_step_policy on a handle with a playback policy and a rollout target then runs a kernel that, next
+ * to VS_ROLLOUT_LOSS (the same bits, as are state, hidden state, observation, flags and step counter), carries
+ * d (state, hidden state) / d theta_j from step to step in forward mode for the n_params chosen parameters theta_j =
+ * vs_param_name(type, param_idx[j]) and sums, where the loss sums a step, with e_d the loss's own e and J_dj = d obs'[d] / d theta_j,
+ * for d = 0 .. O - 1 in that order, in fp32
+ *     VS_ROLLOUT_GRAD[j][lane]   = fmaf(2 weights[d] e_d, J_dj, VS_ROLLOUT_GRAD[j][lane])
+ *     VS_ROLLOUT_GN[(j,l)][lane] = fmaf(weights[d] J_dj, J_dl, VS_ROLLOUT_GN[(j,l)][lane])      (j <= l, upper triangle, row-major)
+ * The derivative runs through _calc_constants and the dynamics on the lane's own VS_PARAMS; the bounds of the action and state
+ * spaces, the initial state and the initial hidden state are held constant with respect to the parameters, and kinks (clip,
+ * dead zone, Coulomb friction's sign) follow the branch taken.  A lane frozen at done adds nothing; a lane that ends early stops
+ * summing at its last step, like the loss.  The kernel carries NP = 1, 2 or 4 tangents: n_params = 3 runs 4 with an unseeded
+ * column.  All three buffers are zeroed by this call and by vs_set_rollout_target (every lane) and by vs_reset (the reset
+ * lanes); they carry over launch cuts.  n_params == 0 (param_idx may be NULL) turns the sensitivities off and frees the
+ * buffers; vs_set_policy_fnn / _rnn / _linear / _playback drop them with the playback policy, removing the target drops them too.
+ * With sensitivities on, vs_step_policy with record != 0 returns VS_ERR_STATE (recorded rollouts come from the plain kernel:
+ * the same values).
+ * Refused with the handle left as it was: NULL param_idx with n_params > 0, n_params outside 0 .. VS_SENS_MAX_PARAMS, an index
+ * outside the family's parameter list or repeated (VS_ERR_ARG); no playback policy or no rollout target on the handle,
+ * auto-reset on, a wrapper pipeline on the handle, the discrete-action family (VS_ERR_STATE). */
+#define VS_SENS_MAX_PARAMS 4
+int vs_set_rollout_sens(vs_handle h, const int32_t* param_idx, int n_params);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

@@ -42,7 +42,7 @@ def __getattr__(name):
         from . import policies
 
         return getattr(policies, name)
-    if name in ("TrajectoryMatchSampler", "TrajectoryMatchResult"):
+    if name in ("TrajectoryMatchSampler", "TrajectoryMatchResult", "TrajectoryMatchGradResult", "expand_upper_triangle"):
         from . import sysid
 
         return getattr(sysid, name)

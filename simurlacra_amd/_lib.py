@@ -12,6 +12,9 @@ ENV_TYPES = {"omo": 0, "bob": 1, "qq-su": 2, "qcp-su": 3, "qbb": 4, "qq-st": 5, 
  VS_FAILED, VS_EPSTAT_COUNT, VS_EPSTAT_RETSUM, VS_EPSTAT_LENSUM, VS_JAC_STATE, VS_JAC_REW, VS_JAC_OBS) = range(25)
 VS_POLICY_HIDDEN, VS_POLICY_HIDDEN_REC = 25, 26  # the recurrent policy's running hidden state and its record plane
 VS_ROLLOUT_LOSS = 27  # per-lane discrepancy sum of vs_set_rollout_target
+# vs_set_rollout_sens: the sum's gradient, its Gauss-Newton matrix (upper triangle) and the carried state tangents
+VS_ROLLOUT_GRAD, VS_ROLLOUT_GN, VS_ROLLOUT_SENS = 28, 29, 30
+VS_SENS_MAX_PARAMS = 4
 VS_FLAG_SIMPLE_DYNAMICS, VS_FLAG_LONG_POLE, VS_FLAG_ACT_NORM, VS_FLAG_FREEZE_DONE, VS_FLAG_LEAN_STEP = 1, 2, 4, 8, 16
 RV_PLAIN, RV_WS256, RV_WS64, RV_WS64G, RV_WS256G = 0, 1, 2, 3, 4  # vs_rollout_variant
 VS_NL_NONE, VS_NL_TANH, VS_NL_RELU, VS_NL_SIGMOID = 0, 1, 2, 3  # vs_fnn_desc nonlinearities
@@ -100,6 +103,7 @@ _SIGNATURES = {
     "vs_set_policy_linear": (C.c_int, [_P, C.POINTER(LinDesc), _P, C.c_int64]),
     "vs_set_policy_playback": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "vs_set_rollout_target": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "vs_set_rollout_sens": (C.c_int, [_P, _P, C.c_int]),
     "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
     "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),
     "vs_set_policy_population": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),

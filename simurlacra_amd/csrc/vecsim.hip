@@ -30,6 +30,13 @@ __global__ __launch_bounds__(256) void k_zero_masked(float* __restrict__ p, cons
     p[i] = 0.f;
 }
 
+// ... and `rows` rows of the sensitivity buffers (VS_ROLLOUT_GRAD / _GN / _SENS) of the reset lanes
+__global__ __launch_bounds__(256) void k_zero_rows_masked(float* __restrict__ p, int rows, size_t ld, const uint8_t* __restrict__ mask, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !mask[i]) return;
+    for (int j = 0; j < rows; ++j) p[(size_t)j * ld + i] = 0.f;
+}
+
 // vs_set_policy_playback / vs_set_rollout_target: the caller's table src [n_rec][rw] (rw = rows x width floats per recording)
 // into the kernel's recording-minor layout dst [rw][n_rec_ld], 0 in the padding columns n_rec .. n_rec_ld - 1
 __global__ __launch_bounds__(256) void k_relay_table(const float* __restrict__ src, int n_rec, int64_t rw, float* __restrict__ dst,
@@ -493,7 +500,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 extern "C" {
 
-int vs_version(void) { return 308; }
+int vs_version(void) { return 309; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -645,6 +652,9 @@ int vs_destroy(vs_handle h) {
     if (h->play.rec_len) (void)hipFree((void*)h->play.rec_len);
     if (h->play.lane_rec) (void)hipFree((void*)h->play.lane_rec);
     if (h->play.loss) (void)hipFree(h->play.loss);
+    if (h->sens.grad) (void)hipFree(h->sens.grad);
+    if (h->sens.gn) (void)hipFree(h->sens.gn);
+    if (h->sens.sens) (void)hipFree(h->sens.sens);
     if (h->rnn.hid) (void)hipFree(h->rnn.hid);
     if (h->pop.w) (void)hipFree((void*)h->pop.w);
     if (h->pop.wg_set) (void)hipFree((void*)h->pop.wg_set);
@@ -823,6 +833,26 @@ int vs_set_obs_pipeline(vs_handle h, const float* scale, const float* shift, con
     return VS_OK;
 }
 
+// rows of VS_ROLLOUT_GRAD / _GN / _SENS of a handle with sensitivities on
+static void sens_rows(vs_handle h, int* g, int* t, int* s) {
+    const EnvInfo& ei = ENV_INFO[h->type];
+    *g = h->sens.n;
+    *t = h->sens.n * (h->sens.n + 1) / 2;
+    *s = (ei.S + ei.H) * h->sens.np;
+}
+
+// zero the three sensitivity buffers: every lane (m == nullptr) or the masked ones (m: the staged device mask)
+static int zero_sens(vs_handle h, const uint8_t* m) {
+    int rows[3];
+    sens_rows(h, &rows[0], &rows[1], &rows[2]);
+    float* bufs[3] = {h->sens.grad, h->sens.gn, h->sens.sens};
+    for (int b = 0; b < 3; ++b) {
+        if (!m) HIPCHK(h, hipMemsetAsync(bufs[b], 0, (size_t)rows[b] * h->d.ld * sizeof(float), h->stream));
+        else hipLaunchKernelGGL(k_zero_rows_masked, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, bufs[b], rows[b], (size_t)h->d.ld, m, h->d.n);
+    }
+    return VS_OK;
+}
+
 int vs_reset(vs_handle h, const float* init_state, int64_t pitch, int full, const uint8_t* mask, uint64_t seed) {
     if (!h) return VS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
@@ -844,6 +874,9 @@ int vs_reset(vs_handle h, const float* init_state, int64_t pitch, int full, cons
     if (h->play.loss) {  // a new rollout starts its discrepancy sum at 0
         if (!m) HIPCHK(h, hipMemsetAsync(h->play.loss, 0, (size_t)h->d.ld * sizeof(float), h->stream));
         else hipLaunchKernelGGL(k_zero_masked, grid_for(h->d.ld), dim3(BLOCK), 0, h->stream, h->play.loss, m, h->d.n);
+    }
+    if (h->sens.n) {  // ... and its sensitivities
+        if (int rc2 = zero_sens(h, m)) return rc2;
     }
     HIPCHK(h, hipGetLastError());
     return VS_OK;
@@ -1072,7 +1105,18 @@ static int drop_lin(vs_handle h) {
     return VS_OK;
 }
 
+static int drop_sens(vs_handle h) {
+    if (h->sens.grad) HIPCHK(h, hipFree(h->sens.grad));
+    h->sens.grad = nullptr;
+    if (h->sens.gn) HIPCHK(h, hipFree(h->sens.gn));
+    h->sens.gn = nullptr;
+    if (h->sens.sens) HIPCHK(h, hipFree(h->sens.sens));
+    h->sens = Sens{};
+    return VS_OK;
+}
+
 static int drop_target(vs_handle h) {
+    if (int rc = drop_sens(h)) return rc;  // (the sensitivities belong to the target's sum)
     if (h->play.tgt) HIPCHK(h, hipFree((void*)h->play.tgt));
     h->play.tgt = nullptr;
     if (h->play.loss) HIPCHK(h, hipFree(h->play.loss));
@@ -1467,10 +1511,62 @@ int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t
         if (dl) (void)hipFree(dl);
         return fail(h, VS_ERR_HIP, "vs_set_rollout_target: allocation", e);
     }
-    if (int rc = drop_target(h)) { (void)hipFree(dt); (void)hipFree(dl); return rc; }
+    const Sens keep = h->sens;  // a new target keeps the sensitivities on and zeroes their sums
+    h->sens = Sens{};
+    if (int rc = drop_target(h)) { h->sens = keep; (void)hipFree(dt); (void)hipFree(dl); return rc; }
+    h->sens = keep;
     h->play.tgt = dt;
     h->play.loss = dl;
     for (int q = 0; q < MAXO; ++q) h->play.w[q] = w[q];
+    if (h->sens.n) return zero_sens(h, nullptr);
+    return VS_OK;
+}
+
+int vs_set_rollout_sens(vs_handle h, const int32_t* param_idx, int n_params) {
+    if (!h) return VS_ERR_ARG;
+    const EnvInfo& ei = ENV_INFO[h->type];
+    if (n_params < 0 || n_params > VS_SENS_MAX_PARAMS) return fail(h, VS_ERR_ARG, "vs_set_rollout_sens: n_params outside 0 .. VS_SENS_MAX_PARAMS");
+    if (n_params > 0) {  // every check before anything changes: a refused call leaves the handle as it was
+        if (!param_idx) return fail(h, VS_ERR_ARG, "vs_set_rollout_sens: NULL param_idx");
+        for (int j = 0; j < n_params; ++j) {
+            if (param_idx[j] < 0 || param_idx[j] >= ei.P) return fail(h, VS_ERR_ARG, "vs_set_rollout_sens: a parameter index outside the family's list");
+            for (int l = 0; l < j; ++l)
+                if (param_idx[l] == param_idx[j]) return fail(h, VS_ERR_ARG, "vs_set_rollout_sens: a parameter index is repeated");
+        }
+        if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, "vs_set_rollout_sens: the discrete-action family takes no playback policy");
+        if (!h->play.act) return fail(h, VS_ERR_STATE, "vs_set_rollout_sens: no playback policy set (vs_set_policy_playback)");
+        if (!h->play.tgt) return fail(h, VS_ERR_STATE, "vs_set_rollout_sens: no rollout target set (vs_set_rollout_target)");
+        if (h->auto_reset) return fail(h, VS_ERR_STATE, "vs_set_rollout_sens: sensitivities run with auto-reset off");
+        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_rollout_sens: not available with a wrapper pipeline on the handle");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still use the buffers this replaces)
+    if (n_params == 0) return drop_sens(h);
+    Sens q{};
+    q.n = n_params;
+    q.np = n_params <= 2 ? n_params : 4;
+    for (int j = 0; j < SENS_MAXP; ++j) q.idx[j] = j < n_params ? param_idx[j] : -1;
+    const size_t ld = (size_t)h->d.ld;
+    const size_t rows[3] = {(size_t)q.n, (size_t)(q.n * (q.n + 1) / 2), (size_t)((ei.S + ei.H) * q.np)};
+    float* bufs[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int b = 0; b < 3 && e == hipSuccess; ++b) {
+        e = hipMalloc((void**)&bufs[b], rows[b] * ld * sizeof(float));
+        if (e == hipSuccess) e = hipMemsetAsync(bufs[b], 0, rows[b] * ld * sizeof(float), h->stream);
+    }
+    if (e != hipSuccess) {
+        for (int b = 0; b < 3; ++b)
+            if (bufs[b]) (void)hipFree(bufs[b]);
+        return fail(h, VS_ERR_HIP, "vs_set_rollout_sens: allocation", e);
+    }
+    if (int rc = drop_sens(h)) {
+        for (int b = 0; b < 3; ++b) (void)hipFree(bufs[b]);
+        return rc;
+    }
+    q.grad = bufs[0];
+    q.gn = bufs[1];
+    q.sens = bufs[2];
+    h->sens = q;
     return VS_OK;
 }
 
@@ -1575,6 +1671,14 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
     if (h->play.act) {
         if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
         if (h->play.tgt && h->auto_reset) return fail(h, VS_ERR_STATE, "vs_step_policy: a rollout target runs with auto-reset off");
+        if (h->sens.n) {
+            if (record) return fail(h, VS_ERR_STATE, "vs_step_policy: no records with sensitivities on (vs_set_rollout_sens)");
+            if (h->auto_reset || !h->play.tgt) return fail(h, VS_ERR_STATE, "vs_step_policy: sensitivities need a rollout target and auto-reset off");
+            HIPCHK(h, hipSetDevice(h->device));
+            DISPATCH_ENV(h->type, Launch<E>::rollout_play_sens(h, k_steps));
+            HIPCHK(h, hipGetLastError());
+            return VS_OK;
+        }
         if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
         HIPCHK(h, hipSetDevice(h->device));
         DISPATCH_ENV(h->type, Launch<E>::rollout_play(h, k_steps, record ? h->record_mode : 0));
@@ -1792,6 +1896,9 @@ static bool buf_info(vs_handle h, int which, void** p, size_t* bytes) {
         case VS_JAC_OBS: *p = d.jac_o; *bytes = d.jac_o ? (size_t)ei.O * (ei.S + ei.A) * ld * 4 : 0; return true;
         case VS_POLICY_HIDDEN: *p = h->rnn.hid; *bytes = h->rnn.hid ? (size_t)h->rnn.hs * ld * 4 : 0; return true;
         case VS_ROLLOUT_LOSS: *p = h->play.loss; *bytes = h->play.loss ? ld * 4 : 0; return true;
+        case VS_ROLLOUT_GRAD: *p = h->sens.grad; *bytes = h->sens.n ? (size_t)h->sens.n * ld * 4 : 0; return true;
+        case VS_ROLLOUT_GN: *p = h->sens.gn; *bytes = h->sens.n ? (size_t)(h->sens.n * (h->sens.n + 1) / 2) * ld * 4 : 0; return true;
+        case VS_ROLLOUT_SENS: *p = h->sens.sens; *bytes = h->sens.n ? (size_t)(ei.S + ei.H) * h->sens.np * ld * 4 : 0; return true;
         case VS_POLICY_HIDDEN_REC: *p = h->d_hrec; *bytes = h->d_hrec ? (size_t)h->traj_cap * h->hrec_width * ld * 4 : 0; return true;
 #ifdef VS_WS_STAMP
         case 99: *p = d.dbg; *bytes = (size_t)(ld / 64) * 12 * 8; return true;

@@ -3,6 +3,11 @@
 // The env math in vecsim_envs.h is templated on its scalar type R.  R = float is the production path (identical code to
 // the untemplated version); R = Dual<N> carries N tangents (one per input: S state dims + A action dims) through the very
 // same expressions, so d(s', r, obs)/d(s, a) comes out of one extra evaluation per lane with no hand-derived formulas.
+// The derived constants have a scalar type of their own, C (vecsim_envs.h: calc_consts<C>, dynamics<R, C>): C = float everywhere
+// but in the trajectory-match sensitivities (k_rollout_play_sens), where C = R = Dual<NP> carries d/d(domain parameter) through
+// _calc_constants and the step.  Convention there: the bounds of the action and state spaces, the initial state and the initial
+// hidden state are held constant with respect to the parameters (act_bounds, state_bounds, limit_act, the reward, sample_init and
+// init_hidden take float constants only).
 // Conventions at kinks follow the true one-sided derivative of the branch that was taken: a clipped action or an action
 // inside the dead zone has zero gradient, fmod has slope 1, the +-pi fold slope -1 on the folded branch, sign() slope 0.
 #pragma once
@@ -91,6 +96,18 @@ __device__ __forceinline__ Dual<N> vmax(const Dual<N>& a, float b) { return vmax
 __device__ __forceinline__ float vabs(float a) { return fabsf(a); }
 template <int N>
 __device__ __forceinline__ Dual<N> vabs(const Dual<N>& a) { return a.v < 0.f ? -a : a; }
+
+// sqrt (the oscillator's omega and zeta): the float overload is the library call the constants have always used
+__device__ __forceinline__ float vsqrt(float a) { return sqrtf(a); }
+template <int N>
+__device__ __forceinline__ Dual<N> vsqrt(const Dual<N>& a) {
+    Dual<N> r;
+    r.v = sqrtf(a.v);
+    const float g = 0.5f / r.v;
+#pragma unroll
+    for (int k = 0; k < N; ++k) r.d[k] = g * a.d[k];
+    return r;
+}
 
 __device__ __forceinline__ bool visnan(float a) { return isnan(a); }
 template <int N>

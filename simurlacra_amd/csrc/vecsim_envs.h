@@ -6,6 +6,10 @@
 // Layout contract shared with vecsim.hip and the Python shim:
 //   params[P]  raw domain parameters in get_nominal_domain_param() order
 //   consts[K]  derived constants; the first KS of them are what one step() reads, the rest are reset-only
+// Scalar types: R of the state / action path and C of the derived constants (vecsim_dual.h).  C = float by default; with
+// C = Dual<NP> calc_consts and dynamics carry d/d(domain parameter).  The bounds of the action and state spaces, the initial
+// state and the initial hidden state are held constant with respect to the parameters: act_bounds, state_bounds, limit_act, the
+// reward, sample_init and init_hidden take float constants only.  Kinks follow the branch taken.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -342,10 +346,11 @@ struct Omo : EnvDefaults<1> {
     static constexpr bool WS_G3 = true;
     // (WS_PAYS: with its batch loops unrolled the split pays even for this small step: +8 % with records, +5 % without)
     enum { C_A10, C_A11, C_B1, C_AMAX };
-    __device__ static void calc_consts(const Task&, const float* p, float* c) {  // _calc_constants :88-103
-        float m = p[0], k = p[1], d = p[2];
-        float omega = sqrtf(k / m);
-        float zeta = d / (2.0f * sqrtf(m * k));
+    template <class C = float>
+    __device__ static void calc_consts(const Task&, const C* p, C* c) {  // _calc_constants :88-103
+        C m = p[0], k = p[1], d = p[2];
+        C omega = vsqrt(k / m);
+        C zeta = d / (2.0f * vsqrt(m * k));
         c[C_A10] = -(omega * omega);        // A[1,0], _step_dynamics :109
         c[C_A11] = -2.0f * zeta * omega;    // A[1,1]
         c[C_B1] = 1.0f / m;                 // B[1]
@@ -355,8 +360,8 @@ struct Omo : EnvDefaults<1> {
         hi[0] = 1.0f; hi[1] = 10.0f; lo[0] = -1.0f; lo[1] = -10.0f;
     }
     __device__ static void act_bounds(const float* c, float* lo, float* hi) { hi[0] = c[C_AMAX]; lo[0] = -c[C_AMAX]; }
-    template <class R>
-    __device__ static void dynamics(const Task& T, const float* c, R* s, R*, const R* a, const R*) {  // :105-114
+    template <class R, class C = float>
+    __device__ static void dynamics(const Task& T, const C* c, R* s, R*, const R* a, const R*) {  // :105-114
         R sd0 = s[1];
         R sd1 = c[C_A10] * s[0] + c[C_A11] * s[1] + c[C_B1] * a[0];
         s[0] = s[0] + sd0 * T.dt;  // forward Euler
@@ -413,9 +418,10 @@ struct BobT : EnvDefaults<1> {
     }
     enum { C_MG, C_M, C_FRICT, C_OFF, C_INV_ZETA_BALL, C_J_BEAM, C_XMAX, C_AMAX, C_CMAX };
     static constexpr int CMAX = C_CMAX;
-    __device__ static void calc_consts(const Task& T, const float* p, float* c) {  // _calc_constants :89-98
-        float g = p[0], m_ball = p[1], r_ball = p[2], m_beam = p[3], l_beam = p[4], d_beam = p[5];
-        float J_ball = 2.0f / 5 * m_ball * r_ball * r_ball;
+    template <class C = float>
+    __device__ static void calc_consts(const Task& T, const C* p, C* c) {  // _calc_constants :89-98
+        C g = p[0], m_ball = p[1], r_ball = p[2], m_beam = p[3], l_beam = p[4], d_beam = p[5];
+        C J_ball = 2.0f / 5 * m_ball * r_ball * r_ball;
         c[C_J_BEAM] = 1.0f / 12 * m_beam * (l_beam * l_beam + d_beam * d_beam);
         c[C_INV_ZETA_BALL] = 1.0f / (m_ball + J_ball / (r_ball * r_ball));  // 1 / zeta_ball
         c[C_MG] = m_ball * g;
@@ -425,8 +431,8 @@ struct BobT : EnvDefaults<1> {
         c[C_XMAX] = l_beam / 2.0f;               // _create_spaces :54
         c[C_AMAX] = l_beam / 2.0f * g * 3.0f;    // :55
         // ScaledExpQuadrErrRewFcn.reset (reward_functions.py:284-297), recomputed per env (Q11)
-        float smax[4] = {c[C_XMAX], PI_4_F, 10.0f, PI_F};
-        float mc = 0.f;
+        C smax[4] = {c[C_XMAX], PI_4_F, 10.0f, PI_F};
+        C mc = 0.f;
         for (int j = 0; j < 4; ++j) mc += smax[j] * (T.qd[j] * smax[j]);
         mc += c[C_AMAX] * (T.rd[0] * c[C_AMAX]);
         c[C_CMAX] = 9.210340371976182f / mc;  // -ln(1e-4)
@@ -436,8 +442,8 @@ struct BobT : EnvDefaults<1> {
         for (int j = 0; j < 4; ++j) lo[j] = -hi[j];
     }
     __device__ static void act_bounds(const float* c, float* lo, float* hi) { hi[0] = c[C_AMAX]; lo[0] = -c[C_AMAX]; }
-    template <class R>
-    __device__ static void dynamics(const Task& T, const float* c, R* s, R*, const R* act, const R*) {  // :110-129
+    template <class R, class C = float>
+    __device__ static void dynamics(const Task& T, const C* c, R* s, R*, const R* act, const R*) {  // :110-129
         R x = s[0], a = s[1] + c[C_OFF], x_dot = s[2], a_dot = s[3];
         R sa, ca;
         sincos_fast(a, &sa, &ca);
@@ -484,10 +490,11 @@ struct QQT : EnvDefaults<1> {
     static constexpr bool WS_G3 = true;
     static constexpr int WS_MIN_WAVES = 3;  // its two-role kernel runs three waves per SIMD between 256 and 384 envs per CU (WS_MID)
     enum { C_C0, C_C1, C_C2, C_C3, C_C4, C_KM, C_RM, C_DR, C_DP, C_TH_NEG, C_TH_POS };
-    __device__ static void calc_consts(const Task&, const float* p, float* c) {  // _calc_constants :70-87
-        float g = p[0], Rm = p[1], km = p[2], mr = p[3], Lr = p[4], Dr = p[5], mp = p[6], Lp = p[7], Dp = p[8];
-        float Jr = mr * Lr * Lr / 12.0f;
-        float Jp = mp * Lp * Lp / 12.0f;
+    template <class C = float>
+    __device__ static void calc_consts(const Task&, const C* p, C* c) {  // _calc_constants :70-87
+        C g = p[0], Rm = p[1], km = p[2], mr = p[3], Lr = p[4], Dr = p[5], mp = p[6], Lp = p[7], Dp = p[8];
+        C Jr = mr * Lr * Lr / 12.0f;
+        C Jp = mp * Lp * Lp / 12.0f;
         c[C_C0] = Jr + mp * Lr * Lr;
         c[C_C1] = 0.25f * mp * Lp * Lp;
         c[C_C2] = 0.5f * mp * Lp * Lr;
@@ -504,19 +511,19 @@ struct QQT : EnvDefaults<1> {
     // tr: (sin, cos)(alpha) of the PRE-step state when the caller has them in registers (fused rollout), else nullptr
     // BASELINE config 2 (4 096 envs): 98 -> 85 vector instructions on the physics wave's chain, 260 -> 241 ns per step (+ 8 %; 32 768 envs + 4 %)
     static constexpr int WS_PREP_G64 = 2;
-    template <class R>
-    __device__ static void dead_zone(const Task&, const float* c, R* a) {  // _step_dynamics :130-131
+    template <class R, class C = float>
+    __device__ static void dead_zone(const Task&, const C* c, R* a) {  // _step_dynamics :130-131
         if (c[C_TH_NEG] <= a[0] && a[0] <= c[C_TH_POS]) a[0] = 0.f;
     }
-    template <class R>
-    __device__ static void dynamics(const Task& T, const float* c, R* s, R* h, const R* act, const R* tr) {
+    template <class R, class C = float>
+    __device__ static void dynamics(const Task& T, const C* c, R* s, R* h, const R* act, const R* tr) {
         R u[1] = {act[0]};
         dead_zone(T, c, u);
         dynamics_core(T, c, s, h, u, tr);
     }
     // the step behind the dead zone (ua: the voltage that reaches the motor)
-    template <class R>
-    __device__ static void dynamics_core(const Task& T, const float* c, R* s, R*, const R* ua, const R* tr) {
+    template <class R, class C = float>
+    __device__ static void dynamics_core(const Task& T, const C* c, R* s, R*, const R* ua, const R* tr) {
         R u = ua[0];
         // _dyn :89-125, evaluated once: the reference's "RK4" re-evaluates _dyn at self.state in every stage (Q1), so
         // k_j differ only in their position-derivative slots and the update collapses to
@@ -607,11 +614,12 @@ struct QcpT : EnvDefaults<1> {
     static constexpr int FINAL = V == 1 ? FINAL_STATE_TIME : FINAL_NONE;
     enum { C_KA, C_ETA_M, C_KB, C_MTG, C_MPL2, C_MU, C_M00, C_MPL, C_M11, C_BEQ, C_BP, C_MPLG, C_TH_NEG, C_TH_POS,
            C_XMAX, C_XDMAX };
-    __device__ static void calc_consts(const Task&, const float* p, float* c) {  // _calc_constants :145-155 + _dynamics
-        float g = p[0], m_c = p[1], l_rail = p[2], eta_m = p[3], eta_g = p[4], K_g = p[5], J_m = p[6], r_mp = p[7],
-              R_m = p[8], k_m = p[9], B_p = p[10], B_eq = p[11], m_p = p[12], l_p = p[13], mu_c = p[14];
-        float J_pole = l_p * l_p * m_p / 3.0f;
-        float J_eq = m_c + (eta_g * K_g * K_g * J_m) / (r_mp * r_mp);
+    template <class C = float>
+    __device__ static void calc_consts(const Task&, const C* p, C* c) {  // _calc_constants :145-155 + _dynamics
+        C g = p[0], m_c = p[1], l_rail = p[2], eta_m = p[3], eta_g = p[4], K_g = p[5], J_m = p[6], r_mp = p[7],
+          R_m = p[8], k_m = p[9], B_p = p[10], B_eq = p[11], m_p = p[12], l_p = p[13], mu_c = p[14];
+        C J_pole = l_p * l_p * m_p / 3.0f;
+        C J_eq = m_c + (eta_g * K_g * K_g * J_m) / (r_mp * r_mp);
         c[C_KA] = (eta_g * K_g * eta_m * k_m) / (R_m * r_mp);  // f_act prefactor :195
         c[C_ETA_M] = eta_m;
         c[C_KB] = K_g * k_m / r_mp;
@@ -642,8 +650,8 @@ struct QcpT : EnvDefaults<1> {
     }
     __device__ static void act_bounds(const float*, float* lo, float* hi) { hi[0] = 6.0f; lo[0] = -6.0f; }  // MAX_ACT_QCP
     // one evaluation of QCartPoleSim._dynamics (:166-230) on the augmented state y = [x, th, x_dot, th_dot], action u
-    template <class R>
-    __device__ __forceinline__ static void f_dyn(const Task& T, const float* c, const R* y, R u, R thdd_prev, R* k, R& thdd_out, const R* tr) {
+    template <class R, class C = float>
+    __device__ __forceinline__ static void f_dyn(const Task& T, const C* c, const R* y, R u, R thdd_prev, R* k, R& thdd_out, const R* tr) {
         R th = y[1], x_dot = y[2], th_dot = y[3];
         R sin_th, cos_th;
         if (tr) { sin_th = tr[0]; cos_th = tr[1]; }
@@ -686,8 +694,8 @@ struct QcpT : EnvDefaults<1> {
     // stages 2 .. 4 of the rk4 below and its final combination; ROT: sin / cos of the stage angles by rotation from the
     // step's own (tr0).  Everything between the first stage and the new state sits inside ONE side of the caller's
     // wave-uniform branch: the stage vectors stay in registers (arrays that crossed the branch went to scratch)
-    template <bool ROT, class R>
-    __device__ __forceinline__ static void rk_tail(const Task& T, const float* c, R* s, R* h, R u, const R* k1, R a1,
+    template <bool ROT, class R, class C = float>
+    __device__ __forceinline__ static void rk_tail(const Task& T, const C* c, R* s, R* h, R u, const R* k1, R a1,
                                                    const R* tr0) {
         R dt = T.dt, dt2 = dt / 2.0f;
         R y[4], trs[2], k2[4], k3[4], k4[4], a2, a3, a4;
@@ -703,8 +711,8 @@ struct QcpT : EnvDefaults<1> {
         for (int j = 0; j < 4; ++j) s[j] = s[j] + dt / 6.0f * (k1[j] + 2.0f * k2[j] + 2.0f * k3[j] + k4[j]);
         h[0] = (a1 + a2 + a3 + a4) / 4.0f;  // mean of the stage th_ddots (:652)
     }
-    template <class R>
-    __device__ __forceinline__ static void dynamics(const Task& T, const float* c, R* s, R* h, const R* act, const R* tr) {
+    template <class R, class C = float>
+    __device__ __forceinline__ static void dynamics(const Task& T, const C* c, R* s, R* h, const R* act, const R* tr) {
         // (force-inlined: with two copies of the later stages the inliner left it a real call -- the constants and the state
         // then lived in scratch and the kernel ran three times slower)
         // rk4 (:591-655) over [x, th, x_dot, th_dot, u]; u has zero derivative; th_ddot chained through the stages.
@@ -774,8 +782,9 @@ struct Pend : EnvDefaults<1> {
     static constexpr bool WS_DRAW_P = true;
     static constexpr bool WS_G3 = true;
     enum { C_MGL2, C_DAMP, C_INV_J, C_AMAX };
-    __device__ static void calc_consts(const Task&, const float* p, float* c) {
-        float g = p[0], m = p[1], l = p[2];
+    template <class C = float>
+    __device__ static void calc_consts(const Task&, const C* p, C* c) {
+        C g = p[0], m = p[1], l = p[2];
         c[C_MGL2] = m * g * l / 2.0f;            // :104
         c[C_DAMP] = p[3];
         c[C_INV_J] = 1.0f / (m * l * l / 3.0f);  // rod about its end
@@ -785,8 +794,8 @@ struct Pend : EnvDefaults<1> {
         hi[0] = PI4_F; hi[1] = PI4_F; lo[0] = -PI4_F; lo[1] = -PI4_F;
     }
     __device__ static void act_bounds(const float* c, float* lo, float* hi) { hi[0] = c[C_AMAX]; lo[0] = -c[C_AMAX]; }
-    template <class R>
-    __device__ static void dynamics(const Task& T, const float* c, R* s, R*, const R* act, const R* tr) {
+    template <class R, class C = float>
+    __device__ static void dynamics(const Task& T, const C* c, R* s, R*, const R* act, const R* tr) {
         R sn, cs;
         if (tr) sn = tr[0];
         else sincos_fast(s[0], &sn, &cs);
@@ -860,12 +869,13 @@ struct Qbb : EnvDefaults<2> {
     enum { C_AM, C_BEQV, C_JEQ, C_CKIN, C_OFFX, C_OFFY, C_TXP, C_TXN, C_TYP, C_TYN, C_BDR2, C_JBR, C_MR2, C_CKMGR2,
            C_ZETA, C_XMAX, C_CMAX, C_IK_X0, C_IK_Y0 };
     static constexpr int CMAX = C_CMAX;
-    __device__ static void calc_consts(const Task& T, const float* p, float* c) {  // _calc_constants :204-223
-        float g = p[0], m_ball = p[1], r_ball = p[2], l_plate = p[3], r_arm = p[4], K_g = p[5], eta_g = p[6],
-              J_l = p[7], J_m = p[8], k_m = p[9], R_m = p[10], eta_m = p[11], B_eq = p[12], ball_damping = p[13];
-        float J_ball = 2.0f / 5 * m_ball * r_ball * r_ball;
-        float c_kin = 2.0f * r_arm / l_plate;
-        float r2 = r_ball * r_ball;
+    template <class C = float>
+    __device__ static void calc_consts(const Task& T, const C* p, C* c) {  // _calc_constants :204-223
+        C g = p[0], m_ball = p[1], r_ball = p[2], l_plate = p[3], r_arm = p[4], K_g = p[5], eta_g = p[6],
+          J_l = p[7], J_m = p[8], k_m = p[9], R_m = p[10], eta_m = p[11], B_eq = p[12], ball_damping = p[13];
+        C J_ball = 2.0f / 5 * m_ball * r_ball * r_ball;
+        C c_kin = 2.0f * r_arm / l_plate;
+        C r2 = r_ball * r_ball;
         c[C_AM] = eta_g * K_g * eta_m * k_m / R_m;
         c[C_BEQV] = eta_g * K_g * K_g * eta_m * k_m * k_m / R_m + B_eq;
         c[C_JEQ] = 1.0f / (eta_g * K_g * K_g * J_m + J_l);  // 1 / J_eq
@@ -878,16 +888,17 @@ struct Qbb : EnvDefaults<2> {
         c[C_CKMGR2] = c_kin * m_ball * g * r2;    // gravity :316
         c[C_ZETA] = 1.0f / (m_ball * r2 + J_ball);  // 1 / zeta
         c[C_XMAX] = l_plate / 2.0f;               // _create_spaces :97-107
-        float smax[8] = {PI_4_F, PI_4_F, c[C_XMAX], c[C_XMAX], PI5_F, PI5_F, 0.5f, 0.5f};
-        float mc = 0.f;
+        C smax[8] = {PI_4_F, PI_4_F, c[C_XMAX], c[C_XMAX], PI5_F, PI5_F, 0.5f, 0.5f};
+        C mc = 0.f;
         for (int j = 0; j < 8; ++j) mc += smax[j] * (T.qd[j] * smax[j]);
         float ma = 0.f;
         for (int j = 0; j < 2; ++j) ma += 3.0f * (T.rd[j] * 3.0f);  // MAX_ACT_QBB
         c[C_CMAX] = 9.210340371976182f / (mc + ma);
         // plate angles of the init-space reset (servo angles 0): depend on the params only -> cached (reset :238-242)
         bool simple = (T.flags & 1) != 0;
-        c[C_IK_X0] = simple ? 0.f : qbb_ik(0.f + c[C_OFFX], r_arm, l_plate / 2.0f);
-        c[C_IK_Y0] = simple ? 0.f : qbb_ik(0.f + c[C_OFFY], r_arm, l_plate / 2.0f);
+        // (the initial hidden state is held constant with respect to the parameters: the IK runs on values)
+        c[C_IK_X0] = simple ? 0.f : qbb_ik(val(0.f + c[C_OFFX]), val(r_arm), val(l_plate / 2.0f));
+        c[C_IK_Y0] = simple ? 0.f : qbb_ik(val(0.f + c[C_OFFY]), val(r_arm), val(l_plate / 2.0f));
     }
     __device__ static void state_bounds(const float* c, float* lo, float* hi) {
         hi[0] = PI_4_F; hi[1] = PI_4_F; hi[2] = c[C_XMAX]; hi[3] = c[C_XMAX];
@@ -898,21 +909,21 @@ struct Qbb : EnvDefaults<2> {
         hi[0] = hi[1] = 3.0f; lo[0] = lo[1] = -3.0f;  // MAX_ACT_QBB
     }
     static constexpr int WS_PREP_C = 2;
-    template <class R>
-    __device__ static void dead_zone(const Task& T, const float* c, R* a) {  // :261-264
+    template <class R, class C = float>
+    __device__ static void dead_zone(const Task& T, const C* c, R* a) {  // :261-264
         bool simple = (T.flags & 1) != 0;
         if (!simple && c[C_TXN] <= a[0] && a[0] <= c[C_TXP]) a[0] = 0.f;
         if (!simple && c[C_TYN] <= a[1] && a[1] <= c[C_TYP]) a[1] = 0.f;
     }
-    template <class R>
-    __device__ static void dynamics(const Task& T, const float* c, R* s, R* h, const R* act, const R* tr) {  // :247-330
+    template <class R, class C = float>
+    __device__ static void dynamics(const Task& T, const C* c, R* s, R* h, const R* act, const R* tr) {  // :247-330
         R u[2] = {act[0], act[1]};
         dead_zone(T, c, u);
         dynamics_core(T, c, s, h, u, tr);
     }
     // the step behind the dead zones (u: the voltages that reach the servos)
-    template <class R>
-    __device__ static void dynamics_core(const Task& T, const float* c, R* s, R* h, const R* u, const R*) {
+    template <class R, class C = float>
+    __device__ static void dynamics_core(const Task& T, const C* c, R* s, R* h, const R* u, const R*) {
         bool simple = (T.flags & 1) != 0;
         R a0 = u[0], a1 = u[1];
         R th_x = s[0] + c[C_OFFX], th_y = s[1] + c[C_OFFY];

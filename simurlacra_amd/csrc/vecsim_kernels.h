@@ -12,6 +12,7 @@
 //                                     LDS: what runs while k_rollout would leave the SIMDs with a single wave
 //   k_*_mixed       vs_mixed_*        several families in one launch (one workgroup = one family)
 //   k_step_jac      vs_step_jac       step + Jacobians by forward-mode dual numbers
+//   k_rollout_play_sens  vs_step_policy   playback rollout + discrepancy with its gradient and Gauss-Newton matrix w.r.t. domain parameters
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2032,6 +2033,215 @@ __global__ __launch_bounds__(64) void k_rollout_play(Task T, Dev d, Play P, int 
     if (TGT) P.loss[i] = acc;
 }
 
+// ------------------------------------------------------------------------ playback rollout with parameter sensitivities
+// vs_set_rollout_sens: k_rollout_play<E, false, 0, true> that also carries d(state, hidden state)/d(theta) for NP chosen domain
+// parameters theta from step to step (forward mode, vecsim_dual.h) and sums, next to the discrepancy, its gradient and the
+// Gauss-Newton matrix.  Same shape: one env per lane, one wave per workgroup, no LDS, no barrier, no auto-reset, no records.
+//   * Prologue: what k_rollout_play loads; the lane's raw parameters as Dual<NP>, tangent j seeded 1 on parameter idx[j] (-1: an
+//     unseeded column, all 0); E::calc_consts<Dual<NP>> on them, then every constant's VALUE replaced by the lane's stored float
+//     constant; the carried tangents from VS_ROLLOUT_SENS, the sums from VS_ROLLOUT_GRAD / VS_ROLLOUT_GN.
+//   * Step of a non-frozen lane: the float path is k_rollout_play's, statement for statement (state, hidden state, observation,
+//     reward, flags, counter and VS_ROLLOUT_LOSS are the same bits).  The tangent path takes the action that reaches the dynamics
+//     from float code (ActNorm map, clip: applied_action) with zero tangent, the pre-step float state / hidden state with their
+//     carried tangents, runs E::dynamics<Dual<NP>, Dual<NP>>, replaces the values by the float path's, and E::observe<Dual<NP>>.
+//     Where the loss sums the step, with e_q the float path's error, q = 0 .. O - 1 in order, j and l inner:
+//         grad[j] = fmaf(2 w[q] e_q, oD[q].d[j], grad[j]);   gn[j][l] = fmaf(w[q] oD[q].d[j], oD[q].d[l], gn[j][l])   (j <= l)
+//   * A frozen lane does nothing; the epilogue stores tangents and sums back, so launch cuts carry them on.
+// Every loop over tangents, state rows and constants is fully unrolled: a run-time index into a Dual array would send it to scratch.
+constexpr int SENS_MAXP = VS_SENS_MAX_PARAMS;
+struct Sens {
+    float* grad;  // VS_ROLLOUT_GRAD f32 [n][ld]
+    float* gn;    // VS_ROLLOUT_GN   f32 [n (n + 1) / 2][ld], upper triangle, row-major
+    float* sens;  // VS_ROLLOUT_SENS f32 [(S + H) * np][ld], row (state / hidden row) * np + tangent
+    int n;        // parameters asked for (0: off)
+    int np;       // tangents the kernel carries: 1, 2 or 4 (n = 3 runs 4 with an unseeded column)
+    int idx[SENS_MAXP];  // parameter index of tangent j, -1 for j >= n
+};
+
+template <class E, int NP>
+__global__ __launch_bounds__(64) void k_rollout_play_sens(Task T, Dev d, Play P, Sens Q, int k_steps) {
+    using D = Dual<NP>;
+    constexpr bool UNI = false;
+    constexpr int HN = E::H > 0 ? E::H : 1;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    const size_t nrl = (size_t)P.n_rec_ld;
+
+    // ---- env state of the lane (k_rollout_play's)
+    float c[E::K], s[E::S], h[HN], a[E::A], ob[E::O];
+    float alo[E::A], ahi[E::A];
+    int step = 0;
+    float ret = 0.f, rew = 0.f;
+    bool yielded = false, frozen = false, done = false, failed = false;
+    EpStat es{0u, 0u, 0.f, 0};
+    load_consts<E, UNI>(d, i, c, 0, E::KS);
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) s[j] = d.state[j * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) h[j] = d.hidden[j * ld + i];
+    step = d.step[i];
+    ret = d.ret[i];
+    yielded = E::FINAL != FINAL_NONE ? d.yielded[i] != 0 : false;
+    frozen = d.done[i] != 0;
+    rew = d.rew[i];
+    done = d.done[i] != 0, failed = d.failed[i] != 0;
+    es = EpStat{d.ep_idx[i], d.es_count[i], d.es_retsum[i], d.es_lensum[i]};
+    const unsigned r = P.lane_rec ? (unsigned)P.lane_rec[i] : (unsigned)(((uint64_t)d.idx0 + (uint64_t)i) % (uint64_t)P.n_rec);
+    const unsigned rl = (unsigned)P.rec_len[r];
+    const float* const act_r = P.act + r;
+    const float* const tgt_r = P.tgt + r;
+    float acc = P.loss[i];
+    // ---- the dual constants: _calc_constants on the seeded parameters, values from the lane's stored constants
+    D cD[E::K];
+    {
+        D pD[E::P];
+#pragma unroll
+        for (int k = 0; k < E::P; ++k) {
+            pD[k].v = d.params[(size_t)k * ld + i];
+#pragma unroll
+            for (int j = 0; j < NP; ++j) pD[k].d[j] = Q.idx[j] == k ? 1.f : 0.f;
+        }
+        E::template calc_consts<D>(T, pD, cD);
+#pragma unroll
+        for (int k = 0; k < E::KS; ++k) cD[k].v = c[k];
+    }
+    // ---- the carried tangents and sums
+    D sD[E::S], hD[HN];
+    float grad[NP], gn[NP][NP];
+#pragma unroll
+    for (int j = 0; j < E::S; ++j)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) sD[j].d[k] = Q.sens[((size_t)j * NP + k) * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) hD[j].d[k] = Q.sens[((size_t)(E::S + j) * NP + k) * ld + i];
+    const int nq = Q.n;  // (wave-uniform) rows of the sums: nq <= NP
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        grad[j] = j < nq ? Q.grad[(size_t)j * ld + i] : 0.f;
+#pragma unroll
+        for (int l = j; l < NP; ++l) gn[j][l] = l < nq ? Q.gn[(size_t)(j * nq - j * (j - 1) / 2 + (l - j)) * ld + i] : 0.f;
+    }
+    E::act_bounds(c, alo, ahi);
+    E::observe(s, ob);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // (see rollout_body: nothing pending at the loop header)
+
+    for (int t = 0; t < k_steps; ++t) {
+        // ---- the action of this lane's env: row `step` of its recording, 0 from rec_len on
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) a[j] = 0.f;
+        if (!frozen) {
+            const unsigned k = (unsigned)step;
+            const size_t row = (size_t)min(k, (unsigned)(P.t_len - 1));
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) {
+                const float v = act_r[(row * E::A + j) * nrl];
+                a[j] = k < rl ? v : 0.f;
+            }
+        }
+        const bool stepped = !frozen;
+        if (!frozen) {
+            // ---- tangent path, inputs: the pre-step values, the action as it reaches the dynamics
+            float a_app[E::A];
+            D aD[E::A];
+#pragma unroll
+            for (int j = 0; j < E::S; ++j) sD[j].v = s[j];
+#pragma unroll
+            for (int j = 0; j < E::H; ++j) hD[j].v = h[j];
+            {
+                // ActNormWrapper's map as in step_one, then the clip
+                const bool nrm = (T.flags & VS_FLAG_ACT_NORM) != 0;
+                float an[E::A];
+#pragma unroll
+                for (int j = 0; j < E::A; ++j) {
+                    float m = alo[j] + (a[j] + 1.0f) * (ahi[j] - alo[j]) * 0.5f;
+                    an[j] = nrm ? m : a[j];
+                }
+                E::limit_act(c, alo, ahi, an, a_app);
+            }
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) aD[j] = D(a_app[j]);
+            // ---- the env step: k_rollout_play's, statement for statement
+            StepOut o = step_one<E, float>(T, c, s, h, a, step, yielded,
+                                           E::TRIG > 0 ? (const float*)(ob + E::TRIG_AT) : (const float*)nullptr);
+            rew = o.rew;
+            done = o.done;
+            failed = o.failed;
+            ret += o.rew;
+            if (o.err && valid) d.err[i] = 1;
+            // ---- tangent path
+            E::template dynamics<D, D>(T, cD, sD, hD, aD, (const D*)nullptr);
+#pragma unroll
+            for (int j = 0; j < E::S; ++j) sD[j].v = s[j];
+#pragma unroll
+            for (int j = 0; j < E::H; ++j) hD[j].v = h[j];
+        } else {
+            rew = 0.f;
+        }
+        bool fin = done && valid && !frozen;
+        if (fin) {
+            es.count += 1u;
+            es.retsum += ret;
+            es.lensum += step;
+        }
+        if (d.log_episodes) append_episode(d, fin, i, ret, step);
+        frozen |= done;
+        E::observe(s, ob);
+        const unsigned k1 = (unsigned)step;
+        if (stepped && k1 <= rl) {
+            D oD[E::O];
+            E::observe(sD, oD);
+            const size_t row = (size_t)min(k1, (unsigned)P.t_len);
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) {
+                const float e = ob[q] - tgt_r[(row * E::O + q) * nrl];
+                acc = fmaf(P.w[q] * e, e, acc);
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {
+                    grad[j] = fmaf(2.0f * P.w[q] * e, oD[q].d[j], grad[j]);
+#pragma unroll
+                    for (int l = j; l < NP; ++l) gn[j][l] = fmaf(P.w[q] * oD[q].d[j], oD[q].d[l], gn[j][l]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) d.state[j * ld + i] = s[j];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) d.hidden[j * ld + i] = h[j];
+#pragma unroll
+    for (int j = 0; j < E::O; ++j) d.obs[j * ld + i] = ob[j];
+    d.step[i] = step;
+    d.ret[i] = ret;
+    d.rew[i] = rew;
+    d.done[i] = done;
+    d.failed[i] = failed;
+    if (E::FINAL != FINAL_NONE) d.yielded[i] = yielded;
+    d.ep_idx[i] = es.epi;
+    d.es_count[i] = es.count;
+    d.es_retsum[i] = es.retsum;
+    d.es_lensum[i] = es.lensum;
+    P.loss[i] = acc;
+#pragma unroll
+    for (int j = 0; j < E::S; ++j)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) Q.sens[((size_t)j * NP + k) * ld + i] = sD[j].d[k];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) Q.sens[((size_t)(E::S + j) * NP + k) * ld + i] = hD[j].d[k];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        if (j < nq) Q.grad[(size_t)j * ld + i] = grad[j];
+#pragma unroll
+        for (int l = j; l < NP; ++l)
+            if (l < nq) Q.gn[(size_t)(j * nq - j * (j - 1) / 2 + (l - j)) * ld + i] = gn[j][l];
+    }
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -3015,6 +3225,7 @@ struct vs_env {
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)
+    vs::Sens sens{};              // vs_set_rollout_sens: the sensitivity buffers and the chosen parameters (sens.n == 0: off)
     int hrec_width = 0;           // vs_set_policy_hidden_record: floats per env and step of the hidden-state record plane, 0 off
     float* d_hrec = nullptr;      // ... the plane, f32 [traj_cap][hrec_width][ld]
     int rollout_variant = -1;     // vs_set_rollout_variant: -1 automatic, 0 k_rollout, 1 k_rollout_ws<256>, 2 k_rollout_ws<64>, 3 / 4 the three-role kernel in 64 / 256-env workgroups
@@ -3059,6 +3270,7 @@ struct Launch {
     static void rollout_rnn(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... recurrent policy
     static void rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... linear policy on a feature stack
     static void rollout_play(vs_env* h, int k, int rec);                      // ... playback of recorded actions (+ discrepancy)
+    static void rollout_play_sens(vs_env* h, int k);                          // ... and its parameter sensitivities (vs_set_rollout_sens)
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -3312,6 +3524,17 @@ void Launch<E>::rollout_play(vs_env* h, int k, int rec) {
                                    h->play, k, h->ar_seed);
             else no_kernel("rollout_play");
         }, h->auto_reset, h->play.tgt != nullptr);
+    });
+}
+
+template <class E>
+void Launch<E>::rollout_play_sens(vs_env* h, int k) {
+    // the shape of rollout_play; NP = 1, 2 or 4 tangents (the C-ABI admits nothing else and no discrete-action family)
+    with_int<1, 2, 4>(h->sens.np, [&](auto NP) __attribute__((always_inline)) {
+        if constexpr (!std::is_same<E, BobD>::value)
+            hipLaunchKernelGGL((k_rollout_play_sens<E, NP>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, h->play,
+                               h->sens, k);
+        else no_kernel("rollout_play_sens");
     });
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from .exceptions import ShapeErr, ValueErr
+from .vec_env import expand_upper_triangle  # noqa: F401  (re-exported)
 from .wrappers import ActNormWrapper, EnvWrapper, all_envs, inner_env
 
 
@@ -67,6 +68,33 @@ class TrajectoryMatchResult:
     def mean_loss(self):
         """[P]: a candidate's summed loss over its segments divided by the steps it took"""
         return self.loss.sum(dim=1) / self.steps.sum(dim=1).clamp(min=1).to(self.loss.dtype)
+
+
+class TrajectoryMatchGradResult(TrajectoryMatchResult):
+    """loss [P, R] and steps [P, R] as TrajectoryMatchResult (the same bits as evaluate()); grad [P, R, G]: d loss / d wrt[j];
+    gn [P, R, G, G] or None: the Gauss-Newton matrix sum_k sum_d w_d J^T J, J = d obs_sim / d wrt (fp32, device); wrt: the names."""
+
+    def __init__(self, loss, steps, grad, gn, wrt):
+        super().__init__(loss, steps)
+        self.grad, self.gn, self.wrt = grad, gn, tuple(wrt)
+
+    def grad_per_candidate(self):
+        """[P, G]: summed over the segments"""
+        return self.grad.sum(dim=1)
+
+    def gn_per_candidate(self):
+        """[P, G, G]: summed over the segments"""
+        if self.gn is None:
+            raise ValueErr(msg="no Gauss-Newton matrix: evaluate_grad(..., gauss_newton=True)")
+        return self.gn.sum(dim=1)
+
+    def lm_step(self, damping: float = 1e-3):
+        """[P, G]: the Levenberg-Marquardt step delta of every candidate, (GN + damping diag GN) delta = -grad / 2"""
+        import torch
+
+        gn = self.gn_per_candidate()
+        lhs = gn + float(damping) * torch.diag_embed(torch.diagonal(gn, dim1=-2, dim2=-1))
+        return torch.linalg.solve(lhs, -0.5 * self.grad_per_candidate().unsqueeze(-1)).squeeze(-1)
 
 
 class TrajectoryMatchSampler:
@@ -161,21 +189,41 @@ class TrajectoryMatchSampler:
             mat[:, all_names.index(k)] = arr[:, c]
         return mat
 
-    def evaluate(self, domain_params, names: Optional[Sequence[str]] = None) -> TrajectoryMatchResult:
-        """The discrepancy of every (candidate, segment) pair.  domain_params: a list of P dicts (names missing from a dict
-        keep the env's value), or a [P, n_names] array with names=."""
+    def _check_wrt(self, wrt, gauss_newton: bool) -> List[str]:
+        """the validated list of parameter names to differentiate with respect to (needs no device)"""
+        from .vec_env import param_names
+
+        all_names = param_names(self._base.name)
+        wrt = [wrt] if isinstance(wrt, str) else list(wrt)
+        if len(wrt) < 1:
+            raise ValueErr(msg="evaluate_grad: wrt names at least one domain parameter")
+        for k in wrt:
+            if k not in all_names:
+                raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {self._base.name}")
+        if len(set(wrt)) != len(wrt):
+            raise ValueErr(msg=f"evaluate_grad: a name is repeated in wrt={tuple(wrt)}")
+        if gauss_newton and len(wrt) > L.VS_SENS_MAX_PARAMS:
+            raise ValueErr(msg=f"evaluate_grad: more than {L.VS_SENS_MAX_PARAMS} parameters run in several passes, which leaves the "
+                               "cross blocks of the Gauss-Newton matrix out: pass gauss_newton=False")
+        return wrt
+
+    def _run(self, mat, sens=None, gauss_newton=False):
+        """The launch loop of evaluate() and evaluate_grad(): per batch of whole candidates set the parameters, reset to the
+        segments' states, replay.  sens: the names of one pass of sensitivities, or None for the plain kernel.
+        Returns (losses, steps, grads, gns): lists with one entry per batch (grads / gns empty without sens / gauss_newton)."""
         import torch
 
-        mat = self.param_matrix(domain_params, names)
         P, R = mat.shape[0], self.num_segments
         t_max = int(self._len.max())
-        losses, steps = [], []
+        losses, steps, grads, gns = [], [], [], []
         for p0, p1 in candidate_batches(P, R, self._batch_lanes):
             nc = p1 - p0
             n = nc * R
             v = self._vec_for(n)
             v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
             try:
+                if sens or getattr(v, "_sens_n", 0):
+                    v.set_rollout_sens(sens)                         # (evaluate(): the plain kernel, no extra call)
                 v.set_params(np.repeat(mat[p0:p1], R, axis=0))      # lane p * R + r: candidate p
                 v.reset(init_state=np.tile(self._init, (nc, 1)))     # ... from segment r's recorded state (zeroes the sums)
                 done_t = v.tensor(L.VS_DONE)[0, :n]
@@ -189,9 +237,53 @@ class TrajectoryMatchSampler:
                 lens = torch.as_tensor(np.tile(self._len, nc).astype(np.int64), device=done_t.device)
                 losses.append(v.rollout_loss().clone().reshape(nc, R))
                 steps.append(torch.minimum(v.tensor(L.VS_STEPCOUNT)[0, :n].to(torch.int64), lens).reshape(nc, R))
+                if sens:
+                    grads.append(v.rollout_grad().clone().reshape(nc, R, len(sens)))
+                    if gauss_newton:
+                        gns.append(v.rollout_gn().reshape(nc, R, len(sens), len(sens)))
             finally:
+                if sens:
+                    v.set_rollout_sens(None)
                 v.use_stream(None)
+        return losses, steps, grads, gns
+
+    def evaluate(self, domain_params, names: Optional[Sequence[str]] = None) -> TrajectoryMatchResult:
+        """The discrepancy of every (candidate, segment) pair.  domain_params: a list of P dicts (names missing from a dict
+        keep the env's value), or a [P, n_names] array with names=."""
+        import torch
+
+        mat = self.param_matrix(domain_params, names)
+        R = self.num_segments
+        losses, steps, _, _ = self._run(mat)
         if not losses:
             dev = f"cuda:{self._base._ctor.get('device', 0)}"
             return TrajectoryMatchResult(torch.zeros(0, R, device=dev), torch.zeros(0, R, dtype=torch.int64, device=dev))
         return TrajectoryMatchResult(torch.cat(losses), torch.cat(steps))
+
+    def evaluate_grad(self, domain_params, names: Optional[Sequence[str]] = None, wrt: Sequence[str] = (),
+                      gauss_newton: bool = True) -> TrajectoryMatchGradResult:
+        """evaluate() together with the gradient of every pair's discrepancy with respect to the domain parameters named in wrt
+        and, with gauss_newton, its Gauss-Newton matrix -- computed inside the rollout kernel by forward-mode sensitivities
+        (vs_set_rollout_sens).  Up to VS_SENS_MAX_PARAMS names run in one pass; more run in passes of that many, with
+        gauss_newton=False only."""
+        import torch
+
+        wrt = self._check_wrt(wrt, gauss_newton)
+        mat = self.param_matrix(domain_params, names)
+        R, G = self.num_segments, len(wrt)
+        loss = step = None
+        grad_cols, gn = [], None
+        for g0 in range(0, G, L.VS_SENS_MAX_PARAMS):
+            part = wrt[g0: g0 + L.VS_SENS_MAX_PARAMS]
+            losses, steps, grads, gns = self._run(mat, sens=part, gauss_newton=gauss_newton)
+            if not losses:
+                dev = f"cuda:{self._base._ctor.get('device', 0)}"
+                return TrajectoryMatchGradResult(torch.zeros(0, R, device=dev), torch.zeros(0, R, dtype=torch.int64, device=dev),
+                                                 torch.zeros(0, R, G, device=dev),
+                                                 torch.zeros(0, R, G, G, device=dev) if gauss_newton else None, wrt)
+            if loss is None:
+                loss, step = torch.cat(losses), torch.cat(steps)
+            grad_cols.append(torch.cat(grads))
+            if gauss_newton:
+                gn = torch.cat(gns)
+        return TrajectoryMatchGradResult(loss, step, torch.cat(grad_cols, dim=2), gn, wrt)

@@ -54,6 +54,19 @@ def nominal_params(name, long=False):
     return np.array(out[:], dtype=np.float32)
 
 
+def expand_upper_triangle(tri, g):
+    """[..., g (g + 1) / 2] (upper triangle, row-major) -> [..., g, g] symmetric; a torch tensor, on the device it lives on"""
+    import torch
+
+    if tri.shape[-1] != g * (g + 1) // 2:
+        raise ShapeErr(msg=f"an upper triangle of a {g} x {g} matrix has {g * (g + 1) // 2} entries, got {tri.shape[-1]}")
+    rows, cols = torch.triu_indices(g, g, device=tri.device)
+    full = tri.new_zeros(tuple(tri.shape[:-1]) + (g, g))
+    full[..., rows, cols] = tri
+    full[..., cols, rows] = tri
+    return full
+
+
 class VecSimEnv:
     """N environments of one Pyrado pysim family on one GPU."""
 
@@ -721,6 +734,40 @@ class VecSimEnv:
             raise ValueErr(msg="no rollout target set (set_rollout_target)")
         return torch.as_tensor(_DevArray(ptr, (self.ld,), "<f4", self), device=f"cuda:{self.device}")[: self.n_envs]
 
+    def set_rollout_sens(self, params=None):
+        """Sensitivities of the trajectory discrepancy (vs_set_rollout_sens): params is a sequence of up to VS_SENS_MAX_PARAMS
+        distinct domain-parameter names or indices; step_policy then also sums rollout_grad() and rollout_gn().  Needs a playback
+        policy and a rollout target, auto-reset off and no wrapper pipeline.  None or an empty sequence turns them off."""
+        idx = []
+        for k in ([] if params is None else ([params] if isinstance(params, (str, int, np.integer)) else list(params))):
+            if isinstance(k, str):
+                if k not in self.param_names:
+                    raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {self.name}")
+                k = self.param_names.index(k)
+            idx.append(int(k))
+        arr = np.ascontiguousarray(np.asarray(idx, dtype=np.int32))
+        rc = self._lib.vs_set_rollout_sens(self._h, arr.ctypes.data_as(C.c_void_p) if idx else None, len(idx))
+        self._check(rc, "vs_set_rollout_sens")
+        self._sens_n = len(idx)
+
+    def _sens_view(self, which, rows):
+        import torch
+
+        ptr = self._lib.vs_get(self._h, which)
+        if not ptr or not rows:
+            raise ValueErr(msg="sensitivities are off (set_rollout_sens)")
+        return torch.as_tensor(_DevArray(ptr, (rows, self.ld), "<f4", self), device=f"cuda:{self.device}")[:, : self.n_envs]
+
+    def rollout_grad(self):
+        """[n_envs, G] device tensor: d rollout_loss / d (parameter j of set_rollout_sens) (a transposed view of VS_ROLLOUT_GRAD)"""
+        return self._sens_view(L.VS_ROLLOUT_GRAD, getattr(self, "_sens_n", 0)).t()
+
+    def rollout_gn(self):
+        """[n_envs, G, G] symmetric device tensor: the Gauss-Newton matrix sum w J^T J, expanded on the device from the upper
+        triangle VS_ROLLOUT_GN holds"""
+        g = getattr(self, "_sens_n", 0)
+        return expand_upper_triangle(self._sens_view(L.VS_ROLLOUT_GN, g * (g + 1) // 2).t(), g)
+
     def set_policy_population(self, params, lane_set=None):
         """A population of parameter vectors for step_policy (vs_set_policy_population): params [P, n_params] -- P vectors of the
         policy of the last set_policy_fnn / set_policy_rnn / set_policy_linear, each in that call's torch order; a torch tensor (host or device) or
@@ -808,6 +855,11 @@ class VecSimEnv:
 
     # ------------------------------------------------------------------------------------------------ data access
     def _rows(self, which):
+        if which in (L.VS_ROLLOUT_GRAD, L.VS_ROLLOUT_GN, L.VS_ROLLOUT_SENS):  # sized by set_rollout_sens
+            g = getattr(self, "_sens_n", 0)
+            np_ = g if g <= 2 else 4
+            return np.dtype("f4"), {L.VS_ROLLOUT_GRAD: g, L.VS_ROLLOUT_GN: g * (g + 1) // 2,
+                                    L.VS_ROLLOUT_SENS: (self.dims["S"] + self.dims["H"]) * np_}[which]
         dt, rows = _BUF_DTYPES[which]
         return np.dtype(dt), (self.dims[rows] if isinstance(rows, str) else rows)
 
@@ -819,7 +871,7 @@ class VecSimEnv:
         buf = np.empty((rows, self.ld), dtype=dt)
         self._check(self._lib.vs_copy_to_host(self._h, which, buf.ctypes.data_as(C.c_void_p)), "vs_copy_to_host")
         out = buf[:, : self.n_envs]
-        if isinstance(_BUF_DTYPES[which][1], int):
+        if which in _BUF_DTYPES and isinstance(_BUF_DTYPES[which][1], int):
             return out[0].copy()
         return np.ascontiguousarray(out.T)
 
