@@ -431,6 +431,37 @@ int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t
  * auto-reset on, a wrapper pipeline on the handle, the discrete-action family (VS_ERR_STATE). */
 #define VS_SENS_MAX_PARAMS 4
 int vs_set_rollout_sens(vs_handle h, const int32_t* param_idx, int n_params);
+/* Reverse-mode gradients through recorded rollouts: the vector-Jacobian product of rows 0 .. t_steps - 1 of VS_TRAJ_REC (record mode
+ * 2: row t holds the state s_t, the hidden state h_t and the raw action a_t before step t) with respect to every action and the
+ * initial state, in one backward sweep -- what a T-step shooting method, an initial-state estimate or any loss written over the
+ * observations and rewards of a rollout needs of the simulator.  (vs_step_jac has the one-step Jacobians, with the hidden state
+ * held constant; vs_set_rollout_sens the forward form for domain parameters.)  The records may come from any recording path with
+ * auto-reset off, started at a reset: vs_step_policy, vs_step_random or vs_step_record.  All pointers are device f32 owned by the
+ * caller, ld = vs_ld(h); the call runs on the handle's stream and writes nothing but d_act and d_init: no state, reward or flag,
+ * the handle's running state is untouched.
+ *   g_rew         [t_steps][ld]         cotangent of the reward of step t; NULL: 0
+ *   g_obs         [t_steps + 1][O][ld]  cotangent of the observation after k steps, row k (row 0: the initial observation); NULL: 0
+ *   g_state_last  [S + H][ld]           cotangent of the state and hidden state after the lane's last step; NULL: 0
+ *   d_act         [t_steps][A][ld]      out: d Phi / d a_t
+ *   d_init        [S + H][ld]           out: d Phi / d (s_0, h_0)
+ * with Phi = sum_t g_rew[t] r_t + sum_k g_obs[k] . obs_k + g_state_last . (s_L, h_L) per lane.  The lane's length is
+ * L = min(t_steps, 1 + first row whose VS_TRAJ_DONE bit is set); lanes >= n_envs have L = 0 and get zeros.  lambda [S + H] starts as
+ * g_state_last; for t = L - 1 .. 0 the step code itself (step_one and observe on dual numbers: step counter t, the final reward not
+ * yet paid, the lane's stored constants) is differentiated at x = (s_t, h_t, a_t) and, for every column k of x, in fp32 in this order
+ *     acc = 0;  for j < S: acc = fmaf(lambda[j], d s'_j / d x_k, acc);  for j < H: acc = fmaf(lambda[S + j], d h'_j / d x_k, acc);
+ *     acc = fmaf(g_rew[t], d r / d x_k, acc);  for q < O: acc = fmaf(g_obs[t + 1][q], d obs'_q / d x_k, acc)
+ * The columns of (s, h) are the new lambda, those of a are d_act[t].  After t = 0, lambda[k] = fmaf(g_obs[0][q], d observe(s_0)_q /
+ * d s_k, lambda[k]) for q < O, and d_init = lambda.  Rows t >= L of d_act are written 0; cotangent rows behind a lane's end are not
+ * read (g_obs rows 0 .. L, g_rew rows 0 .. L - 1 are).
+ * Conventions, as for vs_step_jac and vs_set_rollout_sens: the raw action is the differentiation variable -- ActNormWrapper's map,
+ * the clip and the dead zone are inside the step and kinks follow the branch taken, so nothing reaches the dynamics through a
+ * clipped action (the reward's action cost is a function of the unclipped action and keeps its term); domain parameters and the
+ * bounds of the spaces are constants.  Unlike vs_step_jac the hidden state (qcp: th_ddot, qbb: plate angles) is part of the adjoint.
+ * Refused with nothing written: NULL handle, d_act or d_init, t_steps < 1 or beyond vs_set_traj_capacity (VS_ERR_ARG); record mode
+ * other than 2, auto-reset on, a wrapper pipeline on the handle, a trajectory offset other than 0 (vs_set_traj_offset), the
+ * discrete-action family (VS_ERR_STATE). */
+int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
+                   float* d_init);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

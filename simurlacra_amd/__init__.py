@@ -17,7 +17,7 @@ from .envs import (ENV_CLASSES, BallOnBeamDiscSim, BallOnBeamSim, OneMassOscilla
 from .exceptions import KeyErr, ShapeErr, TypeErr, ValueErr  # noqa: F401
 from .seeding import derive_seed, get_base_seed, set_seed  # noqa: F401
 from .spaces import BoxSpace, CompoundSpace, DiscreteSpace, EnvSpec, Polar2DPosVelSpace, SingularStateSpace  # noqa: F401
-from .vec_env import MixedVecSimEnv, VecSimEnv, env_dims, nominal_params, param_names  # noqa: F401
+from .vec_env import MixedVecSimEnv, VecSimEnv, env_dims, lanes_first, lanes_last, nominal_params, param_names  # noqa: F401
 from .wrappers import (ActDelayWrapper, ActNormWrapper, DomainRandWrapper, DomainRandWrapperBuffer,  # noqa: F401
                        DomainRandWrapperLive, EnvWrapper, EnvWrapperAct, EnvWrapperObs, FusedChain,
                        GaussianActNoiseWrapper, GaussianObsNoiseWrapper, ObsNormWrapper, ObsPartialWrapper, all_envs,
@@ -46,6 +46,10 @@ def __getattr__(name):
         from . import sysid
 
         return getattr(sysid, name)
+    if name in ("DifferentiableRollout", "discounted_return"):
+        from . import diffsim
+
+        return getattr(diffsim, name)
     if name in ("FeatureStack", "MultFeat", "ATan2Feat", "const_feat", "identity_feat", "sign_feat", "abs_feat", "squared_feat",
                 "cubic_feat", "sig_feat", "bell_feat", "sin_feat", "cos_feat", "sinsin_feat", "sincos_feat"):
         from . import features

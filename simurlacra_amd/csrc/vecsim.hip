@@ -500,7 +500,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 extern "C" {
 
-int vs_version(void) { return 309; }
+int vs_version(void) { return 310; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1738,6 +1738,25 @@ int vs_pack_traj(vs_handle h, int n_lanes, int t_steps, const int64_t* lengths, 
     if (((uintptr_t)rows & 3u) != 0) return fail(h, VS_ERR_ARG, "vs_pack_traj: the destination must be 4-byte aligned");
     HIPCHK(h, hipSetDevice(h->device));
     DISPATCH_ENV(h->type, Launch<E>::pack_traj(h, n_lanes, t_steps, (const long long*)lengths, (const long long*)starts, rows));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
+                   float* d_init) {
+    // every refusal comes before the first device call and leaves the outputs untouched
+    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, "vs_rollout_vjp: NULL handle or output");
+    if (t_steps < 1) return fail(h, VS_ERR_ARG, "vs_rollout_vjp: t_steps < 1");
+    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: the discrete-action family has no action gradient");
+    if (h->record_mode != 2) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: needs the records of record mode 2 (vs_set_record_mode)");
+    if (h->auto_reset) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: switch auto-reset off (one rollout per lane, started at a reset)");
+    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: not available with a wrapper pipeline on the handle");
+    if (h->d.traj_t0 != 0) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: set the trajectory offset back to 0 (the sweep reads rows 0 .. t_steps - 1)");
+    if (t_steps > h->traj_cap || !h->d.traj_rec || !h->d.traj_done)
+        return fail(h, VS_ERR_ARG, "vs_rollout_vjp: t_steps exceeds vs_set_traj_capacity");
+    HIPCHK(h, hipSetDevice(h->device));
+    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
+    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp(h, v, t_steps));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

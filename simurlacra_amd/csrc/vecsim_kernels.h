@@ -13,6 +13,7 @@
 //   k_*_mixed       vs_mixed_*        several families in one launch (one workgroup = one family)
 //   k_step_jac      vs_step_jac       step + Jacobians by forward-mode dual numbers
 //   k_rollout_play_sens  vs_step_policy   playback rollout + discrepancy with its gradient and Gauss-Newton matrix w.r.t. domain parameters
+//   k_rollout_vjp   vs_rollout_vjp    reverse-mode sweep over a recorded rollout: gradients w.r.t. its actions and initial state
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2242,6 +2243,169 @@ __global__ __launch_bounds__(64) void k_rollout_play_sens(Task T, Dev d, Play P,
     }
 }
 
+// ------------------------------------------------------------------------------- reverse-mode sweep over recorded rollouts
+// vs_rollout_vjp: the vector-Jacobian product of a recorded rollout with respect to its actions and its initial state, one backward
+// sweep over rows 0 .. t_steps - 1 of VS_TRAJ_REC in record mode 2 (row t: state s_t, hidden state h_t and raw action a_t before
+// step t).  Shape of k_rollout_play_sens: one env per lane, one wave per workgroup, no LDS, no barrier.  Nothing of the handle is
+// written: no state, reward, flag or counter.
+//   * The lane's length L = min(t_steps, 1 + first row whose VS_TRAJ_DONE bit is set); a lane >= n has L = 0.
+//   * lambda [S + H] starts as g_state_last (0 for a NULL pointer).  For t = L - 1 .. 0 the lane loads x = (s_t, h_t, a_t) -- only the
+//     planes of the row that hold one of them, each read contiguously by the wave --, runs step_one<E, Dual<S + H + A>> and
+//     E::observe<Dual<S + H + A>> with step counter t, yielded = false, the lane's constants as float and tangent k seeded on x[k], and forms,
+//     for every input column k, in fp32 and in this order (acc = 0 first)
+//         for j < S: acc = fmaf(lambda[j], s'[j].d[k], acc);   for j < H: acc = fmaf(lambda[S + j], h'[j].d[k], acc);
+//         acc = fmaf(g_rew[t], r.d[k], acc);                   for q < O: acc = fmaf(g_obs[t + 1][q], obs'[q].d[k], acc)
+//     Columns k < S + H are the new lambda, the others d_act[t].  Rows t >= L of d_act are written 0 and read no cotangent.
+//   * After t = 0:  lambda[k] = fmaf(g_obs[0][q], d observe(s_0)[q] / d s_k, lambda[k]) for q < O in order;  d_init = lambda.
+//   * All S + H + A tangents are carried at once (ball balancer 12, cartpole 6): no instantiation spills, the widest is the
+//     cartpole's at 217 VGPRs (profiles/rollout_vjp_kernels.txt).
+// The raw action is the variable (ActNorm map, clip and dead zone are inside step_one; a clipped action reaches the dynamics with a
+// zero tangent), domain parameters and space bounds are constants, and -- unlike k_step_jac -- the hidden state is part of x.
+struct Vjp {
+    const float* g_rew;   // [t_steps][ld] or nullptr
+    const float* g_obs;   // [t_steps + 1][O][ld] or nullptr
+    const float* g_last;  // [S + H][ld] or nullptr
+    float* d_act;         // [t_steps][A][ld]
+    float* d_init;        // [S + H][ld]
+};
+
+// x = (s, h, a_raw) of one record row in mode 2
+template <class E>
+__device__ __forceinline__ void load_record_inputs(const float* row, size_t ld, int i, float* x) {
+    constexpr int F = Rec<E, 2>::F, B = E::O + E::A + 1;
+    using PL = Planes<F>;
+    auto needed = [](int col) constexpr { return (col >= E::O && col < E::O + E::A) || (col >= B && col < B + E::S) || col >= B + E::S + E::A; };
+    float v[F];
+#pragma unroll
+    for (int j = 0; j < F; ++j) v[j] = 0.f;
+#pragma unroll
+    for (int q = 0; q < PL::NQ; ++q)
+        if (needed(4 * q) || needed(4 * q + 1) || needed(4 * q + 2) || needed(4 * q + 3)) {
+            float4 w = reinterpret_cast<const float4*>(row + (size_t)q * 4 * ld)[i];
+            v[4 * q] = w.x, v[4 * q + 1] = w.y, v[4 * q + 2] = w.z, v[4 * q + 3] = w.w;
+        }
+    if (PL::H2 && (needed(4 * PL::NQ) || needed(4 * PL::NQ + 1))) {
+        float2 w = reinterpret_cast<const float2*>(row + (size_t)PL::NQ * 4 * ld)[i];
+        v[4 * PL::NQ] = w.x, v[4 * PL::NQ + 1] = w.y;
+    }
+    if (PL::H1 && needed(F - 1)) v[F - 1] = row[((size_t)PL::NQ * 4 + PL::H2 * 2) * ld + i];
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) x[j] = v[B + j];
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) x[E::S + j] = v[B + E::S + E::A + j];
+#pragma unroll
+    for (int j = 0; j < E::A; ++j) x[E::S + E::H + j] = v[E::O + j];
+}
+
+// out[k] = column k of J_t^T (lambda, g_rew, g_obs), k < S + H + A
+template <class E>
+__device__ __forceinline__ void vjp_step(const Task& T, const float* c, const float* x, int t, const float* lam, float grew,
+                                         const float* gob, float* out) {
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    using D = Dual<NI>;
+    D s[E::S], h[E::H > 0 ? E::H : 1], a[E::A], ob[E::O];
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) {
+        s[j] = D(x[j]);
+        s[j].d[j] = 1.f;
+    }
+#pragma unroll
+    for (int j = 0; j < E::H; ++j) {
+        h[j] = D(x[E::S + j]);
+        h[j].d[E::S + j] = 1.f;
+    }
+#pragma unroll
+    for (int j = 0; j < E::A; ++j) {
+        a[j] = D(x[NS + j]);
+        a[j].d[NS + j] = 1.f;
+    }
+    int step = t;
+    bool yielded = false;
+    StepOutT<D> o = step_one<E, D>(T, c, s, h, a, step, yielded, (const D*)nullptr);
+    E::observe(s, ob);
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < E::S; ++j) acc = fmaf(lam[j], s[j].d[k], acc);
+#pragma unroll
+        for (int j = 0; j < E::H; ++j) acc = fmaf(lam[E::S + j], h[j].d[k], acc);
+        acc = fmaf(grew, o.rew.d[k], acc);
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) acc = fmaf(gob[q], ob[q].d[k], acc);
+        out[k] = acc;
+    }
+}
+
+// lam[k] += (d observe(s)[q] / d s_k) gob[q], k < S
+template <class E>
+__device__ __forceinline__ void vjp_observe(const float* x, const float* gob, float* lam) {
+    using D = Dual<E::S>;
+    D s[E::S], ob[E::O];
+#pragma unroll
+    for (int j = 0; j < E::S; ++j) {
+        s[j] = D(x[j]);
+        s[j].d[j] = 1.f;
+    }
+    E::observe(s, ob);
+#pragma unroll
+    for (int k = 0; k < E::S; ++k)
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) lam[k] = fmaf(gob[q], ob[q].d[k], lam[k]);
+}
+
+template <class E>
+__global__ __launch_bounds__(64) void k_rollout_vjp(Task T, Dev d, Vjp V, int t_steps) {
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    float c[E::K];
+    load_consts<E, false>(d, i, c, 0, E::KS);
+    // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (bits behind t_steps may be stale)
+    int L = 0;
+    if (valid) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = d.traj_done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    float lam[NS], x[NI], out[NI], gob[E::O];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = (valid && V.g_last) ? V.g_last[(size_t)k * ld + i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = 0.f;
+
+    for (int t = t_steps - 1; t >= 0; --t) {
+#pragma unroll
+        for (int k = 0; k < NI; ++k) out[k] = 0.f;
+        if (t < L) {
+            load_record_inputs<E>(d.traj_rec + (size_t)t * Rec<E, 2>::F * ld, ld, i, x);
+            const float grew = V.g_rew ? V.g_rew[(size_t)t * ld + i] : 0.f;
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) gob[q] = V.g_obs ? V.g_obs[((size_t)(t + 1) * E::O + q) * ld + i] : 0.f;
+            vjp_step<E>(T, c, x, t, lam, grew, gob, out);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) lam[k] = out[k];
+        }
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = out[NS + j];
+    }
+    if (L > 0) {  // x is row 0 here: every lane with a rollout ran t = 0 last
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) gob[q] = V.g_obs ? V.g_obs[(size_t)q * ld + i] : 0.f;
+        vjp_observe<E>(x, gob, lam);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -3271,6 +3435,7 @@ struct Launch {
     static void rollout_lin(vs_env* h, int k, int rec, uint64_t noise_seed);  // ... linear policy on a feature stack
     static void rollout_play(vs_env* h, int k, int rec);                      // ... playback of recorded actions (+ discrepancy)
     static void rollout_play_sens(vs_env* h, int k);                          // ... and its parameter sensitivities (vs_set_rollout_sens)
+    static void rollout_vjp(vs_env* h, const Vjp& v, int t_steps);            // vs_rollout_vjp
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -3536,6 +3701,14 @@ void Launch<E>::rollout_play_sens(vs_env* h, int k) {
                                h->sens, k);
         else no_kernel("rollout_play_sens");
     });
+}
+
+template <class E>
+void Launch<E>::rollout_vjp(vs_env* h, const Vjp& v, int t_steps) {
+    // the shape of rollout_play; the C-ABI admits no discrete-action family
+    if constexpr (!std::is_same<E, BobD>::value)
+        hipLaunchKernelGGL((k_rollout_vjp<E>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, t_steps);
+    else no_kernel("rollout_vjp");
 }
 
 template <class E>

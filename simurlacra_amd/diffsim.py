@@ -1,0 +1,174 @@
+"""
+Differentiable playback rollouts: a batch of open-loop rollouts whose observations and rewards are attached to torch autograd.
+
+The forward pass is the recording playback launch the library already has (vs_set_policy_playback, record mode 2, one launch of T
+steps); the backward pass is ONE reverse-mode sweep over those records (vs_rollout_vjp, k_rollout_vjp) that turns the incoming
+gradients of the observations and rewards into gradients of the actions and of the initial states.  What it serves: shooting
+trajectory optimisation on the return, initial-state estimation next to the parameter identification of sysid.py, and any loss
+written in torch over the observations and rewards of a rollout.
+
+Conventions are those of the kernel: the raw action is the variable (ActNormWrapper's map, the clip and the dead zone are inside
+the step, kinks follow the branch taken), domain parameters and the initial hidden state are constants.
+"""
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib as L
+from .exceptions import ShapeErr, TypeErr, ValueErr
+from .sysid import check_playback_env, domain_param_matrix, vec_env_like
+from .vec_env import lanes_first, lanes_last
+
+
+def discounted_return(rew, lengths, gamma: float):
+    """[N]: sum over t < lengths[n] of gamma^t rew[n, t]; rew [N, T], lengths [N] (torch tensors on one device).  The gradient of
+    its sum with respect to rew[n, t] is the float32 value gamma^t inside a rollout and 0 behind its end."""
+    if rew.dim() != 2 or tuple(lengths.shape) != (rew.shape[0],):
+        raise ShapeErr(msg=f"rew [N, T] and lengths [N], got {tuple(rew.shape)} and {tuple(lengths.shape)}")
+    if not 0.0 <= float(gamma) <= 1.0:
+        raise ValueErr(given=gamma, ge_constraint="0", le_constraint="1")
+    steps = torch.arange(rew.shape[1], device=rew.device)
+    disc = torch.pow(torch.tensor(float(gamma), dtype=rew.dtype, device=rew.device), steps.to(rew.dtype))
+    inside = (steps[None, :] < lengths[:, None]).to(rew.dtype)
+    return (rew * (disc[None, :] * inside)).sum(dim=1)
+
+
+class DifferentiableRollout:
+    """rollout = DifferentiableRollout(env);  obs, rew, lengths = rollout(actions, init_states, domain_params=None)
+
+    env: one of the pysim envs, optionally inside an ActNormWrapper (the actions are then in [-1, 1] units); any other wrapper and
+    the discrete-action family raise ValueErr.  actions [N, T, A] and init_states [N, S] (the FULL state every rollout starts
+    from) are float32 tensors on the env's device.  Returns obs [N, T + 1, O] (row k: the observation after k steps), rew [N, T]
+    and lengths [N] (int64: the steps a rollout took before its episode ended); rows behind a rollout's end are 0.  obs and rew
+    carry gradients to actions and init_states; domain_params -- a list of N dicts or an [N, n_names] array with names=, as for
+    TrajectoryMatchSampler.param_matrix; None: the env's own -- gets none.  More than batch_lanes rollouts run in batches."""
+
+    def __init__(self, env, batch_lanes: int = 65536):
+        self._base, self._act_norm = check_playback_env(env, "DifferentiableRollout")
+        if batch_lanes < 1:
+            raise ValueErr(given=batch_lanes, ge_constraint="1")
+        self.env = env
+        self._batch_lanes = int(batch_lanes)
+        self._vecs = {}  # batch index -> [handle, token of the rollouts its records hold]
+        self._calls = 0
+
+    def close(self):
+        for v, _ in self._vecs.values():
+            v.close()
+        self._vecs = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dims(self):
+        b = self._base
+        return b.act_space.flat_dim, b.state_space.flat_dim, b.obs_space.flat_dim
+
+    def _record(self, b, token, actions, init_states, params):
+        """the recording playback launch of one batch on its handle; a handle that still holds these records is left alone"""
+        n, T = actions.shape[0], actions.shape[1]
+        slot = self._vecs.get(b)
+        if slot is not None and slot[0].n_envs != n:
+            slot[0].close()
+            slot = None
+        if slot is None:
+            v = vec_env_like(self._base, n, self._act_norm)
+            v.set_record_mode(2)
+            slot = self._vecs[b] = [v, None]
+        v = slot[0]
+        if slot[1] == token:
+            return v
+        v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+        try:
+            v.set_params(params)
+            v.set_policy_playback(actions)                          # one recording per lane: lane i replays recording i
+            v.reset(init_state=init_states.detach().cpu().numpy())
+            v.set_traj_offset(0)
+            v.step_policy(T, record=True)
+        finally:
+            v.use_stream(None)
+        slot[1] = token
+        return v
+
+    def __call__(self, actions, init_states, domain_params=None, names: Optional[Sequence[str]] = None):
+        A, S, _ = self._dims()
+        if not hasattr(actions, "dim") or not hasattr(init_states, "dim"):
+            raise TypeErr(msg="actions and init_states must be torch tensors")
+        if actions.dim() != 3 or actions.shape[2] != A or actions.shape[0] < 1 or actions.shape[1] < 1:
+            raise ShapeErr(msg=f"actions must be [N, T, {A}], got shape {tuple(actions.shape)}")
+        if tuple(init_states.shape) != (actions.shape[0], S):
+            raise ShapeErr(msg=f"init_states must be [{actions.shape[0]}, {S}], got shape {tuple(init_states.shape)}")
+        N = actions.shape[0]
+        params = domain_param_matrix(self._base, [dict()] * N if domain_params is None else domain_params, names)
+        if params.shape[0] != N:
+            raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
+        for name, x in (("actions", actions), ("init_states", init_states)):
+            if not x.is_cuda or x.dtype != torch.float32:
+                raise TypeErr(msg=f"{name} must be a float32 tensor on the GPU")
+        self._calls += 1
+        obs, rew, lengths = _RolloutFn.apply(self, self._calls, params, actions, init_states)
+        return obs, rew, lengths
+
+    def _batches(self, N):
+        return [(n0, min(n0 + self._batch_lanes, N)) for n0 in range(0, N, self._batch_lanes)]
+
+    def _forward(self, call, params, actions, init_states):
+        A, S, O = self._dims()
+        N, T = actions.shape[0], actions.shape[1]
+        obs = torch.empty(N, T + 1, O, dtype=torch.float32, device=actions.device)
+        rew = torch.empty(N, T, dtype=torch.float32, device=actions.device)
+        lengths = torch.empty(N, dtype=torch.int64, device=actions.device)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, (call, b), actions[n0:n1].contiguous(), init_states[n0:n1], params[n0:n1])
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                tt = v.traj_tensors(T, n)
+                lengths[n0:n1] = v.rollout_lengths(n, T)[0]
+                obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
+                obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
+                rew[n0:n1] = tt["rew"].t()
+            finally:
+                v.use_stream(None)
+        steps = torch.arange(T + 1, device=actions.device)
+        obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
+        rew = rew * (steps[None, :T] < lengths[:, None]).to(rew.dtype)
+        return obs, rew, lengths
+
+    def _backward(self, call, params, actions, init_states, grad_obs, grad_rew):
+        A, S, O = self._dims()
+        N, T = actions.shape[0], actions.shape[1]
+        d_act = torch.empty(N, T, A, dtype=torch.float32, device=actions.device)
+        d_init = torch.empty(N, S, dtype=torch.float32, device=actions.device)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, (call, b), actions[n0:n1].contiguous(), init_states[n0:n1], params[n0:n1])
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                g_rew = None if grad_rew is None else lanes_last(grad_rew[n0:n1].to(torch.float32), v.ld)
+                g_obs = None if grad_obs is None else lanes_last(grad_obs[n0:n1].to(torch.float32), v.ld)
+                da, di = v.rollout_vjp(T, g_rew=g_rew, g_obs=g_obs)
+                d_act[n0:n1] = lanes_first(da, n)
+                d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
+            finally:
+                v.use_stream(None)
+        return d_act, d_init
+
+
+class _RolloutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, roll, call, params, actions, init_states):
+        obs, rew, lengths = roll._forward(call, params, actions.detach(), init_states.detach())
+        ctx.roll, ctx.call, ctx.params = roll, call, params
+        ctx.save_for_backward(actions, init_states)
+        ctx.mark_non_differentiable(lengths)
+        return obs, rew, lengths
+
+    @staticmethod
+    def backward(ctx, grad_obs, grad_rew, _grad_lengths):
+        actions, init_states = ctx.saved_tensors
+        d_act, d_init = ctx.roll._backward(ctx.call, ctx.params, actions.detach(), init_states.detach(), grad_obs, grad_rew)
+        return None, None, None, d_act, d_init

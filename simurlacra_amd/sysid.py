@@ -57,6 +57,57 @@ def pad_recordings(recs: Sequence, width: int, extra_rows: int = 0) -> Tuple[np.
     return tab, lens
 
 
+def check_playback_env(env, who: str):
+    """(innermost env, whether an ActNormWrapper is around it) of a plain env or one inside an ActNormWrapper; anything else raises"""
+    for w in all_envs(env):
+        if isinstance(w, EnvWrapper) and not isinstance(w, ActNormWrapper):
+            raise ValueErr(msg=f"{who} takes a plain env or one inside an ActNormWrapper, not {type(w).__name__}")
+    base = inner_env(env)
+    if base.name == "bob-d":
+        raise ValueErr(msg="the discrete-action family takes no playback policy")
+    return base, any(isinstance(w, ActNormWrapper) for w in all_envs(env))
+
+
+def vec_env_like(base, n: int, act_norm: bool):
+    """a handle of n lanes built with the constructor arguments of the env `base`, auto-reset off"""
+    from .vec_env import VecSimEnv
+
+    ctor = dict(base._ctor)
+    for k in ("num_envs", "load_experimental_tholds", "mass"):
+        ctor.pop(k, None)
+    dev = ctor.pop("device", 0)
+    v = VecSimEnv(base.name, n, ctor.pop("dt"), ctor.pop("max_steps"), task_args=ctor.pop("task_args") or None, device=dev, **ctor)
+    v.set_act_norm(act_norm)
+    v.set_auto_reset(False)
+    return v
+
+
+def domain_param_matrix(base, domain_params, names: Optional[Sequence[str]] = None) -> np.ndarray:
+    """[P, all parameters of the family] float32: the domain parameters of the env `base` with every row's entries on top.
+    domain_params: a list of P dicts (names missing from a dict keep the env's value), or a [P, n_names] array with names="""
+    from .vec_env import param_names
+
+    all_names = param_names(base.name)
+    nominal = np.array([base.domain_param[k] for k in all_names], dtype=np.float32)
+    if isinstance(domain_params, (list, tuple)) and (len(domain_params) == 0 or isinstance(domain_params[0], dict)):
+        mat = np.tile(nominal, (len(domain_params), 1))
+        for p, d in enumerate(domain_params):
+            for k, val in d.items():
+                if k not in all_names:
+                    raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {base.name}")
+                mat[p, all_names.index(k)] = float(np.asarray(val).reshape(-1)[0])
+        return mat
+    arr = np.asarray(domain_params.detach().cpu().numpy() if hasattr(domain_params, "detach") else domain_params, dtype=np.float32)
+    if names is None or arr.ndim != 2 or arr.shape[1] != len(names):
+        raise ShapeErr(msg="domain_params: a list of dicts, or a [P, n_names] array together with names=")
+    mat = np.tile(nominal, (arr.shape[0], 1))
+    for c, k in enumerate(names):
+        if k not in all_names:
+            raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {base.name}")
+        mat[:, all_names.index(k)] = arr[:, c]
+    return mat
+
+
 class TrajectoryMatchResult:
     """loss [P, R]: sum over the compared steps k and observation rows d of w_d (obs_sim - obs_rec)^2 (fp32, device);
     steps [P, R]: how many steps went into each sum (int64, device): the segment's length, or fewer when the simulated episode
@@ -106,14 +157,8 @@ class TrajectoryMatchSampler:
 
     def __init__(self, env, act_recordings, obs_recordings, init_states, obs_weights=None, batch_lanes: int = 65536,
                  chunk: int = 128):
-        for w in all_envs(env):
-            if isinstance(w, EnvWrapper) and not isinstance(w, ActNormWrapper):
-                raise ValueErr(msg=f"TrajectoryMatchSampler takes a plain env or one inside an ActNormWrapper, not {type(w).__name__}")
+        self._base, self._act_norm = check_playback_env(env, "TrajectoryMatchSampler")
         self.env = env
-        self._base = inner_env(env)
-        if self._base.name == "bob-d":
-            raise ValueErr(msg="the discrete-action family takes no playback policy")
-        self._act_norm = any(isinstance(w, ActNormWrapper) for w in all_envs(env))
         A, O, S = self._base.act_space.flat_dim, self._base.obs_space.flat_dim, self._base.state_space.flat_dim
         if len(act_recordings) < 1 or len(act_recordings) != len(obs_recordings):
             raise ShapeErr(msg="one observation recording per action recording, at least one")
@@ -147,19 +192,10 @@ class TrajectoryMatchSampler:
 
     def _vec_for(self, n):
         """a handle of n lanes configured like the env, with the recordings and the target on it"""
-        from .vec_env import VecSimEnv
-
         if self._vec is not None and self._vec.n_envs != n:
             self.close()
         if self._vec is None:
-            ctor = dict(self._base._ctor)
-            for k in ("num_envs", "load_experimental_tholds", "mass"):
-                ctor.pop(k, None)
-            dev = ctor.pop("device", 0)
-            v = VecSimEnv(self._base.name, n, ctor.pop("dt"), ctor.pop("max_steps"), task_args=ctor.pop("task_args") or None,
-                          device=dev, **ctor)
-            v.set_act_norm(self._act_norm)
-            v.set_auto_reset(False)
+            v = vec_env_like(self._base, n, self._act_norm)
             v.set_policy_playback(self._act, self._len, batch_lane_rec(n // self.num_segments, self.num_segments))
             v.set_rollout_target(self._obs, self._weights)
             self._vec = v
@@ -167,27 +203,7 @@ class TrajectoryMatchSampler:
 
     def param_matrix(self, domain_params, names: Optional[Sequence[str]] = None) -> np.ndarray:
         """[P, all parameters of the family] float32: the env's current domain parameters with every candidate's entries on top"""
-        from .vec_env import param_names
-
-        all_names = param_names(self._base.name)
-        nominal = np.array([self._base.domain_param[k] for k in all_names], dtype=np.float32)
-        if isinstance(domain_params, (list, tuple)) and (len(domain_params) == 0 or isinstance(domain_params[0], dict)):
-            mat = np.tile(nominal, (len(domain_params), 1))
-            for p, d in enumerate(domain_params):
-                for k, val in d.items():
-                    if k not in all_names:
-                        raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {self._base.name}")
-                    mat[p, all_names.index(k)] = float(np.asarray(val).reshape(-1)[0])
-            return mat
-        arr = np.asarray(domain_params.detach().cpu().numpy() if hasattr(domain_params, "detach") else domain_params, dtype=np.float32)
-        if names is None or arr.ndim != 2 or arr.shape[1] != len(names):
-            raise ShapeErr(msg="domain_params: a list of dicts, or a [P, n_names] array together with names=")
-        mat = np.tile(nominal, (arr.shape[0], 1))
-        for c, k in enumerate(names):
-            if k not in all_names:
-                raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {self._base.name}")
-            mat[:, all_names.index(k)] = arr[:, c]
-        return mat
+        return domain_param_matrix(self._base, domain_params, names)
 
     def _check_wrt(self, wrt, gauss_newton: bool) -> List[str]:
         """the validated list of parameter names to differentiate with respect to (needs no device)"""

@@ -67,6 +67,26 @@ def expand_upper_triangle(tri, g):
     return full
 
 
+def lanes_last(x, ld):
+    """[N, ...] row-major -> [..., ld]: the lane index last and padded with zeros to ld, the struct-of-arrays layout of the kernels
+    ([N, T] -> [T, ld], [N, T, D] -> [T, D, ld]).  A torch tensor on any device; the result is contiguous."""
+    import torch
+
+    n = x.shape[0]
+    if n > ld:
+        raise ShapeErr(msg=f"{n} lanes do not fit a leading dimension of {ld}")
+    out = torch.zeros(tuple(x.shape[1:]) + (int(ld),), dtype=x.dtype, device=x.device)
+    out[..., :n] = x.movedim(0, -1)
+    return out
+
+
+def lanes_first(y, n):
+    """[..., ld] -> [n, ...] row-major: the inverse of lanes_last for the first n lanes (contiguous)"""
+    if n > y.shape[-1]:
+        raise ShapeErr(msg=f"{n} lanes asked of a leading dimension of {y.shape[-1]}")
+    return y[..., :n].movedim(-1, 0).contiguous()
+
+
 class VecSimEnv:
     """N environments of one Pyrado pysim family on one GPU."""
 
@@ -837,6 +857,36 @@ class VecSimEnv:
             self.set_traj_capacity(getattr(self, "_traj_t0", 0) + int(k_steps))
         self._check(self._lib.vs_step_policy(self._h, int(k_steps), int(bool(record)), int(noise_seed) & (2 ** 64 - 1)),
                     "vs_step_policy")
+
+    def rollout_vjp(self, t_steps, g_rew=None, g_obs=None, g_state_last=None):
+        """Reverse-mode sweep over the recorded rollouts in rows 0 .. t_steps - 1 (vs_rollout_vjp; record mode 2, auto-reset off,
+        trajectory offset 0): the gradient of  sum g_rew r + sum g_obs . obs + g_state_last . (s_L, h_L)  per lane with respect to
+        the raw actions and the initial state.  Cotangents are float32 device tensors in the kernels' layout (lanes_last) or None
+        for 0: g_rew [T, ld], g_obs [T + 1, O, ld] (row k: the observation after k steps), g_state_last [S + H, ld].
+        Returns (d_act [T, A, ld], d_init [S + H, ld]) on the device; rows behind a lane's end and lanes >= n_envs are 0."""
+        import torch
+
+        T = int(t_steps)
+        S, A, O, H = (self.dims[k] for k in "SAOH")
+        dev = torch.device(f"cuda:{self.device}")
+        ptrs = []
+        for name, g, shape in (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                               ("g_state_last", g_state_last, (S + H, self.ld))):
+            if g is None:
+                ptrs.append(None)
+                continue
+            if not hasattr(g, "data_ptr") or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+                raise TypeErr(msg=f"{name} must be a contiguous float32 tensor on the GPU")
+            if tuple(g.shape) != shape:
+                raise ShapeErr(msg=f"{name} must be {shape}, got {tuple(g.shape)}")
+            ptrs.append(C.c_void_p(g.data_ptr()))
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        d_act = torch.empty(T, A, self.ld, dtype=torch.float32, device=dev)
+        d_init = torch.empty(S + H, self.ld, dtype=torch.float32, device=dev)
+        self._check(self._lib.vs_rollout_vjp(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
+                    "vs_rollout_vjp")
+        return d_act, d_init
 
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")
