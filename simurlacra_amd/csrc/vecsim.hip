@@ -361,6 +361,11 @@ static int fail(vs_handle h, int code, const char* what, hipError_t e = hipSucce
     return code;
 }
 
+// ... with the entry point's name in front: shared checks word their refusals as the entry point itself would
+static int fail(vs_handle h, int code, const char* who, const char* what, hipError_t e = hipSuccess) {
+    return fail(h, code, (std::string(who) + ": " + what).c_str(), e);
+}
+
 #define HIPCHK(h, x)                                              \
     do {                                                          \
         hipError_t e_ = (x);                                      \
@@ -398,6 +403,15 @@ static int dalloc(vs_handle h, T** p, size_t count) {
     HIPCHK(h, hipMemsetAsync(q, 0, count * sizeof(T) > 0 ? count * sizeof(T) : 4, h->stream));
     h->allocs.push_back(q);
     *p = (T*)q;
+    return VS_OK;
+}
+
+// free the device buffers that are set and forget them (not for members of h->allocs)
+template <class T, class... Ts>
+static int dfree(vs_handle h, T*& p, Ts*&... rest) {
+    if (p) HIPCHK(h, hipFree((void*)p));
+    p = nullptr;
+    if constexpr (sizeof...(rest) > 0) return dfree(h, rest...);
     return VS_OK;
 }
 
@@ -495,6 +509,105 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
     hipError_t e = hipMemcpyAsync(m->dev, &m->host, sizeof(Segs), hipMemcpyHostToDevice, h0->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h0->stream);  // host.s is rewritten by the next call
     if (e != hipSuccess) { m->err = std::string("mixed_upload: ") + hipGetErrorString(e); return VS_ERR_HIP; }
+    return VS_OK;
+}
+
+// ---- the policy slot of a handle: one in-kernel policy at a time, shared by the setters of the four kinds and vs_destroy
+static int drop_pop(vs_handle h) {
+    if (int rc = dfree(h, h->pop.w, h->pop.wg_set)) return rc;
+    h->pop = Pop{};
+    h->pop_sets = 0;
+    h->pop_g256 = h->pop_inert = false;
+    return VS_OK;
+}
+
+static int drop_fnn(vs_handle h) {
+    if (int rc = dfree(h, h->fnn.w)) return rc;
+    h->fnn = Fnn{};
+    return VS_OK;
+}
+
+static int drop_rnn(vs_handle h) {
+    if (int rc = dfree(h, h->rnn.w, h->rnn.hid)) return rc;
+    h->rnn = Rnn{};
+    return VS_OK;
+}
+
+static int drop_lin(vs_handle h) {
+    if (int rc = dfree(h, h->lin.w)) return rc;
+    h->lin = Lin{};
+    return VS_OK;
+}
+
+static int drop_sens(vs_handle h) {
+    if (int rc = dfree(h, h->sens.grad, h->sens.gn, h->sens.sens)) return rc;
+    h->sens = Sens{};
+    return VS_OK;
+}
+
+static int drop_target(vs_handle h) {
+    if (int rc = drop_sens(h)) return rc;  // (the sensitivities belong to the target's sum)
+    return dfree(h, h->play.tgt, h->play.loss);
+}
+
+static int drop_play(vs_handle h) {  // the playback policy and the target that belongs to it
+    if (int rc = drop_target(h)) return rc;
+    if (int rc = dfree(h, h->play.act, h->play.rec_len, h->play.lane_rec)) return rc;
+    h->play = Play{};
+    return VS_OK;
+}
+
+// one in-kernel policy at a time: whichever kind is set goes, with what belongs to it -- the running hidden state, the playback
+// target and its sensitivities, the population (it was set for this policy) and the packer's index map
+static int drop_policy(vs_handle h) {
+    if (int rc = drop_fnn(h)) return rc;
+    if (int rc = drop_rnn(h)) return rc;
+    if (int rc = drop_lin(h)) return rc;
+    if (int rc = drop_play(h)) return rc;
+    if (int rc = drop_pop(h)) return rc;
+    h->pol_map.clear();
+    h->pol_n_params = 0;
+    return VS_OK;
+}
+
+// the observation rows a policy sees, descriptor D -> kernel arguments P (n_obs == 0: all of them, in order; ident: exactly that)
+template <class D, class P>
+static int policy_view(vs_handle h, const char* who, const D& desc, P& f) {
+    const int O = ENV_INFO[h->type].O;
+    f.n_vis = desc.n_obs > 0 ? desc.n_obs : O;
+    if (f.n_vis > O) return fail(h, VS_ERR_ARG, who, "more visible observation rows than the env has");
+    f.ident = f.n_vis == O;
+    for (int k = 0; k < f.n_vis; ++k) {
+        f.obs_idx[k] = desc.n_obs > 0 ? desc.obs_idx[k] : k;
+        if (f.obs_idx[k] < 0 || f.obs_idx[k] >= O) return fail(h, VS_ERR_ARG, who, "obs_idx out of range");
+        if (f.obs_idx[k] != k) f.ident = 0;
+    }
+    return VS_OK;
+}
+
+// ... and its exploration noise
+template <class D, class P>
+static int policy_noise(vs_handle h, const char* who, const D& desc, P& f) {
+    for (int j = 0; j < ENV_INFO[h->type].A; ++j) {
+        f.noise_std[j] = desc.noise_std[j];
+        if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, who, "noise_std must be >= 0");
+        if (f.noise_std[j] > 0.f) f.noisy = 1;
+    }
+    return VS_OK;
+}
+
+// the packed vector of one policy in a new device buffer: the caller's `need` parameters (host or device) laid out by the
+// index map (packed slot -> source index, -1: zero padding)
+static int upload_packed(vs_handle h, const char* who, const std::vector<int>& map, const float* params, int64_t need, const float** out) {
+    std::vector<float> src((size_t)need), pk(map.size(), 0.f);
+    HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    for (size_t q = 0; q < map.size(); ++q)
+        if (map[q] >= 0) pk[q] = src[(size_t)map[q]];
+    float* dw = nullptr;
+    HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, who, "upload", e); }
+    *out = dw;
     return VS_OK;
 }
 
@@ -644,20 +757,7 @@ int vs_destroy(vs_handle h) {
     if (h->stage_mask) (void)hipFree(h->stage_mask);
     if (h->d_pbuf) (void)hipFree(h->d_pbuf);
     if (h->d_ring) (void)hipFree(h->d_ring);
-    if (h->fnn.w) (void)hipFree((void*)h->fnn.w);
-    if (h->rnn.w) (void)hipFree((void*)h->rnn.w);
-    if (h->lin.w) (void)hipFree((void*)h->lin.w);
-    if (h->play.act) (void)hipFree((void*)h->play.act);
-    if (h->play.tgt) (void)hipFree((void*)h->play.tgt);
-    if (h->play.rec_len) (void)hipFree((void*)h->play.rec_len);
-    if (h->play.lane_rec) (void)hipFree((void*)h->play.lane_rec);
-    if (h->play.loss) (void)hipFree(h->play.loss);
-    if (h->sens.grad) (void)hipFree(h->sens.grad);
-    if (h->sens.gn) (void)hipFree(h->sens.gn);
-    if (h->sens.sens) (void)hipFree(h->sens.sens);
-    if (h->rnn.hid) (void)hipFree(h->rnn.hid);
-    if (h->pop.w) (void)hipFree((void*)h->pop.w);
-    if (h->pop.wg_set) (void)hipFree((void*)h->pop.wg_set);
+    (void)drop_policy(h);
     if (h->d_hrec) (void)hipFree(h->d_hrec);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -975,8 +1075,7 @@ int vs_step_jac(vs_handle h, const float* actions, int64_t env_stride, int64_t d
 
 // the hidden-state record plane: traj_cap rows of hrec_width floats per env (when both are set)
 static int alloc_hrec(vs_handle h) {
-    if (h->d_hrec) HIPCHK(h, hipFree(h->d_hrec));
-    h->d_hrec = nullptr;
+    if (int rc = dfree(h, h->d_hrec)) return rc;
     if (h->hrec_width <= 0 || h->traj_cap <= 0) return VS_OK;
     const size_t bytes = (size_t)h->traj_cap * h->hrec_width * h->d.ld * sizeof(float);
     HIPCHK(h, hipMalloc((void**)&h->d_hrec, bytes));
@@ -996,8 +1095,7 @@ static int free_traj(vs_handle h) {
     }
     d.traj_rec = nullptr;
     d.traj_done = nullptr;
-    if (h->d_hrec) HIPCHK(h, hipFree(h->d_hrec));
-    h->d_hrec = nullptr;
+    if (int rc = dfree(h, h->d_hrec)) return rc;
     h->traj_cap = 0;
     d.traj_rows = 0;
     return VS_OK;
@@ -1083,93 +1181,19 @@ int vs_step_random(vs_handle h, uint64_t seed, int k_steps, int record) {
     return VS_OK;
 }
 
-static int drop_pop(vs_handle h) {
-    if (h->pop.w) HIPCHK(h, hipFree((void*)h->pop.w));
-    if (h->pop.wg_set) HIPCHK(h, hipFree((void*)h->pop.wg_set));
-    h->pop = Pop{};
-    h->pop_sets = 0;
-    h->pop_g256 = h->pop_inert = false;
-    return VS_OK;
-}
-
-static int drop_rnn(vs_handle h) {
-    if (h->rnn.w) HIPCHK(h, hipFree((void*)h->rnn.w));
-    if (h->rnn.hid) HIPCHK(h, hipFree(h->rnn.hid));
-    h->rnn = Rnn{};
-    return VS_OK;
-}
-
-static int drop_lin(vs_handle h) {
-    if (h->lin.w) HIPCHK(h, hipFree((void*)h->lin.w));
-    h->lin = Lin{};
-    return VS_OK;
-}
-
-static int drop_sens(vs_handle h) {
-    if (h->sens.grad) HIPCHK(h, hipFree(h->sens.grad));
-    h->sens.grad = nullptr;
-    if (h->sens.gn) HIPCHK(h, hipFree(h->sens.gn));
-    h->sens.gn = nullptr;
-    if (h->sens.sens) HIPCHK(h, hipFree(h->sens.sens));
-    h->sens = Sens{};
-    return VS_OK;
-}
-
-static int drop_target(vs_handle h) {
-    if (int rc = drop_sens(h)) return rc;  // (the sensitivities belong to the target's sum)
-    if (h->play.tgt) HIPCHK(h, hipFree((void*)h->play.tgt));
-    h->play.tgt = nullptr;
-    if (h->play.loss) HIPCHK(h, hipFree(h->play.loss));
-    h->play.loss = nullptr;
-    return VS_OK;
-}
-
-static int drop_play(vs_handle h) {  // the playback policy and the target that belongs to it
-    if (int rc = drop_target(h)) return rc;
-    if (h->play.act) HIPCHK(h, hipFree((void*)h->play.act));
-    h->play.act = nullptr;
-    if (h->play.rec_len) HIPCHK(h, hipFree((void*)h->play.rec_len));
-    h->play.rec_len = nullptr;
-    if (h->play.lane_rec) HIPCHK(h, hipFree((void*)h->play.lane_rec));
-    h->play = Play{};
-    return VS_OK;
-}
-
-// the packed vector of one policy from its index map (packed slot -> source index, -1: zero padding)
-static std::vector<float> pack_by_map(const std::vector<int>& map, const std::vector<float>& src) {
-    std::vector<float> pk(map.size(), 0.f);
-    for (size_t q = 0; q < map.size(); ++q)
-        if (map[q] >= 0) pk[q] = src[(size_t)map[q]];
-    return pk;
-}
-
 int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params, int64_t n_params) {
     if (!h) return VS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }
-    h->fnn = Fnn{};
-    if (int rc = drop_rnn(h)) return rc;  // one in-kernel policy at a time
-    if (int rc = drop_lin(h)) return rc;
-    if (int rc = drop_play(h)) return rc;
-    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
-    h->pol_map.clear();
-    h->pol_n_params = 0;
+    if (int rc = drop_policy(h)) return rc;  // before any check: a refused call leaves no policy
     if (!desc) return VS_OK;
     const EnvInfo& ei = ENV_INFO[h->type];
+    const char* who = "vs_set_policy_fnn";
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: the discrete-action family takes no network policy");
     if (!params || desc->n_hidden < 1 || desc->n_hidden > FNN_MAXH) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: 1 .. 4 hidden layers and a parameter vector");
     Fnn f{};
     f.n_hidden = desc->n_hidden;
-    f.n_vis = desc->n_obs > 0 ? desc->n_obs : ei.O;
-    if (f.n_vis > ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: more visible observation rows than the env has");
-    f.ident = 1;
-    for (int k = 0; k < f.n_vis; ++k) {
-        f.obs_idx[k] = desc->n_obs > 0 ? desc->obs_idx[k] : k;
-        if (f.obs_idx[k] < 0 || f.obs_idx[k] >= ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: obs_idx out of range");
-        if (f.obs_idx[k] != k) f.ident = 0;
-    }
-    if (f.n_vis != ei.O) f.ident = 0;
+    if (int rc = policy_view(h, who, *desc, f)) return rc;
     f.feat = desc->feat != 0;
     if (f.feat && f.n_vis < 2) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: the sin / cos featurisation needs two observation rows");
     f.in_dim = f.n_vis + f.feat;
@@ -1196,16 +1220,10 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     f.off_b[f.n_hidden] = off;
     off += 8;
     if (n_params != need) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: parameter count does not match the layer sizes");
-    for (int j = 0; j < ei.A; ++j) {
-        f.noise_std[j] = desc->noise_std[j];
-        if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_fnn: noise_std must be >= 0");
-        if (f.noise_std[j] > 0.f) f.noisy = 1;
-    }
+    if (int rc = policy_noise(h, who, *desc, f)) return rc;
     // torch layout -> transposed, zero-padded rows: unit j of layer l reads Wt_l[k][j], contiguous over j (scalar-load friendly);
     // built as an index map (packed slot -> source index) that vs_set_policy_population reuses on the device
-    std::vector<float> src((size_t)need);
     std::vector<int> map((size_t)off, -1);
-    HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
     int q = 0;
     last = f.in_dim;
     for (int l = 0; l < f.n_hidden; ++l) {
@@ -1217,12 +1235,7 @@ int vs_set_policy_fnn(vs_handle h, const vs_fnn_desc* desc, const float* params,
     for (int j = 0; j < ei.A; ++j)
         for (int k = 0; k < last; ++k) map[(size_t)f.off_w[f.n_hidden] + (size_t)j * FNN_W + k] = q++;
     for (int j = 0; j < ei.A; ++j) map[(size_t)f.off_b[f.n_hidden] + j] = q++;
-    const std::vector<float> pk = pack_by_map(map, src);
-    float* dw = nullptr;
-    HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_fnn: upload", e); }
-    f.w = dw;
+    if (int rc = upload_packed(h, who, map, params, need, &f.w)) return rc;
     h->fnn = f;
     h->pol_map = std::move(map);
     h->pol_n_params = need;
@@ -1233,16 +1246,10 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     if (!h) return VS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (int rc = drop_rnn(h)) return rc;
-    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
-    h->fnn = Fnn{};
-    if (int rc = drop_lin(h)) return rc;
-    if (int rc = drop_play(h)) return rc;
-    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
-    h->pol_map.clear();
-    h->pol_n_params = 0;
+    if (int rc = drop_policy(h)) return rc;  // before any check: a refused call leaves no policy
     if (!desc) return VS_OK;
     const EnvInfo& ei = ENV_INFO[h->type];
+    const char* who = "vs_set_policy_rnn";
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: the discrete-action family takes no network policy");
     if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_policy_rnn: not available with a wrapper pipeline on the handle");
     if (!params || desc->cell < VS_RNN_TANH || desc->cell > VS_RNN_LSTM) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: unknown cell kind or no parameter vector");
@@ -1257,19 +1264,8 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     const int G = rnn_gates(f.cell), lstm = f.cell == VS_RNN_LSTM;
     f.hs = f.n_layers * f.hidden * (lstm ? 2 : 1);
     f.out_nonlin = desc->out_nonlin;
-    f.n_vis = desc->n_obs > 0 ? desc->n_obs : ei.O;
-    if (f.n_vis > ei.O || f.n_vis > RNN_XP) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: more visible observation rows than the env has");
-    f.ident = f.n_vis == ei.O;
-    for (int k = 0; k < f.n_vis; ++k) {
-        f.obs_idx[k] = desc->n_obs > 0 ? desc->obs_idx[k] : k;
-        if (f.obs_idx[k] < 0 || f.obs_idx[k] >= ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: obs_idx out of range");
-        if (f.obs_idx[k] != k) f.ident = 0;
-    }
-    for (int j = 0; j < ei.A; ++j) {
-        f.noise_std[j] = desc->noise_std[j];
-        if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_rnn: noise_std must be >= 0");
-        if (f.noise_std[j] > 0.f) f.noisy = 1;
-    }
+    if (int rc = policy_view(h, who, *desc, f)) return rc;  // (at most O <= MAXO = RNN_XP rows: they fit the padded input row)
+    if (int rc = policy_noise(h, who, *desc, f)) return rc;
     const int64_t Hh = f.hidden;
     int64_t need = 0;
     int off = 0;
@@ -1287,9 +1283,7 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     f.lds_rows = (f.n_layers * (lstm ? 2 : 1) + f.n_layers) * f.hp;
     // torch order -> per unit blocks, gate-interleaved rows (the kernel reads G consecutive floats per input); an index map
     // as in vs_set_policy_fnn
-    std::vector<float> src((size_t)need);
     std::vector<int> map((size_t)off, -1);
-    HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
     int q = 0;
     for (int l = 0; l < f.n_layers; ++l) {
         const int in = l == 0 ? f.n_vis : f.hidden, inp = l == 0 ? RNN_XP : f.hp;
@@ -1304,16 +1298,11 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
     for (int j = 0; j < ei.A; ++j)
         for (int k = 0; k < f.hidden; ++k) map[(size_t)f.off_o + (size_t)j * f.hp + k] = q++;
     for (int j = 0; j < ei.A; ++j) map[(size_t)f.off_o + (size_t)ei.A * f.hp + j] = q++;
-    const std::vector<float> pk = pack_by_map(map, src);
-    float* dw = nullptr;
-    HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_rnn: upload", e); }
-    f.w = dw;
+    if (int rc = upload_packed(h, who, map, params, need, &f.w)) return rc;
     const size_t hb = (size_t)f.hs * h->d.ld * sizeof(float);
-    e = hipMalloc((void**)&f.hid, hb);
+    hipError_t e = hipMalloc((void**)&f.hid, hb);
     if (e == hipSuccess) e = hipMemset(f.hid, 0, hb);
-    if (e != hipSuccess) { (void)hipFree(dw); if (f.hid) (void)hipFree(f.hid); return fail(h, VS_ERR_HIP, "vs_set_policy_rnn: hidden state", e); }
+    if (e != hipSuccess) { (void)hipFree((void*)f.w); if (f.hid) (void)hipFree(f.hid); return fail(h, VS_ERR_HIP, who, "hidden state", e); }
     h->rnn = f;
     h->pol_map = std::move(map);
     h->pol_n_params = need;
@@ -1322,6 +1311,7 @@ int vs_set_policy_rnn(vs_handle h, const vs_rnn_desc* desc, const float* params,
 
 int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* params, int64_t n_params) {
     if (!h) return VS_ERR_ARG;
+    const char* who = "vs_set_policy_linear";
     Lin f{};
     std::vector<int> map;
     int64_t need = 0;
@@ -1330,19 +1320,8 @@ int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* para
         if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: the discrete-action family takes no in-kernel policy");
         if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_set_policy_linear: not available with a wrapper pipeline on the handle");
         if (!params || desc->n_terms < 1 || desc->n_terms > VS_LIN_MAX_TERMS) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: 1 .. 51 terms and a parameter vector");
-        f.n_vis = desc->n_obs > 0 ? desc->n_obs : ei.O;
-        if (f.n_vis > ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: more visible observation rows than the env has");
-        f.ident = f.n_vis == ei.O;
-        for (int k = 0; k < f.n_vis; ++k) {
-            f.obs_idx[k] = desc->n_obs > 0 ? desc->obs_idx[k] : k;
-            if (f.obs_idx[k] < 0 || f.obs_idx[k] >= ei.O) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: obs_idx out of range");
-            if (f.obs_idx[k] != k) f.ident = 0;
-        }
-        for (int j = 0; j < ei.A; ++j) {
-            f.noise_std[j] = desc->noise_std[j];
-            if (!(f.noise_std[j] >= 0.f)) return fail(h, VS_ERR_ARG, "vs_set_policy_linear: noise_std must be >= 0");
-            if (f.noise_std[j] > 0.f) f.noisy = 1;
-        }
+        if (int rc = policy_view(h, who, *desc, f)) return rc;
+        if (int rc = policy_noise(h, who, *desc, f)) return rc;
         // feature q of the stack -> slot of a packed weight row (see k_rollout_lin)
         std::vector<int> slot;
         for (int t = 0; t < desc->n_terms; ++t) {
@@ -1376,25 +1355,10 @@ int vs_set_policy_linear(vs_handle h, const vs_lin_desc* desc, const float* para
     }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float* dw = nullptr;
-    if (desc) {
-        std::vector<float> src((size_t)need);
-        HIPCHK(h, hipMemcpy(src.data(), params, (size_t)need * sizeof(float), is_device_ptr(params) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        const std::vector<float> pk = pack_by_map(map, src);
-        HIPCHK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
-        hipError_t e = hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(dw); return fail(h, VS_ERR_HIP, "vs_set_policy_linear: upload", e); }
-    }
-    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
-    h->fnn = Fnn{};
-    if (int rc = drop_rnn(h)) return rc;
-    if (int rc = drop_lin(h)) return rc;
-    if (int rc = drop_play(h)) return rc;
-    if (int rc = drop_pop(h)) return rc;  // (a population belongs to the policy it was set for)
-    h->pol_map.clear();
-    h->pol_n_params = 0;
+    if (desc)
+        if (int rc = upload_packed(h, who, map, params, need, &f.w)) return rc;
+    if (int rc = drop_policy(h)) return rc;
     if (!desc) return VS_OK;
-    f.w = dw;
     h->lin = f;
     h->pol_map = std::move(map);
     h->pol_n_params = need;
@@ -1474,14 +1438,7 @@ int vs_set_policy_playback(vs_handle h, const float* actions, int n_rec, int t_l
         p.n_rec_ld = nrl;
         p.t_len = t_len;
     }
-    if (h->fnn.w) { HIPCHK(h, hipFree((void*)h->fnn.w)); }  // one in-kernel policy at a time
-    h->fnn = Fnn{};
-    if (int rc = drop_rnn(h)) return rc;
-    if (int rc = drop_lin(h)) return rc;
-    if (int rc = drop_play(h)) return rc;  // (with its target)
-    if (int rc = drop_pop(h)) return rc;
-    h->pol_map.clear();
-    h->pol_n_params = 0;
+    if (int rc = drop_policy(h)) return rc;
     h->play = p;
     return VS_OK;
 }
@@ -1511,10 +1468,8 @@ int vs_set_rollout_target(vs_handle h, const float* target_obs, int n_rec, int t
         if (dl) (void)hipFree(dl);
         return fail(h, VS_ERR_HIP, "vs_set_rollout_target: allocation", e);
     }
-    const Sens keep = h->sens;  // a new target keeps the sensitivities on and zeroes their sums
-    h->sens = Sens{};
-    if (int rc = drop_target(h)) { h->sens = keep; (void)hipFree(dt); (void)hipFree(dl); return rc; }
-    h->sens = keep;
+    // the old tables go, not drop_target(): a new target keeps the sensitivities on and zeroes their sums
+    if (int rc = dfree(h, h->play.tgt, h->play.loss)) { (void)hipFree(dt); (void)hipFree(dl); return rc; }
     h->play.tgt = dt;
     h->play.loss = dl;
     for (int q = 0; q < MAXO; ++q) h->play.w[q] = w[q];
@@ -1668,10 +1623,11 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
                                                       : "vs_step_policy: a population runs with auto-reset off");
         if (!record) return fail(h, VS_ERR_STATE, "vs_step_policy: a population runs with records on");
     }
+    if (!h->fnn.w && !h->rnn.w && !h->lin.w && !h->play.act) return fail(h, VS_ERR_STATE, "vs_step_policy: no network set (vs_set_policy_fnn)");
+    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
     if (h->play.act) {
-        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
         if (h->play.tgt && h->auto_reset) return fail(h, VS_ERR_STATE, "vs_step_policy: a rollout target runs with auto-reset off");
-        if (h->sens.n) {
+        if (h->sens.n) {  // no records: the launch goes from here
             if (record) return fail(h, VS_ERR_STATE, "vs_step_policy: no records with sensitivities on (vs_set_rollout_sens)");
             if (h->auto_reset || !h->play.tgt) return fail(h, VS_ERR_STATE, "vs_step_policy: sensitivities need a rollout target and auto-reset off");
             HIPCHK(h, hipSetDevice(h->device));
@@ -1679,43 +1635,29 @@ int vs_step_policy(vs_handle h, int k_steps, int record, uint64_t noise_seed) {
             HIPCHK(h, hipGetLastError());
             return VS_OK;
         }
-        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
-        HIPCHK(h, hipSetDevice(h->device));
-        DISPATCH_ENV(h->type, Launch<E>::rollout_play(h, k_steps, record ? h->record_mode : 0));
-        HIPCHK(h, hipGetLastError());
-        return VS_OK;
     }
-    if (h->rnn.w) {
-        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
-        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
-        if (record && h->hrec_width && h->hrec_width != h->rnn.hs)
-            return fail(h, VS_ERR_STATE, "vs_step_policy: the hidden-state record width differs from the policy's hidden size");
-        HIPCHK(h, hipSetDevice(h->device));
-        h->rnn.hrec = h->d_hrec;
-        DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, record ? h->record_mode : 0, noise_seed));
-        HIPCHK(h, hipGetLastError());
-        return VS_OK;
-    }
-    if (h->lin.w) {
-        if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
-        if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
-        HIPCHK(h, hipSetDevice(h->device));
-        DISPATCH_ENV(h->type, Launch<E>::rollout_lin(h, k_steps, record ? h->record_mode : 0, noise_seed));
-        HIPCHK(h, hipGetLastError());
-        return VS_OK;
-    }
-    if (!h->fnn.w) return fail(h, VS_ERR_STATE, "vs_step_policy: no network set (vs_set_policy_fnn)");
-    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_step_policy: not available with a wrapper pipeline on the handle");
     if (record && h->d.traj_t0 + k_steps > h->traj_cap) return fail(h, VS_ERR_STATE, "vs_step_policy: traj offset + k_steps exceeds vs_set_traj_capacity");
+    if (h->rnn.w && record && h->hrec_width && h->hrec_width != h->rnn.hs)
+        return fail(h, VS_ERR_STATE, "vs_step_policy: the hidden-state record width differs from the policy's hidden size");
     HIPCHK(h, hipSetDevice(h->device));
-    int shape = fnn_shape(h);
-    if (h->pop.w && shape != 0 && !h->pop_g256) {
-        // the 256-env shapes take one set per workgroup of 256 lanes: a table that is uniform in groups of 64 only runs shape 0
-        // when the choice is automatic, and is refused when shape 1 or 2 is pinned
-        if (h->policy_shape > 0) return fail(h, VS_ERR_STATE, "vs_step_policy: the pinned 256-env shape needs a population table uniform in groups of 256 lanes");
-        shape = 0;
+    const int rec = record ? h->record_mode : 0;
+    if (h->play.act) {
+        DISPATCH_ENV(h->type, Launch<E>::rollout_play(h, k_steps, rec));
+    } else if (h->rnn.w) {
+        h->rnn.hrec = h->d_hrec;
+        DISPATCH_ENV(h->type, Launch<E>::rollout_rnn(h, k_steps, rec, noise_seed));
+    } else if (h->lin.w) {
+        DISPATCH_ENV(h->type, Launch<E>::rollout_lin(h, k_steps, rec, noise_seed));
+    } else {
+        int shape = fnn_shape(h);
+        if (h->pop.w && shape != 0 && !h->pop_g256) {
+            // the 256-env shapes take one set per workgroup of 256 lanes: a table that is uniform in groups of 64 only runs shape 0
+            // when the choice is automatic, and is refused when shape 1 or 2 is pinned
+            if (h->policy_shape > 0) return fail(h, VS_ERR_STATE, "vs_step_policy: the pinned 256-env shape needs a population table uniform in groups of 256 lanes");
+            shape = 0;
+        }
+        DISPATCH_ENV(h->type, Launch<E>::rollout_fnn(h, k_steps, rec, noise_seed, shape));
     }
-    DISPATCH_ENV(h->type, Launch<E>::rollout_fnn(h, k_steps, record ? h->record_mode : 0, noise_seed, shape));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -570,6 +570,28 @@ class VecSimEnv:
     # ------------------------------------------------------------------------------------------------ policy in the kernel
     _NONLIN = {None: L.VS_NL_NONE, "none": L.VS_NL_NONE, "tanh": L.VS_NL_TANH, "relu": L.VS_NL_RELU, "sigmoid": L.VS_NL_SIGMOID}
 
+    @staticmethod
+    def _policy_view(d, obs_idx, noise_std, noise_rows=2):
+        """obs_idx / noise_std of a setter into its descriptor d (FnnDesc, RnnDesc or LinDesc): the rows the policy sees
+        (None: all of them, in order) and the exploration noise per action dimension (None: none)"""
+        if obs_idx is not None:
+            idx = [int(x) for x in obs_idx]
+            if len(idx) > 8:
+                raise ValueErr(msg="at most 8 visible observation rows")
+            d.n_obs = len(idx)
+            for k, x in enumerate(idx):
+                d.obs_idx[k] = x
+        if noise_std is not None:
+            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))[:noise_rows]):
+                d.noise_std[k] = float(x)
+
+    @staticmethod
+    def _flat_params(params):
+        """a policy's parameter vector (torch tensor or array) as a contiguous float32 host vector"""
+        if hasattr(params, "detach"):
+            params = params.detach().to("cpu").numpy()
+        return np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+
     def set_policy_fnn(self, params, hidden_sizes, hidden_nonlin="tanh", output_nonlin=None, feat=False, obs_idx=None,
                        noise_std=None):
         """Hand a feed-forward network policy (FNN of P/policies/feed_back/fnn.py:43-160) to the fused kernel of step_policy.
@@ -593,17 +615,8 @@ class VecSimEnv:
             d.hidden_nonlin[k] = self._NONLIN[f]
         d.output_nonlin = self._NONLIN[output_nonlin]
         d.feat = int(bool(feat))
-        if obs_idx is not None:
-            idx = [int(x) for x in obs_idx]
-            d.n_obs = len(idx)
-            for k, x in enumerate(idx):
-                d.obs_idx[k] = x
-        if noise_std is not None:
-            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))):
-                d.noise_std[k] = float(x)
-        if hasattr(params, "detach"):
-            params = params.detach().to("cpu").numpy()
-        flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+        self._policy_view(d, obs_idx, noise_std, noise_rows=None)  # (more than two noise entries: IndexError, as ever)
+        flat = self._flat_params(params)
         self._check(self._lib.vs_set_policy_fnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_fnn")
 
@@ -624,19 +637,8 @@ class VecSimEnv:
         d.n_layers = int(n_layers)
         d.hidden = int(hidden_size)
         d.out_nonlin = self._NONLIN[output_nonlin]
-        if obs_idx is not None:
-            idx = [int(x) for x in obs_idx]
-            if len(idx) > 8:
-                raise ValueErr(msg="at most 8 visible observation rows")
-            d.n_obs = len(idx)
-            for k, x in enumerate(idx):
-                d.obs_idx[k] = x
-        if noise_std is not None:
-            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))[:2]):
-                d.noise_std[k] = float(x)
-        if hasattr(params, "detach"):
-            params = params.detach().to("cpu").numpy()
-        flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+        self._policy_view(d, obs_idx, noise_std)
+        flat = self._flat_params(params)
         self._check(self._lib.vs_set_policy_rnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_rnn")
         self._rnn_hs = d.n_layers * d.hidden * (2 if d.cell == L.VS_RNN_LSTM else 1)
@@ -671,19 +673,8 @@ class VecSimEnv:
             d.terms[k].n_idx = len(idcs)
             for r, x in enumerate(idcs):
                 d.terms[k].idx[r] = int(x)
-        if obs_idx is not None:
-            idx = [int(x) for x in obs_idx]
-            if len(idx) > 8:
-                raise ValueErr(msg="at most 8 visible observation rows")
-            d.n_obs = len(idx)
-            for k, x in enumerate(idx):
-                d.obs_idx[k] = x
-        if noise_std is not None:
-            for k, x in enumerate(np.atleast_1d(np.asarray(noise_std, dtype=np.float32))[:2]):
-                d.noise_std[k] = float(x)
-        if hasattr(params, "detach"):
-            params = params.detach().to("cpu").numpy()
-        flat = np.ascontiguousarray(np.asarray(params, dtype=np.float32).reshape(-1))
+        self._policy_view(d, obs_idx, noise_std)
+        flat = self._flat_params(params)
         self._check(self._lib.vs_set_policy_linear(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_linear")
 
@@ -695,7 +686,7 @@ class VecSimEnv:
             t = x.detach()
             if t.is_cuda:
                 t = t.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-                torch.cuda.current_stream(self.device).synchronize()  # (the library re-lays it on its own stream)
+                torch.cuda.current_stream(self.device).synchronize()  # (the library reads it on its own stream)
                 return t, t.data_ptr(), tuple(t.shape)
             x = t.numpy()
         keep = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
@@ -796,20 +787,7 @@ class VecSimEnv:
         if params is None:
             self._check(self._lib.vs_set_policy_population(self._h, None, 0, 0, None), "vs_set_policy_population")
             return
-        keep = None
-        if hasattr(params, "detach"):
-            import torch
-
-            t = params.detach()
-            if t.is_cuda:
-                t = t.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-                torch.cuda.current_stream(self.device).synchronize()  # (the library packs it on its own stream)
-                keep, ptr, shape = t, t.data_ptr(), tuple(t.shape)
-            else:
-                params = t.numpy()
-        if keep is None:
-            keep = np.ascontiguousarray(np.asarray(params, dtype=np.float32))
-            ptr, shape = keep.ctypes.data, keep.shape
+        keep, ptr, shape = self._table_arg(params)
         if len(shape) != 2:
             raise ShapeErr(msg=f"params must be [n_sets, n_params], got shape {tuple(shape)}")
         ls = np.ascontiguousarray(np.asarray(lane_set, dtype=np.int32).reshape(-1))
