@@ -462,6 +462,27 @@ int vs_set_rollout_sens(vs_handle h, const int32_t* param_idx, int n_params);
  * discrete-action family (VS_ERR_STATE). */
 int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
                    float* d_init);
+/* The same sweep for CLOSED-LOOP rollouts: rows 0 .. t_steps - 1 were recorded by vs_step_policy with the handle's current linear
+ * policy (vs_set_policy_linear) in the loop, a_t = W phi(obs_t) + n_t, where n_t -- the exploration noise, if any -- is a constant the
+ * recorded raw action already contains.  The caller answers for the policy on the handle being the one that made the records.
+ * Per lane the differentiated function is
+ *     Phi = sum_t g_rew[t] r_t + sum_k g_obs[k] . obs_k + sum_t g_act[t] . a_t + g_state_last . (s_L, h_L)
+ * of that closed loop, L and every convention as for vs_rollout_vjp.  Arguments, layout (ld = vs_ld(h)), stream and the rule "refused
+ * before the first device call, outputs untouched" are vs_rollout_vjp's, with one more cotangent:
+ *   g_act   [t_steps][A][ld]   cotangent of the raw policy action a_t; NULL: 0
+ *   d_act   [t_steps][A][ld]   out: the TOTAL adjoint abar_t of a_t = d Phi / d n_t -- what the policy's parameter gradient needs:
+ *                              d Phi / d W = sum_t abar_t phi(obs_t)^T over the recorded observations (left to the caller: one GEMM)
+ *   d_init  [S + H][ld]        out: d Phi / d (s_0, h_0), feedback through the policy included
+ * For t = L - 1 .. 0 the step is differentiated as in vs_rollout_vjp with the observation cotangent g_obs[t + 1] + gpol, gpol [O] being
+ * the policy's pull-back of step t + 1 (0 at t = L - 1; observe(s_{t+1}) is the observation the policy saw);  abar_t = (the step's
+ * action column) + g_act[t];  gpol = (d phi / d obs)(obs_t)^T W^T abar_t with obs_t = observe(s_t) of the recorded state and the
+ * derivatives of the feature functions as the rollout kernel evaluates them (sign, const: 0; |v|: sign(v), 0 at 0; MultFeat: product
+ * rule per position; ATan2Feat(y, x): (x, -y) / (x^2 + y^2)).  After t = 0 the initial observation takes g_obs[0] + gpol.
+ * With a stack of constant features the result equals vs_rollout_vjp's bit for bit.
+ * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no linear policy on the handle (an FNN, RNN
+ * or playback policy, or none) and a policy population on the handle (VS_ERR_STATE).  FNN / RNN policies have no closed-loop sweep. */
+int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                          const float* g_state_last, float* d_act, float* d_init);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

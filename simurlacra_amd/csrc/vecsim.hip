@@ -613,7 +613,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 310; }
+int vs_version(void) { return 311; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1699,6 +1699,27 @@ int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp(h, v, t_steps));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                          const float* g_state_last, float* d_act, float* d_init) {
+    // every refusal comes before the first device call and leaves the outputs untouched
+    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: NULL handle or output");
+    if (t_steps < 1) return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: t_steps < 1");
+    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: the discrete-action family has no action gradient");
+    if (!h->lin.w) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: no linear policy on the handle (vs_set_policy_linear)");
+    if (h->pop.w) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: not available with a policy population on the handle");
+    if (h->record_mode != 2) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: needs the records of record mode 2 (vs_set_record_mode)");
+    if (h->auto_reset) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: switch auto-reset off (one rollout per lane, started at a reset)");
+    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: not available with a wrapper pipeline on the handle");
+    if (h->d.traj_t0 != 0) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: set the trajectory offset back to 0 (the sweep reads rows 0 .. t_steps - 1)");
+    if (t_steps > h->traj_cap || !h->d.traj_rec || !h->d.traj_done)
+        return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: t_steps exceeds vs_set_traj_capacity");
+    HIPCHK(h, hipSetDevice(h->device));
+    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
+    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_lin(h, v, g_act, t_steps));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

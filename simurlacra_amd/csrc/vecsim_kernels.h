@@ -14,6 +14,7 @@
 //   k_step_jac      vs_step_jac       step + Jacobians by forward-mode dual numbers
 //   k_rollout_play_sens  vs_step_policy   playback rollout + discrepancy with its gradient and Gauss-Newton matrix w.r.t. domain parameters
 //   k_rollout_vjp   vs_rollout_vjp    reverse-mode sweep over a recorded rollout: gradients w.r.t. its actions and initial state
+//   k_rollout_vjp_lin  vs_rollout_vjp_policy  the same sweep with the handle's linear policy in the loop (closed-loop adjoints)
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2406,6 +2407,197 @@ __global__ __launch_bounds__(64) void k_rollout_vjp(Task T, Dev d, Vjp V, int t_
     for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
 }
 
+// ------------------------------------------------------------------- reverse-mode sweep with a linear policy in the loop
+// vs_rollout_vjp_policy: k_rollout_vjp for rollouts that k_rollout_lin recorded -- a_t = W phi(obs_t) + n_t with the handle's linear
+// policy (Lin: the same packed weights, slot order, kinds, xterm and observation view) and n_t constant (the exploration noise is in the
+// recorded raw action already).  Same shape: one env per lane, one wave per workgroup, no LDS, no barrier, nothing of the handle written.
+//   * gpol [O] is the policy's pull-back onto the observation it saw, carried from step t + 1 (0 at t = L - 1).  observe(s_{t+1}) IS
+//     that observation, so step t runs vjp_step with the observation cotangent g_obs[t + 1] + gpol: the whole feedback path.
+//   * abar_t[j] = out[NS + j] + g_act[t][j] (g_act: cotangent on the raw action, NULL = 0, then no addition) is stored to d_act[t]: the
+//     total adjoint of a_t, d Phi / d n_t.
+//   * ob_t = E::observe(s_t) of the recorded state (the function the forward kernel ran: the same bits as the recorded row), x = ob_t
+//     through obs_idx.  Per slot of a kind the stack holds  wbar = sum_j abar_t[j] W[j][slot]  (weight = uniform operand) and
+//     gx[k] = fmaf(wbar, phi'(x_k), gx[k]);  sincos_fast, v_exp_f32 and v_rcp_f32 in the forward kernel's expressions, so the derivative
+//     is that of the function that ran.  sign and const have derivative 0 and cost nothing; |v|' = sign(v), 0 at 0, as torch has it.
+//     MultFeat: the product rule per position (a row named twice gets both terms); ATan2Feat(y, x): (x, -y) / (x^2 + y^2); both add to
+//     the observation rows directly.  gx goes back to observation rows through obs_idx by wave-uniform selects: the next gpol.
+//   * After t = 0: vjp_observe with g_obs[0] + gpol, d_init = lambda.  Rows t >= L of d_act and lanes >= n are 0 and read no cotangent.
+// With a stack whose features are all constant gpol stays +0 and every float operation is k_rollout_vjp's: the same bits.
+template <class E>
+__global__ __launch_bounds__(64) void k_rollout_vjp_lin(Task T, Dev d, Vjp V, const float* g_act, Lin P, int t_steps) {
+    typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    const cfp W = (cfp)P.w;
+    const unsigned kinds = P.kinds;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    float c[E::K];
+    load_consts<E, false>(d, i, c, 0, E::KS);
+    // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (bits behind t_steps may be stale)
+    int L = 0;
+    if (valid) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = d.traj_done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    float lam[NS], x[NI], out[NI], gob[E::O], gpol[E::O];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = (valid && V.g_last) ? V.g_last[(size_t)k * ld + i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = 0.f;
+#pragma unroll
+    for (int q = 0; q < E::O; ++q) gpol[q] = 0.f;
+
+    for (int t = t_steps - 1; t >= 0; --t) {
+#pragma unroll
+        for (int k = 0; k < NI; ++k) out[k] = 0.f;
+        if (t < L) {
+            load_record_inputs<E>(d.traj_rec + (size_t)t * Rec<E, 2>::F * ld, ld, i, x);
+            const float grew = V.g_rew ? V.g_rew[(size_t)t * ld + i] : 0.f;
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[((size_t)(t + 1) * E::O + q) * ld + i] : 0.f) + gpol[q];
+            vjp_step<E>(T, c, x, t, lam, grew, gob, out);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) lam[k] = out[k];
+            // ---- the total adjoint of a_t
+            float ab[E::A];
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) {
+                ab[j] = g_act ? out[NS + j] + g_act[((size_t)t * E::A + j) * ld + i] : out[NS + j];
+                out[NS + j] = ab[j];
+            }
+            // ---- what the policy saw of obs_t, as in k_rollout_lin
+            float ob[E::O], xv[E::O], gx[E::O];
+            E::observe(x, ob);
+            if (P.ident) {
+#pragma unroll
+                for (int k = 0; k < E::O; ++k) xv[k] = ob[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < E::O; ++k) {
+                    float v = 0.f;
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                    xv[k] = v;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < E::O; ++k) gx[k] = gpol[k] = 0.f;
+            // ---- gx[k] += (sum_j abar[j] W[j][slot of (q, k)]) phi_q'(x_k), kind by kind  (df: the derivative as an expression of v)
+#define VS_LINB_KIND(q, df)                                                                           \
+    if (kinds & (1u << (q))) {                                                                        \
+        _Pragma("unroll") for (int k = 0; k < E::O; ++k) {                                            \
+            const float v = xv[k];                                                                    \
+            float wb = 0.f;                                                                           \
+            _Pragma("unroll") for (int j = 0; j < E::A; ++j)                                          \
+                wb = fmaf(W[j * LIN_SLOTS + (q) * MAXO + k], ab[j], wb);                              \
+            gx[k] = fmaf(wb, (df), gx[k]);                                                            \
+        }                                                                                             \
+    }
+            VS_LINB_KIND(LIN_ID, 1.0f + 0.f * v)
+            VS_LINB_KIND(LIN_ABS, v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.f))
+            VS_LINB_KIND(LIN_SQ, 2.0f * v)
+            VS_LINB_KIND(LIN_CUBIC, 3.0f * (v * v))
+            if (kinds & (1u << LIN_SIG)) {
+#pragma unroll
+                for (int k = 0; k < E::O; ++k) {
+                    const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * xv[k]));
+                    float wb = 0.f;
+#pragma unroll
+                    for (int j = 0; j < E::A; ++j) wb = fmaf(W[j * LIN_SLOTS + LIN_SIG * MAXO + k], ab[j], wb);
+                    gx[k] = fmaf(wb, sg * (1.0f - sg), gx[k]);
+                }
+            }
+            VS_LINB_KIND(LIN_BELL, -v * __builtin_amdgcn_exp2f(-0.7213475204444817f * (v * v)))
+#undef VS_LINB_KIND
+            if (kinds & ((1u << LIN_SIN) | (1u << LIN_COS) | (1u << LIN_SINSIN) | (1u << LIN_SINCOS))) {
+                float sn[E::O], cs[E::O];
+#pragma unroll
+                for (int k = 0; k < E::O; ++k) sincos_fast(xv[k], &sn[k], &cs[k]);
+#define VS_LINB_TRIG(q, df)                                                                           \
+    if (kinds & (1u << (q))) {                                                                        \
+        _Pragma("unroll") for (int k = 0; k < E::O; ++k) {                                            \
+            float wb = 0.f;                                                                           \
+            _Pragma("unroll") for (int j = 0; j < E::A; ++j)                                          \
+                wb = fmaf(W[j * LIN_SLOTS + (q) * MAXO + k], ab[j], wb);                              \
+            gx[k] = fmaf(wb, (df), gx[k]);                                                            \
+        }                                                                                             \
+    }
+                VS_LINB_TRIG(LIN_SIN, cs[k])
+                VS_LINB_TRIG(LIN_COS, -sn[k])
+                VS_LINB_TRIG(LIN_SINSIN, 2.0f * (sn[k] * cs[k]))
+                VS_LINB_TRIG(LIN_SINCOS, cs[k] * cs[k] - sn[k] * sn[k])
+#undef VS_LINB_TRIG
+            }
+            // ---- gx back to observation rows: the elementwise part of the next gpol
+            if (P.ident) {
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) gpol[j] = gx[j];
+            } else {
+#pragma unroll
+                for (int k = 0; k < E::O; ++k)
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) gpol[j] += (k < P.n_vis && P.obs_idx[k] == j) ? gx[k] : 0.f;  // wave-uniform selects
+            }
+            for (int e = 0; e < P.n_x; ++e) {  // MultFeat / ATan2Feat terms (uniform); their rows are observation rows already
+                const unsigned xt = P.xterm[e];
+                float v[4], g[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = (int)((xt >> (3 * r)) & 7u);
+                    float u = 0.f;
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) u = row == j ? ob[j] : u;  // wave-uniform selects
+                    v[r] = u;
+                }
+                float wb = 0.f;
+#pragma unroll
+                for (int j = 0; j < E::A; ++j) wb = fmaf(W[j * LIN_SLOTS + LIN_CONST_SLOT + 1 + e], ab[j], wb);
+                int rows;
+                if (xt >> 31) {  // atan2(y = v[0], x = v[1])
+                    rows = 2;
+                    const float q = wb / fmaf(v[1], v[1], v[0] * v[0]);
+                    g[0] = v[1] * q;
+                    g[1] = -v[0] * q;
+                    g[2] = g[3] = 0.f;
+                } else {  // the product rule per position
+                    rows = 2 + (int)((xt >> 12) & 3u);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float p = wb;
+#pragma unroll
+                        for (int r2 = 0; r2 < 4; ++r2) p = (r2 != r && r2 < rows) ? p * v[r2] : p;
+                        g[r] = p;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = (int)((xt >> (3 * r)) & 7u);
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) gpol[j] += (r < rows && row == j) ? g[r] : 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = out[NS + j];
+    }
+    if (L > 0) {  // x is row 0 here: every lane with a rollout ran t = 0 last
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[(size_t)q * ld + i] : 0.f) + gpol[q];
+        vjp_observe<E>(x, gob, lam);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -3436,6 +3628,7 @@ struct Launch {
     static void rollout_play(vs_env* h, int k, int rec);                      // ... playback of recorded actions (+ discrepancy)
     static void rollout_play_sens(vs_env* h, int k);                          // ... and its parameter sensitivities (vs_set_rollout_sens)
     static void rollout_vjp(vs_env* h, const Vjp& v, int t_steps);            // vs_rollout_vjp
+    static void rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_policy
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -3709,6 +3902,15 @@ void Launch<E>::rollout_vjp(vs_env* h, const Vjp& v, int t_steps) {
     if constexpr (!std::is_same<E, BobD>::value)
         hipLaunchKernelGGL((k_rollout_vjp<E>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, t_steps);
     else no_kernel("rollout_vjp");
+}
+
+template <class E>
+void Launch<E>::rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int t_steps) {
+    // the shape of rollout_vjp; the discrete-action family takes no linear policy
+    if constexpr (!std::is_same<E, BobD>::value)
+        hipLaunchKernelGGL((k_rollout_vjp_lin<E>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, g_act, h->lin,
+                           t_steps);
+    else no_kernel("rollout_vjp_lin");
 }
 
 template <class E>

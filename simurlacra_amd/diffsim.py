@@ -9,6 +9,11 @@ written in torch over the observations and rewards of a rollout.
 
 Conventions are those of the kernel: the raw action is the variable (ActNormWrapper's map, the clip and the dead zone are inside
 the step, kinks follow the branch taken), domain parameters and the initial hidden state are constants.
+
+DifferentiablePolicyRollout is the closed-loop form: a LinearPolicy on a feature stack runs inside the recording launch
+(vs_set_policy_linear), and the backward pass is one closed-loop sweep (vs_rollout_vjp_policy, k_rollout_vjp_lin) -- the action's
+dependence on the observation is part of the adjoint -- followed by one batched torch pass over the recorded observations for the
+gradient of the policy's parameters.
 """
 from typing import Optional, Sequence
 
@@ -33,18 +38,12 @@ def discounted_return(rew, lengths, gamma: float):
     return (rew * (disc[None, :] * inside)).sum(dim=1)
 
 
-class DifferentiableRollout:
-    """rollout = DifferentiableRollout(env);  obs, rew, lengths = rollout(actions, init_states, domain_params=None)
+class _RecordedBatches:
+    """What the two rollout classes share: the env checks, one handle per batch of at most batch_lanes lanes, and a token per handle
+    that says which rollouts its records hold, so that a backward pass re-records only after another forward call overwrote them."""
 
-    env: one of the pysim envs, optionally inside an ActNormWrapper (the actions are then in [-1, 1] units); any other wrapper and
-    the discrete-action family raise ValueErr.  actions [N, T, A] and init_states [N, S] (the FULL state every rollout starts
-    from) are float32 tensors on the env's device.  Returns obs [N, T + 1, O] (row k: the observation after k steps), rew [N, T]
-    and lengths [N] (int64: the steps a rollout took before its episode ended); rows behind a rollout's end are 0.  obs and rew
-    carry gradients to actions and init_states; domain_params -- a list of N dicts or an [N, n_names] array with names=, as for
-    TrajectoryMatchSampler.param_matrix; None: the env's own -- gets none.  More than batch_lanes rollouts run in batches."""
-
-    def __init__(self, env, batch_lanes: int = 65536):
-        self._base, self._act_norm = check_playback_env(env, "DifferentiableRollout")
+    def __init__(self, env, who: str, batch_lanes: int):
+        self._base, self._act_norm = check_playback_env(env, who)
         if batch_lanes < 1:
             raise ValueErr(given=batch_lanes, ge_constraint="1")
         self.env = env
@@ -67,9 +66,12 @@ class DifferentiableRollout:
         b = self._base
         return b.act_space.flat_dim, b.state_space.flat_dim, b.obs_space.flat_dim
 
-    def _record(self, b, token, actions, init_states, params):
-        """the recording playback launch of one batch on its handle; a handle that still holds these records is left alone"""
-        n, T = actions.shape[0], actions.shape[1]
+    def _batches(self, N):
+        return [(n0, min(n0 + self._batch_lanes, N)) for n0 in range(0, N, self._batch_lanes)]
+
+    def _recorded(self, b, token, n, launch):
+        """the handle of batch b with the records `token` names: launch(handle) records them (on the caller's stream) unless the
+        handle still holds them"""
         slot = self._vecs.get(b)
         if slot is not None and slot[0].n_envs != n:
             slot[0].close()
@@ -83,15 +85,38 @@ class DifferentiableRollout:
             return v
         v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
         try:
+            launch(v)
+        finally:
+            v.use_stream(None)
+        slot[1] = token
+        return v
+
+
+class DifferentiableRollout(_RecordedBatches):
+    """rollout = DifferentiableRollout(env);  obs, rew, lengths = rollout(actions, init_states, domain_params=None)
+
+    env: one of the pysim envs, optionally inside an ActNormWrapper (the actions are then in [-1, 1] units); any other wrapper and
+    the discrete-action family raise ValueErr.  actions [N, T, A] and init_states [N, S] (the FULL state every rollout starts
+    from) are float32 tensors on the env's device.  Returns obs [N, T + 1, O] (row k: the observation after k steps), rew [N, T]
+    and lengths [N] (int64: the steps a rollout took before its episode ended); rows behind a rollout's end are 0.  obs and rew
+    carry gradients to actions and init_states; domain_params -- a list of N dicts or an [N, n_names] array with names=, as for
+    TrajectoryMatchSampler.param_matrix; None: the env's own -- gets none.  More than batch_lanes rollouts run in batches."""
+
+    def __init__(self, env, batch_lanes: int = 65536):
+        super().__init__(env, "DifferentiableRollout", batch_lanes)
+
+    def _record(self, b, token, actions, init_states, params):
+        """the recording playback launch of one batch on its handle; a handle that still holds these records is left alone"""
+        T = actions.shape[1]
+
+        def launch(v):
             v.set_params(params)
             v.set_policy_playback(actions)                          # one recording per lane: lane i replays recording i
             v.reset(init_state=init_states.detach().cpu().numpy())
             v.set_traj_offset(0)
             v.step_policy(T, record=True)
-        finally:
-            v.use_stream(None)
-        slot[1] = token
-        return v
+
+        return self._recorded(b, token, actions.shape[0], launch)
 
     def __call__(self, actions, init_states, domain_params=None, names: Optional[Sequence[str]] = None):
         A, S, _ = self._dims()
@@ -111,9 +136,6 @@ class DifferentiableRollout:
         self._calls += 1
         obs, rew, lengths = _RolloutFn.apply(self, self._calls, params, actions, init_states)
         return obs, rew, lengths
-
-    def _batches(self, N):
-        return [(n0, min(n0 + self._batch_lanes, N)) for n0 in range(0, N, self._batch_lanes)]
 
     def _forward(self, call, params, actions, init_states):
         A, S, O = self._dims()
@@ -172,3 +194,139 @@ class _RolloutFn(torch.autograd.Function):
         actions, init_states = ctx.saved_tensors
         d_act, d_init = ctx.roll._backward(ctx.call, ctx.params, actions.detach(), init_states.detach(), grad_obs, grad_rew)
         return None, None, None, d_act, d_init
+
+
+class DifferentiablePolicyRollout(_RecordedBatches):
+    """roll = DifferentiablePolicyRollout(env, policy);  obs, rew, act, lengths = roll(init_states, T, domain_params=None)
+
+    Closed-loop rollouts of a LinearPolicy on a FeatureStack that linear_kernel_spec accepts (optionally inside a
+    NormalActNoiseExplStrat; any other policy raises TypeErr, a stack the kernel cannot take ValueErr), attached to torch autograd.
+    env: as for DifferentiableRollout.  init_states [N, S] is a float32 tensor on the env's device, T the number of steps.  Returns
+    obs [N, T + 1, O], rew [N, T], act [N, T, A] (the raw policy actions, exploration noise included) and lengths [N] (int64);
+    rows behind a rollout's end are 0.  obs, rew and act carry gradients to init_states and to policy.parameters() -- through the
+    dynamics AND through the policy's dependence on the observations.  The exploration noise (keyed by noise_seed) is a constant
+    of the graph: its std gets no gradient; domain_params get none either.
+    Forward: set_policy_linear from the module's current weights, reset(init_state), one recording step_policy(T).  Backward: one
+    rollout_vjp_policy per batch for the action adjoints and d init_states, then ONE batched pass of the policy over the recorded
+    [N T] observations for the parameter gradients."""
+
+    def __init__(self, env, policy, batch_lanes: int = 65536):
+        from .policies import LinearPolicy, NormalActNoiseExplStrat, linear_kernel_spec
+
+        inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
+        if not isinstance(inner, LinearPolicy):
+            raise TypeErr(msg="DifferentiablePolicyRollout takes a LinearPolicy, optionally inside a NormalActNoiseExplStrat, got "
+                              f"{type(inner).__name__}")
+        spec = linear_kernel_spec(policy)
+        if spec is None:
+            raise ValueErr(msg=f"the rollout kernel cannot evaluate {inner.features}: every elementwise feature and const_feat at "
+                               "most once, MultFeat of 2 .. 4 rows, ATan2Feat, at most 39 of those two and 128 features in all")
+        super().__init__(env, "DifferentiablePolicyRollout", batch_lanes)
+        A, _, O = self._dims()
+        if inner.env_spec.obs_space.flat_dim != O or inner.env_spec.act_space.flat_dim != A:
+            raise ShapeErr(msg=f"the policy maps {inner.env_spec.obs_space.flat_dim} observation rows to "
+                               f"{inner.env_spec.act_space.flat_dim} actions, the env has {O} and {A}")
+        self.policy, self._mean, self._terms = policy, inner, spec["terms"]
+
+    def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0):
+        from .policies import linear_kernel_spec
+
+        _, S, _ = self._dims()
+        if not hasattr(init_states, "dim"):
+            raise TypeErr(msg="init_states must be a torch tensor")
+        if init_states.dim() != 2 or init_states.shape[1] != S or init_states.shape[0] < 1:
+            raise ShapeErr(msg=f"init_states must be [N, {S}], got shape {tuple(init_states.shape)}")
+        if int(T) < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        N = init_states.shape[0]
+        params = domain_param_matrix(self._base, [dict()] * N if domain_params is None else domain_params, names)
+        if params.shape[0] != N:
+            raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
+        if not init_states.is_cuda or init_states.dtype != torch.float32:
+            raise TypeErr(msg="init_states must be a float32 tensor on the GPU")
+        noise_std = linear_kernel_spec(self.policy)["noise_std"]     # (the std may have been updated since the constructor)
+        self._calls += 1
+        setup = (self, self._calls, params, int(T), noise_std, int(noise_seed))
+        obs, rew, act, lengths = _PolicyRolloutFn.apply(setup, init_states, *self._mean.parameters())
+        return obs, rew, act, lengths
+
+    def _record(self, b, setup, n0, n1, init_states, weight):
+        """the recording closed-loop launch of one batch (rollouts n0 .. n1 - 1) on its handle; a handle that still holds these
+        records is left alone"""
+        _, call, params, T, noise_std, noise_seed = setup
+
+        def launch(v):
+            v.set_params(params[n0:n1])
+            v.set_policy_linear(weight.detach().to(torch.float32).reshape(-1), self._terms, noise_std=noise_std)
+            v.reset(init_state=init_states[n0:n1].detach().cpu().numpy())
+            v.set_traj_offset(0)
+            v.step_policy(T, record=True, noise_seed=noise_seed)
+
+        return self._recorded(b, (call, b), n1 - n0, launch)
+
+    def _forward(self, setup, init_states, weight):
+        A, S, O = self._dims()
+        N, T, dev = init_states.shape[0], setup[3], init_states.device
+        obs = torch.empty(N, T + 1, O, dtype=torch.float32, device=dev)
+        rew = torch.empty(N, T, dtype=torch.float32, device=dev)
+        act = torch.empty(N, T, A, dtype=torch.float32, device=dev)
+        lengths = torch.empty(N, dtype=torch.int64, device=dev)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, setup, n0, n1, init_states, weight)
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                tt = v.traj_tensors(T, n)
+                lengths[n0:n1] = v.rollout_lengths(n, T)[0]
+                obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
+                obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
+                rew[n0:n1] = tt["rew"].t()
+                act[n0:n1] = tt["act"].transpose(0, 1)
+            finally:
+                v.use_stream(None)
+        steps = torch.arange(T + 1, device=dev)
+        inside = (steps[None, :T] < lengths[:, None]).to(torch.float32)
+        obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
+        return obs, rew * inside, act * inside[:, :, None], lengths
+
+    def _backward(self, setup, init_states, weight, grad_obs, grad_rew, grad_act):
+        """(gradients of the policy's parameters, d init_states)"""
+        A, S, O = self._dims()
+        N, T, dev = init_states.shape[0], setup[3], init_states.device
+        abar = torch.empty(N, T, A, dtype=torch.float32, device=dev)
+        seen = torch.empty(N, T, O, dtype=torch.float32, device=dev)
+        d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, setup, n0, n1, init_states, weight)
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
+                da, di = v.rollout_vjp_policy(T, g_rew=g[0], g_obs=g[1], g_act=g[2])
+                abar[n0:n1] = lanes_first(da, n)                   # (0 behind a rollout's end: the kernel writes it so)
+                d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
+                seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
+            finally:
+                v.use_stream(None)
+        params = list(self._mean.parameters())
+        with torch.enable_grad():
+            mean = self._mean(seen.detach().reshape(N * T, O))      # one batched pass over the [N T] recorded observations
+            d_params = torch.autograd.grad(mean, params, grad_outputs=abar.reshape(N * T, A).to(device=mean.device, dtype=mean.dtype))
+        return d_params, d_init
+
+
+class _PolicyRolloutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, setup, init_states, *params):
+        roll = setup[0]
+        obs, rew, act, lengths = roll._forward(setup, init_states.detach(), params[0].detach())
+        ctx.setup = setup
+        ctx.save_for_backward(init_states, *params)
+        ctx.mark_non_differentiable(lengths)
+        return obs, rew, act, lengths
+
+    @staticmethod
+    def backward(ctx, grad_obs, grad_rew, grad_act, _grad_lengths):
+        init_states, *params = ctx.saved_tensors
+        d_params, d_init = ctx.setup[0]._backward(ctx.setup, init_states.detach(), params[0].detach(), grad_obs, grad_rew, grad_act)
+        return (None, d_init) + tuple(d_params)

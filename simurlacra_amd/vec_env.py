@@ -836,20 +836,15 @@ class VecSimEnv:
         self._check(self._lib.vs_step_policy(self._h, int(k_steps), int(bool(record)), int(noise_seed) & (2 ** 64 - 1)),
                     "vs_step_policy")
 
-    def rollout_vjp(self, t_steps, g_rew=None, g_obs=None, g_state_last=None):
-        """Reverse-mode sweep over the recorded rollouts in rows 0 .. t_steps - 1 (vs_rollout_vjp; record mode 2, auto-reset off,
-        trajectory offset 0): the gradient of  sum g_rew r + sum g_obs . obs + g_state_last . (s_L, h_L)  per lane with respect to
-        the raw actions and the initial state.  Cotangents are float32 device tensors in the kernels' layout (lanes_last) or None
-        for 0: g_rew [T, ld], g_obs [T + 1, O, ld] (row k: the observation after k steps), g_state_last [S + H, ld].
-        Returns (d_act [T, A, ld], d_init [S + H, ld]) on the device; rows behind a lane's end and lanes >= n_envs are 0."""
+    def _vjp_args(self, t_steps, cotangents):
+        """(T, ctypes pointers of the optional cotangents [(name, tensor or None, shape)], d_act, d_init) of the two sweeps"""
         import torch
 
         T = int(t_steps)
-        S, A, O, H = (self.dims[k] for k in "SAOH")
+        S, A, H = (self.dims[k] for k in "SAH")
         dev = torch.device(f"cuda:{self.device}")
         ptrs = []
-        for name, g, shape in (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
-                               ("g_state_last", g_state_last, (S + H, self.ld))):
+        for name, g, shape in cotangents:
             if g is None:
                 ptrs.append(None)
                 continue
@@ -862,8 +857,34 @@ class VecSimEnv:
             raise ValueErr(given=T, ge_constraint="1")
         d_act = torch.empty(T, A, self.ld, dtype=torch.float32, device=dev)
         d_init = torch.empty(S + H, self.ld, dtype=torch.float32, device=dev)
+        return T, ptrs, d_act, d_init
+
+    def rollout_vjp(self, t_steps, g_rew=None, g_obs=None, g_state_last=None):
+        """Reverse-mode sweep over the recorded rollouts in rows 0 .. t_steps - 1 (vs_rollout_vjp; record mode 2, auto-reset off,
+        trajectory offset 0): the gradient of  sum g_rew r + sum g_obs . obs + g_state_last . (s_L, h_L)  per lane with respect to
+        the raw actions and the initial state.  Cotangents are float32 device tensors in the kernels' layout (lanes_last) or None
+        for 0: g_rew [T, ld], g_obs [T + 1, O, ld] (row k: the observation after k steps), g_state_last [S + H, ld].
+        Returns (d_act [T, A, ld], d_init [S + H, ld]) on the device; rows behind a lane's end and lanes >= n_envs are 0."""
+        T = int(t_steps)
+        S, O, H = (self.dims[k] for k in "SOH")
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_state_last", g_state_last, (S + H, self.ld))))
         self._check(self._lib.vs_rollout_vjp(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
                     "vs_rollout_vjp")
+        return d_act, d_init
+
+    def rollout_vjp_policy(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
+        """The sweep of rollout_vjp for closed-loop records (vs_rollout_vjp_policy): rows 0 .. t_steps - 1 were recorded by
+        step_policy with the linear policy of set_policy_linear that is still on the handle, a_t = W phi(obs_t) + n_t with the
+        exploration noise n_t a constant.  One more cotangent, g_act [T, A, ld], on the raw policy action.  Returns
+        (d_act [T, A, ld], d_init [S + H, ld]): d_act[t] is the TOTAL adjoint of a_t (= d Phi / d n_t; the parameter gradient is
+        sum_t d_act[t] phi(obs_t)^T), d_init includes the feedback through the policy."""
+        T = int(t_steps)
+        S, A, O, H = (self.dims[k] for k in "SAOH")
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld))))
+        self._check(self._lib.vs_rollout_vjp_policy(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
+                    "vs_rollout_vjp_policy")
         return d_act, d_init
 
     def sync(self):

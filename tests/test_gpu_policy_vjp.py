@@ -1,0 +1,556 @@
+"""
+vs_rollout_vjp_policy / k_rollout_vjp_lin: the reverse-mode sweep over CLOSED-LOOP recorded rollouts (a linear policy on a feature stack
+in the loop), VecSimEnv.rollout_vjp_policy and DifferentiablePolicyRollout.
+
+Shapes are those of test_gpu_rollout_vjp.py: 150 lanes (three waves, the last one partial), T = 24 steps, max_steps = 50, +-5 % per-lane
+parameters, lanes 0 .. 9 start at the edge of the state space and end early, random cotangents on all four cotangent inputs.
+
+The reference is a closed-loop fp64 rollout: oracle.cpu_ref for the step, the NumPy feature stack below for the policy,
+a_t = W phi(obs_t) + n_t with an additive per-step offset n_t (0 unless a test says otherwise).  Central differences of Phi at relative
+steps 1e-6 and 1e-5 with respect to every n_t entry (-> d_act, the total adjoint of a_t) and every initial-state entry (-> d_init), the
+lane's length held at its unperturbed value, per unit of the input's scale (ACT_IN, INIT_SCALE).  Tolerance, per lane, the project's:
+3e-3 |g| + 3e-4 max |g_smooth|, at most a 2e-3 share of bad entries, entries smooth where the two step sizes agree to 1e-4, at most 1 %
+not smooth (asserted from the oracle alone).
+
+The weights keep every lane inside the action box and outside the dead zones for all 24 steps: the const feature is a bias of
++-0.45 ACT_IN, every other feature f has the weight +-0.12 ACT_IN / (F max |phi_f|), the maximum taken over a rollout under the bias
+alone, so that their sum stays within +-0.15 ACT_IN (asserted on the oracle's closed loop).
+"""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from oracle import cpu_ref
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+KW = {"omo": dict(dt=0.02), "bob": dict(dt=0.01), "qq-su": dict(dt=0.004), "qcp-su": dict(dt=0.002), "pend": dict(dt=0.01),
+      "qbb": dict(dt=0.01)}
+ACT_IN = {"omo": 10.0, "bob": 10.0, "qq-su": 4.0, "qcp-su": 5.0, "pend": 3.0, "qbb": 2.5}
+INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
+              "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
+N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
+
+ELEM = ("identity", "squared", "cubic", "sig", "bell", "sin", "cos", "sinsin", "sincos")
+SMALL = ("identity", "sin", "const", ("mult", (0, 1)))
+# case -> (family, the stack in order, obs_idx or None)
+CASES = {
+    "qq-su": ("qq-su", ELEM + ("const", ("mult", (4, 5)), ("mult", (0, 4, 0)), ("atan2", (0, 1))), None),
+    "omo": ("omo", ELEM + ("const", ("mult", (0, 1)), ("mult", (1, 0, 1))), None),
+    "omo-kinks": ("omo", ("identity", "sign", "abs", "const", ("mult", (0, 1))), None),
+    "bob": ("bob", SMALL, None),
+    "qcp-su": ("qcp-su", SMALL, None),
+    "pend-view": ("pend", SMALL, (2, 0)),          # the policy sees (th_dot, sin th): a permuted strict subset of the rows
+    "qbb": ("qbb", SMALL, None),
+    "pend-const": ("pend", ("const",), None), "omo-const": ("omo", ("const",), None), "bob-const": ("bob", ("const",), None),
+    "qq-su-const": ("qq-su", ("const",), None), "qcp-su-const": ("qcp-su", ("const",), None), "qbb-const": ("qbb", ("const",), None),
+}
+ORACLE_CASES = ["qq-su", "omo", "omo-kinks", "bob", "qcp-su", "pend-view", "qbb"]
+
+
+@pytest.fixture(scope="module")
+def vs():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import simurlacra_amd
+
+    return simurlacra_amd
+
+
+def edge_states(name, init):
+    """lanes 0 .. N_EDGE - 1 start at the edge of the state space, moving out: they end early"""
+    init = init.copy()
+    e = slice(0, N_EDGE)
+    if name == "qbb":
+        init[e, 2], init[e, 6] = 0.13, 0.45
+    elif name == "qq-su":
+        init[e, 0], init[e, 2] = 2.0, 5.0
+    elif name == "bob":
+        init[e, 0], init[e, 2] = 0.98, 3.0
+    elif name == "omo":
+        init[e, 0], init[e, 1] = 0.98, 5.0
+    elif name == "qcp-su":
+        init[e, 0], init[e, 2] = 0.25, 0.6
+    else:  # pend
+        init[e, 0], init[e, 1] = 12.5, 5.0
+    return init
+
+
+# ------------------------------------------------------------------------------------------------ the fp64 feature stack
+def features(terms, x):
+    """phi [n, F] of the visible rows x [n, n_vis] (fp64), the stack in order"""
+    sg = 1.0 / (1.0 + np.exp(-x))
+    elem = {"identity": x, "sign": np.sign(x), "abs": np.abs(x), "squared": x ** 2, "cubic": x ** 3, "sig": sg,
+            "bell": np.exp(-x ** 2 / 2.0), "sin": np.sin(x), "cos": np.cos(x), "sinsin": np.sin(x) ** 2, "sincos": np.sin(x) * np.cos(x)}
+    cols = []
+    for t in terms:
+        if t == "const":
+            cols.append(np.ones((x.shape[0], 1)))
+        elif isinstance(t, str):
+            cols.append(elem[t])
+        elif t[0] == "mult":
+            cols.append(np.prod(x[:, list(t[1])], axis=1, keepdims=True))
+        else:
+            cols.append(np.arctan2(x[:, t[1][0]], x[:, t[1][1]])[:, None])
+    return np.concatenate(cols, axis=1)
+
+
+def closed_loop(ref, params, state0, hidden0, terms, obs_idx, W, offs, open_acts=None):
+    """the fp64 oracle under a_t = W phi(obs_t) + offs[:, t] (it does not freeze at done), or along open_acts [n, T, A] ->
+    states [T + 1, n, S], hiddens [T + 1, n, H], obs [T + 1, n, O], rew [T, n], done [T, n], acts [T, n, A]"""
+    st, hid = state0.copy(), hidden0.copy()
+    ob = ref.observe(st)
+    states, hiddens, obs, rew, done, acts = [st], [hid], [ob], [], [], []
+    with np.errstate(all="ignore"):
+        for t in range(offs.shape[1]):
+            if open_acts is None:
+                x = ob if obs_idx is None else ob[:, list(obs_idx)]
+                a = features(terms, x) @ W.T + offs[:, t]
+            else:
+                a = open_acts[:, t]
+            out = ref.step(st, hid, a, params, np.full(st.shape[0], t))
+            st, hid, ob = out["state"], out["hidden"], out["obs"]
+            states.append(st), hiddens.append(hid), obs.append(ob), rew.append(out["rew"]), done.append(out["done"]), acts.append(a)
+    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done), np.stack(acts)
+
+
+def lengths_of(done):
+    return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
+
+
+def make_weights(ref, name, terms, obs_idx, params, s0, h0, rng, n_steps):
+    """W [A, F] float32 (see the module docstring)"""
+    n_vis = ref.O if obs_idx is None else len(obs_idx)
+    F = features(terms, np.zeros((1, n_vis))).shape[1]
+    const_at = [q for q, on in enumerate(_const_mask(terms, n_vis)) if on]
+    W = np.zeros((ref.A, F))
+    if const_at:
+        W[:, const_at[0]] = 0.45 * ACT_IN[name] * rng.choice([-1.0, 1.0], ref.A)
+    obs = closed_loop(ref, params, s0, h0, terms, obs_idx, W, np.zeros((s0.shape[0], n_steps, ref.A)))[2]
+    x = obs.reshape(-1, ref.O)
+    x = x if obs_idx is None else x[:, list(obs_idx)]
+    top = np.maximum(np.abs(features(terms, x)).max(axis=0), 1e-3)
+    for q in range(F):
+        if q not in const_at:
+            W[:, q] = 0.12 * ACT_IN[name] / (F * top[q]) * rng.choice([-1.0, 1.0], ref.A)
+    return W.astype(np.float32)
+
+
+def _const_mask(terms, n_vis):
+    out = []
+    for t in terms:
+        out += [t == "const"] * (n_vis if isinstance(t, str) and t != "const" else 1)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(key):
+    """the inputs of a case, float32 and left unchanged by the tests: params [N, P], init [N, S], W [A, F] and the cotangents
+    g_rew [N, T], g_obs [N, T + 1, O], g_act [N, T, A], g_last [N, S + H]"""
+    name, terms, obs_idx = CASES[key]
+    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
+    rng = np.random.default_rng(29)
+    nominal = ref.nominal_params(1).astype(np.float32)[0]
+    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
+    init = edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
+    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
+    W = make_weights(ref, name, terms, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T)
+    c = dict(name=name, terms=terms, obs_idx=obs_idx, ref=ref, params=params, init=init, h0=h0, W=W,
+             g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
+             g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
+    for v in c.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+def phi(c, state0, offs, length, open_acts=None):
+    """[N]: sum g_rew r + sum g_obs . obs + sum g_act . a + g_last . (s_L, h_L) of every lane over its first length[n] steps"""
+    states, hiddens, obs, rew, _, acts = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"], c["terms"], c["obs_idx"],
+                                                     c["W"].astype(np.float64), offs, open_acts)
+    k = np.arange(T + 1)[:, None]
+    n = np.arange(state0.shape[0])
+    inside = k[:T] < length[None, :]
+    out = np.where(inside, c["g_rew"].T.astype(np.float64) * rew, 0.0).sum(axis=0)
+    out += np.where(inside[:, :, None], c["g_act"].transpose(1, 0, 2).astype(np.float64) * acts, 0.0).sum(axis=(0, 2))
+    out += np.where((k <= length[None, :])[:, :, None], c["g_obs"].transpose(1, 0, 2).astype(np.float64) * obs, 0.0).sum(axis=(0, 2))
+    last = np.concatenate([states[length, n], hiddens[length, n]], axis=1)
+    return out + (c["g_last"].astype(np.float64) * last).sum(axis=1)
+
+
+def reference(c, offs0):
+    """central differences of Phi at relative steps 1e-6 and 1e-5: two arrays [N, T * A + S] (offsets first, step-major), the
+    oracle's lane lengths, its actions [T, N, A], and d_init [N, S] of the OPEN loop along those actions (step 1e-6)"""
+    ref, name = c["ref"], c["name"]
+    s0 = c["init"].astype(np.float64)
+    roll = closed_loop(ref, c["params"].astype(np.float64), s0, c["h0"], c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)
+    length, acts = lengths_of(roll[4]), roll[5]
+    out = []
+    for h in (1e-6, 1e-5):
+        g = np.zeros((N, T * ref.A + ref.S))
+        for t in range(T):
+            for j in range(ref.A):
+                d = np.zeros_like(offs0)
+                d[:, t, j] = h * ACT_IN[name]
+                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length) - phi(c, s0, offs0 - d, length)) / (2.0 * h)
+        for j in range(ref.S):
+            d = np.zeros_like(s0)
+            d[:, j] = h * INIT_SCALE[name][j]
+            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length) - phi(c, s0 - d, offs0, length)) / (2.0 * h)
+        out.append(g)
+    open_init = np.zeros((N, ref.S))
+    fixed = acts.transpose(1, 0, 2)
+    for j in range(ref.S):
+        d = np.zeros_like(s0)
+        d[:, j] = 1e-6 * INIT_SCALE[name][j]
+        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed) - phi(c, s0 - d, offs0, length, fixed)) / 2e-6
+    return out[0], out[1], length, acts, open_init
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_reference(key):
+    c = case(key)
+    return reference(c, np.zeros((N, T, c["ref"].A)))
+
+
+def smooth_of(g1, g2):
+    mag = np.maximum(np.abs(g1), np.abs(g2))
+    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max(axis=1, keepdims=True))
+
+
+def tolerance(want, smooth):
+    top = np.where(smooth, np.abs(want), 0.0).max(axis=1, keepdims=True)
+    return 3e-3 * np.abs(want) + 3e-4 * np.where(smooth.any(axis=1, keepdims=True), top, 1.0)
+
+
+def within(got, want, smooth):
+    """the project's tolerance per lane on the smooth entries -> (share of bad entries, worst error / tolerance)"""
+    tol = tolerance(want, smooth)
+    err = np.abs(got - want)
+    bad = smooth & (err > tol)
+    return float(bad.mean()), float((err[smooth] / tol[smooth]).max())
+
+
+def dev(x):
+    return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
+
+
+def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0):
+    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case, recorded in mode 2 by step_policy in the given launches"""
+    c = case(key)
+    name = c["name"]
+    e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
+    e.set_auto_reset(False)
+    e.set_record_mode(2)
+    e.set_traj_capacity(T)
+    e.set_params(c["params"])
+    e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
+    e.reset(init_state=c["init"])
+    t0 = 0
+    for k in splits:
+        e.set_traj_offset(t0)
+        e.step_policy(k, record=True, noise_seed=noise_seed)
+        t0 += k
+    e.set_traj_offset(0)
+    return e
+
+
+def cotangents(vs, key, e, with_act=True):
+    c = case(key)
+    out = dict(g_rew=vs.lanes_last(dev(c["g_rew"]), e.ld), g_obs=vs.lanes_last(dev(c["g_obs"]), e.ld),
+               g_state_last=vs.lanes_last(dev(c["g_last"]), e.ld))
+    if with_act:
+        out["g_act"] = vs.lanes_last(dev(c["g_act"]), e.ld)
+    return out
+
+
+def scaled(vs, c, d_act, d_init):
+    ref, name = c["ref"], c["name"]
+    d_act, d_init = vs.lanes_first(d_act, N).cpu().numpy(), vs.lanes_first(d_init, N).cpu().numpy()
+    got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
+    assert np.isfinite(got).all()
+    return got.astype(np.float64)
+
+
+def check_policy_keeps_the_box(c, acts, length):
+    """the oracle's actions inside the lengths: the bias +- at most 0.15 ACT_IN, hence |a| in [0.30, 0.60] ACT_IN"""
+    W, name = c["W"].astype(np.float64), c["name"]
+    n_vis = c["ref"].O if c["obs_idx"] is None else len(c["obs_idx"])
+    bias = W[:, np.array(_const_mask(c["terms"], n_vis))].sum(axis=1)
+    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
+    assert (np.abs(np.where(inside, acts - bias, 0.0)) <= 0.15 * ACT_IN[name]).all(), name
+
+
+# ----------------------------------------------------------------------------------- 1. + 2. against the fp64 oracle
+@pytest.mark.parametrize("key", ORACLE_CASES)
+def test_against_the_closed_loop_fp64_oracle(vs, key):
+    """Worst error / tolerance measured on the MI355X (printed with -s): 0.012 (QQube, full stack), 0.001
+    (oscillator with either stack, cartpole, pendulum through obs_idx), below 0.0005 (ball-on-beam, ball balancer); every entry smooth,
+    no bad entry; the feedback is seen on 0.55 (cartpole) to 0.96 (ball balancer) of the full-length lanes."""
+    c = case(key)
+    ref = c["ref"]
+    f1, f2, length, acts, open_init = oracle_reference(key)
+    smooth = smooth_of(f1, f2)
+    assert (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
+    check_policy_keeps_the_box(c, acts, length)
+    assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
+    # ---- the test can see the feedback (oracle alone): closed- and open-loop d_init differ by more than 10 x the tolerance on at
+    # least half of the full-length lanes
+    init_cols = slice(T * ref.A, None)
+    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance(f1, smooth)[:, init_cols]
+    full = length == T
+    seen = float(gap.any(axis=1)[full].mean())
+    assert seen >= 0.5, (key, seen)
+    e = recorded(vs, key)
+    assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    got = scaled(vs, c, *e.rollout_vjp_policy(T, **cotangents(vs, key, e)))
+    assert e.error_count() == 0
+    e.close()
+    bad, worst = within(got, f1, smooth)
+    print(f"{key}: not smooth {(~smooth).mean():.4f}, feedback seen on {seen:.2f} of the full lanes, bad share {bad:.2e}, "
+          f"worst error / tolerance {worst:.3f}")
+    assert bad <= 2e-3, (key, bad, worst)
+
+
+# ------------------------------------------------------------------------------------ 3. reduction to the open-loop sweep
+@pytest.mark.parametrize("key", ["omo-const", "bob-const", "qq-su-const", "qcp-su-const", "pend-const", "qbb-const"])
+def test_a_constant_policy_reduces_to_the_open_loop_sweep(vs, key):
+    e = recorded(vs, key)
+    cot = cotangents(vs, key, e, with_act=False)
+    oa, oi = e.rollout_vjp(T, **cot)
+    pa, pi = e.rollout_vjp_policy(T, **cot)
+    assert torch.equal(pa, oa) and torch.equal(pi, oi) and bool(oa.any()) and bool(oi.any())
+    g_act = cotangents(vs, key, e)["g_act"]
+    ga, gi = e.rollout_vjp_policy(T, g_act=g_act, **cot)
+    length = e.rollout_lengths(N, T)[0]
+    inside = torch.zeros(T, 1, e.ld, device="cuda")
+    inside[:, 0, :N] = (torch.arange(T, device="cuda")[:, None] < length[None, :]).float()
+    assert torch.equal(ga, oa + g_act * inside) and torch.equal(gi, oi)
+    assert e.error_count() == 0
+    e.close()
+
+
+# ------------------------------------------------------------------------------------------------- 4. exact structure
+STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG")
+
+
+@pytest.mark.parametrize("key", ["qq-su", "qcp-su"])
+def test_exact_structure(vs, key):
+    L = vs._lib
+    e = recorded(vs, key, SPLITS)
+    cot = cotangents(vs, key, e)
+    before = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
+    da, di = e.rollout_vjp_policy(T, **cot)
+    for b, x in zip(STATE_BUFFERS, before):  # the handle's state, step counter and flags are untouched
+        assert np.array_equal(e.get(getattr(L, b)), x), b
+    assert e.ld > N and not da[..., N:].any() and not di[..., N:].any()
+    d_act = vs.lanes_first(da, N).cpu().numpy()
+    length = e.rollout_lengths(N, T)[0].cpu().numpy()
+    early = np.flatnonzero(length < T)
+    assert early.size > 0 and (early < N_EDGE).all()
+    for n in early:
+        assert not d_act[n, length[n]:].any() and d_act[n, :length[n]].all()
+    assert d_act[length == T].all() and bool(di[:, :N].any(dim=0).all())
+    for kw in ({k: torch.zeros_like(v) for k, v in cot.items()}, {}):  # zero cotangents, and none at all
+        za, zi = e.rollout_vjp_policy(T, **kw)
+        assert not za.any() and not zi.any()
+    one = recorded(vs, key)  # records made in one launch: the same bits
+    assert all(torch.equal(a, b) for a, b in zip(one.rollout_vjp_policy(T, **cot), (da, di)))
+    assert e.error_count() == 0 and one.error_count() == 0
+    one.close()
+    e.close()
+
+
+# ----------------------------------------------------------------------------------------------------------- 5. noise
+def test_exploration_noise_is_an_additive_constant(vs):
+    """The recorded raw action contains the noise: n_t = a_recorded - W phi(obs_recorded), taken from the records in fp64, is fed to
+    the oracle as a constant offset; the comparison is test 1's."""
+    key = "pend-view"
+    c = case(key)
+    ref = c["ref"]
+    e = recorded(vs, key, noise_std=np.full(ref.A, 0.02 * ACT_IN[c["name"]]), noise_seed=77)
+    tt = e.traj_tensors(T, N)
+    obs, act = tt["obs"].cpu().numpy().astype(np.float64), tt["act"].cpu().numpy().astype(np.float64)  # [T, N, .]
+    x = obs.reshape(T * N, ref.O)[:, list(c["obs_idx"])]
+    offs = (act - (features(c["terms"], x) @ c["W"].astype(np.float64).T).reshape(T, N, ref.A)).transpose(1, 0, 2)
+    assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
+    f1, f2, length, _, _ = reference(c, np.ascontiguousarray(offs))
+    smooth = smooth_of(f1, f2)
+    assert (~smooth).mean() <= 0.01
+    assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    got = scaled(vs, c, *e.rollout_vjp_policy(T, **cotangents(vs, key, e)))
+    assert e.error_count() == 0
+    e.close()
+    bad, worst = within(got, f1, smooth)
+    print(f"{key} + noise: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
+    assert bad <= 2e-3, (bad, worst)
+
+
+# ---------------------------------------------------------------------------------------------------------- 6. refusals
+def test_refusals_leave_the_outputs_untouched(vs):
+    L = vs._lib
+    lib = L.load()
+    key = "qq-su"
+    c = case(key)
+    d = vs.env_dims(c["name"])
+    e = recorded(vs, key)
+    d_act = torch.full((T, d["A"], e.ld), 7.0, device="cuda")
+    d_init = torch.full((d["S"] + d["H"], e.ld), 7.0, device="cuda")
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+
+    def call(handle, t_steps=T, out=(d_act, d_init)):
+        rc = lib.vs_rollout_vjp_policy(handle._h if handle is not None else None, t_steps, None, None, None, None,
+                                       ptr(out[0]) if out[0] is not None else None, ptr(out[1]) if out[1] is not None else None)
+        torch.cuda.synchronize()
+        return rc
+
+    def refused(code, *args, **kw):
+        assert call(*args, **kw) == code
+        assert bool((d_act == 7.0).all()) and bool((d_init == 7.0).all())  # the sentinels
+
+    def linear():
+        e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]))
+
+    refused(L.VS_ERR_ARG, None)
+    refused(L.VS_ERR_ARG, e, out=(None, d_init))
+    refused(L.VS_ERR_ARG, e, out=(d_act, None))
+    for t_steps in (0, -3, T + 1):
+        refused(L.VS_ERR_ARG, e, t_steps)
+    e.set_traj_offset(3)
+    refused(L.VS_ERR_STATE, e)
+    with pytest.raises(RuntimeError):  # the Python face raises
+        e.rollout_vjp_policy(T)
+    e.set_traj_offset(0)
+    e.set_auto_reset(True)
+    refused(L.VS_ERR_STATE, e)
+    e.set_auto_reset(False)
+    e.set_policy_population(np.tile(c["W"].reshape(1, -1), (3, 1)), lane_set=np.arange(N) // 64)
+    refused(L.VS_ERR_STATE, e)
+    e.set_policy_population(None)
+    assert call(e) == L.VS_OK and not bool((d_act == 7.0).any()) and not bool((d_init == 7.0).any())  # the same handle still serves
+    d_act.fill_(7.0), d_init.fill_(7.0)
+    e.set_policy_linear(None, None)                             # no policy
+    refused(L.VS_ERR_STATE, e)
+    n_fnn = (d["O"] + 1) * 8 + (8 + 1) * d["A"]
+    e.set_policy_fnn(np.zeros(n_fnn, dtype=np.float32), [8])    # an FNN policy
+    refused(L.VS_ERR_STATE, e)
+    e.set_policy_playback(np.zeros((N, T, d["A"]), dtype=np.float32))  # a playback policy
+    refused(L.VS_ERR_STATE, e)
+    linear()
+    assert call(e) == L.VS_OK
+    d_act.fill_(7.0), d_init.fill_(7.0)
+    e.set_record_mode(1)
+    e.set_traj_capacity(T)
+    refused(L.VS_ERR_STATE, e)
+    assert e.error_count() == 0
+    e.close()
+    disc = vs.VecSimEnv("bob-d", 64, dt=0.01, max_steps=MAX_STEPS)
+    disc.set_record_mode(2)
+    disc.set_traj_capacity(T)
+    o1, o2 = torch.full((T, 1, disc.ld), 7.0, device="cuda"), torch.full((4, disc.ld), 7.0, device="cuda")
+    assert lib.vs_rollout_vjp_policy(disc._h, T, None, None, None, None, ptr(o1), ptr(o2)) == L.VS_ERR_STATE
+    torch.cuda.synchronize()
+    assert bool((o1 == 7.0).all()) and bool((o2 == 7.0).all())
+    disc.close()
+
+
+# ----------------------------------------------------------------------------------------------------------- 7. autograd
+ENVS = {"qq-su": "QQubeSwingUpSim", "qcp-su": "QCartPoleSwingUpSim"}
+NT, TT, GAMMA = 70, 12, 0.99
+
+
+@functools.lru_cache(maxsize=None)
+def torch_case(name):
+    """init [NT, S] float32, the policy's weights W [A, F] float32 and the oracle's pieces for the loss of test 7"""
+    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
+    rng = np.random.default_rng(37)
+    init = (rng.uniform(-1.0, 1.0, (NT, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32)
+    params = np.tile(ref.nominal_params(1).astype(np.float32).astype(np.float64), (NT, 1))
+    h0 = ref.reset(params, init.astype(np.float64), True)["hidden"]
+    W = make_weights(ref, name, SMALL, None, params, init.astype(np.float64), h0, rng, TT)
+    return dict(ref=ref, init=init, params=params, h0=h0, W=W)
+
+
+def oracle_loss(name, W, s0, length=None):
+    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop, and the lane lengths"""
+    tc = torch_case(name)
+    _, _, _, rew, done, acts = closed_loop(tc["ref"], tc["params"], s0, tc["h0"], SMALL, None, W, np.zeros((NT, TT, tc["ref"].A)))
+    length = lengths_of(done) if length is None else length
+    inside = np.arange(TT)[:, None] < length[None, :]
+    disc = GAMMA ** np.arange(TT)[:, None]
+    return -np.where(inside, disc * rew, 0.0).sum(axis=0) + 1e-3 * np.where(inside[:, :, None], acts ** 2, 0.0).sum(axis=(0, 2)), length
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_loss_gradients(name):
+    """central differences at relative steps 1e-6 and 1e-5 per unit of |W| (the whole weight vector: [1, A F]) and of INIT_SCALE
+    ([NT, S])"""
+    tc = torch_case(name)
+    W0, s0 = tc["W"].astype(np.float64), tc["init"].astype(np.float64)
+    length = oracle_loss(name, W0, s0)[1]
+    gw, gs = [], []
+    for h in (1e-6, 1e-5):
+        g = np.zeros(W0.shape)
+        for idx in np.ndindex(*W0.shape):
+            d = np.zeros_like(W0)
+            d[idx] = h * abs(W0[idx])
+            g[idx] = (oracle_loss(name, W0 + d, s0, length)[0].sum() - oracle_loss(name, W0 - d, s0, length)[0].sum()) / (2.0 * h)
+        gw.append(g.reshape(1, -1))
+        g = np.zeros(s0.shape)
+        for j in range(s0.shape[1]):
+            d = np.zeros_like(s0)
+            d[:, j] = h * INIT_SCALE[name][j]
+            g[:, j] = (oracle_loss(name, W0, s0 + d, length)[0] - oracle_loss(name, W0, s0 - d, length)[0]) / (2.0 * h)
+        gs.append(g)
+    return gw, gs, length
+
+
+@pytest.mark.parametrize("name", ["qq-su", "qcp-su"])
+def test_autograd(vs, name):
+    tc = torch_case(name)
+    gw, gs, length = oracle_loss_gradients(name)
+    for pair in (gw, gs):
+        assert (~smooth_of(*pair)).mean() <= 0.01
+    env = getattr(vs, ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
+    roll = vs.DifferentiablePolicyRollout(env, policy)
+    wscale = np.abs(tc["W"].astype(np.float64))
+
+    def loss_of(init):
+        obs, rew, act, lengths = roll(init, TT)
+        assert tuple(obs.shape) == (NT, TT + 1, tc["ref"].O) and tuple(rew.shape) == (NT, TT) and tuple(act.shape) == (NT, TT, tc["ref"].A)
+        assert not lengths.requires_grad and np.array_equal(lengths.cpu().numpy(), length)
+        return -vs.discounted_return(rew, lengths, GAMMA).sum() + 1e-3 * act.pow(2).sum()
+
+    with torch.no_grad():
+        policy.net.weight.copy_(torch.as_tensor(tc["W"]))
+    init = dev(tc["init"]).requires_grad_(True)
+    loss = loss_of(init)
+    g1 = torch.autograd.grad(loss, (policy.net.weight, init), retain_graph=True)
+    with torch.no_grad():
+        roll(dev(tc["init"]) * 0.5, TT)  # another forward call overwrites the records
+    g2 = torch.autograd.grad(loss, (policy.net.weight, init))  # the re-record path
+    assert all(torch.equal(a, b) for a, b in zip(g1, g2))
+    got_w = (g1[0].detach().cpu().numpy().astype(np.float64) * wscale).reshape(1, -1)
+    got_s = g1[1].cpu().numpy().astype(np.float64) * np.array(INIT_SCALE[name])
+    for what, got, (f1, f2) in (("weights", got_w, gw), ("init_states", got_s, gs)):
+        bad, worst = within(got, f1, smooth_of(f1, f2))
+        print(f"{name} {what}: bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
+        assert bad <= 2e-3, (name, what, bad, worst)
+    # ---- two steps of plain gradient descent on the weights (in units of |W|) lower the oracle's loss
+    s0 = tc["init"].astype(np.float64)
+    eta = 0.02 * np.sqrt(wscale.size) / np.linalg.norm(gw[0])
+    losses = [oracle_loss(name, tc["W"].astype(np.float64), s0, length)[0].sum()]
+    for _ in range(2):
+        policy.net.weight.grad = None
+        loss_of(dev(tc["init"])).backward()
+        with torch.no_grad():
+            policy.net.weight -= eta * policy.net.weight.grad * torch.as_tensor(wscale ** 2, dtype=torch.float32)
+        losses.append(oracle_loss(name, policy.net.weight.detach().numpy().astype(np.float64), s0, length)[0].sum())
+    print(f"{name}: oracle loss {losses[0]:.6f} -> {losses[1]:.6f} -> {losses[2]:.6f}")
+    assert losses[2] < losses[1] < losses[0], losses
+    roll.close()
