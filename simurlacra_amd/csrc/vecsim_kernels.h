@@ -957,10 +957,13 @@ __device__ __forceinline__ float tanh_fast(float x) {
     float r = (1.0f - t) * rcp_fast(1.0f + t);
     return copysignf(r, x);
 }
+// sigmoid through v_exp_f32 and the BARE v_rcp_f32 (1 ulp), as the recurrent gates and the linear policy's feature: below
+// x ~ -88.7 the exponential is +inf, 1 / inf is 0 from the hardware reciprocal, and rcp_fast's Newton step would make NaN of
+// it (fmaf(-inf, 0, 1)); finite for every finite x, NaN stays NaN
 __device__ __forceinline__ float fnn_nonlin(int kind, float x) {  // kind is wave-uniform
     if (kind == FNN_TANH) return tanh_fast(x);
     if (kind == FNN_RELU) return fmaxf(x, 0.f);
-    if (kind == FNN_SIGMOID) return rcp_fast(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+    if (kind == FNN_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
     return x;
 }
 

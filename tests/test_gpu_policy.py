@@ -7,6 +7,8 @@ What is checked, through the C-ABI:
     different summation order than torch's GEMM and a v_exp-based tanh: |act - torch| <= 1e-5 (1 + |torch|) asserted (measured 3.4e-6), printed with -s;
   * everything else is the step kernel's: vs_step fed with the recorded actions from the same initial state reproduces the
     recorded observations, states, rewards and done flags BIT FOR BIT (with and without auto-reset, launches split unevenly);
+  * a sigmoid layer with pre-activations of -100 and +100 gives finite actions (1 / (1 + inf) is 0, not NaN), on the vector ALU
+    and on the matrix cores, within the same 1e-5 of the network in double precision;
   * exploration noise: (act - network(obs)) / std is N(0, 1) by its moments and does not depend on how the steps are cut
     into launches;
   * the sampler: ParallelRolloutSampler with an FNNPolicy takes the fused path and returns rollouts whose every step is
@@ -129,6 +131,42 @@ def test_policy_kernel_against_torch_and_the_step_kernel(vs, case, auto_reset, s
             assert np.array_equal(x, y)
     for e in envs:
         e.close()
+
+
+@pytest.mark.parametrize("hidden,nonlin,shape", [([16], "sigmoid", "64"), ([64, 64], ["tanh", "sigmoid"], "mfma")],
+                         ids=["16-vector-alu", "64x64-matrix-cores"])
+def test_sigmoid_layer_far_in_both_tails(vs, hidden, nonlin, shape):
+    """half the units of the sigmoid layer with a bias of -100, a quarter with +100: below -88.7 the kernel's exponential is +inf
+    and its reciprocal has to be 0, not NaN -- on the vector ALU (one layer of 16) and in the matrix-core shape's in-register
+    nonlinearity (second layer of [64, 64]).  Reference: the network in double precision on the recorded observations."""
+    import copy
+
+    name, n, T = "qq-su", 300, 6
+    O, A = vs.env_dims(name)["O"], vs.env_dims(name)["A"]
+    net = make_net(vs, O, A, hidden, nonlin, None, 1.0, seed=21)
+    w = hidden[-1]
+    with torch.no_grad():
+        net.hidden_layers[-1].bias[: w // 2] = -100.0
+        net.hidden_layers[-1].bias[w // 2: w // 2 + w // 4] = 100.0
+    e = vs.VecSimEnv(name, n, **KW[name])
+    e.reset(seed=9)
+    e.set_policy_fnn(torch.nn.utils.parameters_to_vector(net.parameters()), hidden, nonlin, None)
+    e.set_policy_shape(shape)
+    e.set_record_mode(2)
+    e.set_traj_capacity(T)
+    e.step_policy(T, record=True)
+    tr = e.traj(T)
+    with torch.no_grad():
+        want = copy.deepcopy(net).double()(torch.from_numpy(tr["obs"].astype(np.float64))).numpy()
+    assert want.dtype == np.float64
+    print(f"{name} {hidden} {nonlin} shape {shape}: {int(np.isnan(tr['act']).sum())} NaN of {tr['act'].size} recorded actions, "
+          f"error_count {e.error_count()}")
+    assert np.isfinite(tr["act"]).all()
+    assert e.error_count() == 0
+    err = np.abs(tr["act"] - want) / (1.0 + np.abs(want))
+    print(f"    max |act - fp64| / (1 + |fp64|) = {err.max():.2e}")
+    assert err.max() < 1e-5
+    e.close()
 
 
 def test_policy_kernel_exploration_noise(vs):
