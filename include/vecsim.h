@@ -591,8 +591,16 @@ int vs_clear_episodes(vs_handle h);
 /* ---- mixed batches (BASELINE config 5): several env families stepped by ONE launch ----
  * A mixed handle groups up to 5 ordinary handles on one device (lanes sorted by type: each handle is one contiguous
  * segment).  A workgroup belongs to one segment, so the env-type dispatch is uniform per workgroup / wavefront.
- * Parameters, resets and data access go through the member handles; the mixed handle only fuses the launches.  All
- * members share the stream of the first one and must agree on auto-reset. */
+ * Parameters, resets and data access go through the member handles; the mixed handle only fuses the launches.
+ * vs_mixed_create (VS_ERR_ARG otherwise): 1..5 handles, each once, on one device, agreeing on auto-reset; it moves every
+ * member onto the stream of the first.
+ * A launch takes the auto-reset setting, the stream and -- vs_mixed_step_random -- the record mode from the first member, so it
+ * refuses (VS_ERR_STATE) members that no longer agree on them: after vs_set_auto_reset or vs_set_record_mode on some members
+ * only, or after vs_set_stream gave a member another stream than the first member's (its own resets and copies would no longer
+ * be ordered with the launch; give every member the same stream again).  It also refuses a member that carries a wrapper
+ * pipeline (vs_set_act_pipeline / vs_set_obs_pipeline) and a recording rollout whose traj offset + k_steps exceeds a member's
+ * vs_set_traj_capacity; k_steps < 1 and action pointers that are not device memory are VS_ERR_ARG.  Every check comes before
+ * any member changes: a refused launch moves no random stream and writes no buffer; vs_mixed_last_error names the cause. */
 typedef struct vs_mixed* vs_mixed_handle;
 int vs_mixed_create(const vs_handle* handles, int n, vs_mixed_handle* out);
 int vs_mixed_destroy(vs_mixed_handle m);

@@ -479,16 +479,35 @@ static bool mixed_redraws(const vs_mixed* m) {
     return false;
 }
 
+// What every mixed launch checks before it touches a member: the members still agree on what the ONE launch takes from the
+// first of them (auto-reset, the stream; for a rollout the record mode), none carries a wrapper pipeline, and a recording
+// rollout fits every member's record buffers.  A refusal names the entry point (`who`) and leaves every handle as it was.
+static int mixed_check(vs_mixed* m, const char* who, bool rollout, int k_steps, int record) {
+    auto refuse = [&](const char* what) {
+        m->err = std::string(who) + ": " + what;
+        return VS_ERR_STATE;
+    };
+    vs_handle h0 = m->sub[0];
+    for (int q = 0; q < m->n; ++q) {
+        vs_handle h = m->sub[q];
+        if (rollout && record && h->d.traj_t0 + k_steps > h->traj_cap) return refuse("k_steps exceeds a segment's vs_set_traj_capacity");
+        if (h->auto_reset != h0->auto_reset) return refuse("segments differ in auto-reset");
+        if (rollout && h->record_mode != h0->record_mode) return refuse("segments differ in record mode");
+        if (h->d.pipe.act_on || h->d.pipe.obs_on)
+            return refuse("a segment carries an action/observation pipeline (single-family handles only)");
+        // one launch, one stream: a member moved to another one would no longer order its own resets and copies with the launch
+        if (h->stream != h0->stream) return refuse("a segment's stream differs from the first segment's (vs_set_stream after vs_mixed_create)");
+    }
+    return VS_OK;
+}
+
+// the segment table of one launch (after mixed_check); the members' action streams advance once it is on the device
 static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* env_strides, const int64_t* dim_strides,
                         int k_steps) {
     int blocks = 0;
     vs_handle h0 = m->sub[0];
     for (int q = 0; q < m->n; ++q) {
         vs_handle h = m->sub[q];
-        if (h->d.pipe.act_on || h->d.pipe.obs_on) {
-            m->err = "mixed batch: a segment carries an action/observation pipeline (single-family handles only)";
-            return VS_ERR_STATE;
-        }
         Seg& sg = m->host.s[q];
         blocks += (h->d.ld + BLOCK - 1) / BLOCK;
         sg.type = h->type;
@@ -500,7 +519,6 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
         sg.dim_stride = dim_strides ? (long)dim_strides[q] : 0;
         sg.reset_seed = h->ar_seed;
         sg.epoch0 = h->epoch;
-        h->epoch += (uint64_t)k_steps;
     }
     m->host.n = m->n;
     m->total_blocks = blocks;
@@ -509,6 +527,7 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
     hipError_t e = hipMemcpyAsync(m->dev, &m->host, sizeof(Segs), hipMemcpyHostToDevice, h0->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h0->stream);  // host.s is rewritten by the next call
     if (e != hipSuccess) { m->err = std::string("mixed_upload: ") + hipGetErrorString(e); return VS_ERR_HIP; }
+    for (int q = 0; q < m->n; ++q) m->sub[q]->epoch += (uint64_t)k_steps;
     return VS_OK;
 }
 
@@ -613,7 +632,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 311; }
+int vs_version(void) { return 312; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1765,6 +1784,8 @@ int vs_mixed_create(const vs_handle* handles, int n, vs_mixed_handle* out) {
         if (!handles[q]) return fail(nullptr, VS_ERR_ARG, "vs_mixed_create: NULL handle");
         if (handles[q]->device != handles[0]->device) return fail(nullptr, VS_ERR_ARG, "vs_mixed_create: handles on different devices");
         if (handles[q]->auto_reset != handles[0]->auto_reset) return fail(nullptr, VS_ERR_ARG, "vs_mixed_create: handles differ in auto-reset");
+        for (int p = 0; p < q; ++p)  // a segment is a handle's own buffers: two segments on one handle would race on them
+            if (handles[p] == handles[q]) return fail(nullptr, VS_ERR_ARG, "vs_mixed_create: the same handle twice");
     }
     vs_mixed* m = new (std::nothrow) vs_mixed();
     if (!m) return fail(nullptr, VS_ERR_HIP, "vs_mixed_create: out of host memory");
@@ -1791,14 +1812,12 @@ int vs_mixed_destroy(vs_mixed_handle m) {
 const char* vs_mixed_last_error(vs_mixed_handle m) { return m ? m->err.c_str() : ""; }
 
 int vs_mixed_step_random(vs_mixed_handle m, uint64_t seed, int k_steps, int record) {
-    if (!m || k_steps < 1) return VS_ERR_ARG;
-    for (int q = 0; q < m->n; ++q) {
-        if (record && m->sub[q]->d.traj_t0 + k_steps > m->sub[q]->traj_cap) { m->err = "vs_mixed_step_random: k_steps exceeds a segment's vs_set_traj_capacity"; return VS_ERR_STATE; }
-        if (m->sub[q]->auto_reset != m->sub[0]->auto_reset) { m->err = "vs_mixed_step_random: segments differ in auto-reset"; return VS_ERR_STATE; }
-        if (m->sub[q]->record_mode != m->sub[0]->record_mode) { m->err = "vs_mixed_step_random: segments differ in record mode"; return VS_ERR_STATE; }
-    }
+    if (!m) return VS_ERR_ARG;
+    if (k_steps < 1) { m->err = "vs_mixed_step_random: k_steps must be >= 1"; return VS_ERR_ARG; }
+    int rc = mixed_check(m, "vs_mixed_step_random", true, k_steps, record);
+    if (rc) return rc;
     if (hipSetDevice(m->sub[0]->device) != hipSuccess) return VS_ERR_HIP;
-    int rc = mixed_upload(m, nullptr, nullptr, nullptr, k_steps);
+    rc = mixed_upload(m, nullptr, nullptr, nullptr, k_steps);
     if (rc) return rc;
     launch_rollout_mixed((const Segs*)m->dev, m->total_blocks, m->sub[0]->stream, m->sub[0]->auto_reset,
                          record ? m->sub[0]->record_mode : 0, k_steps, seed, mixed_redraws(m));
@@ -1808,11 +1827,14 @@ int vs_mixed_step_random(vs_mixed_handle m, uint64_t seed, int k_steps, int reco
 }
 
 int vs_mixed_step(vs_mixed_handle m, const float* const* actions, const int64_t* env_strides, const int64_t* dim_strides) {
-    if (!m || !actions || !env_strides || !dim_strides) return VS_ERR_ARG;
+    if (!m) return VS_ERR_ARG;
+    if (!actions || !env_strides || !dim_strides) { m->err = "vs_mixed_step: NULL argument"; return VS_ERR_ARG; }
     for (int q = 0; q < m->n; ++q)
         if (!actions[q] || !is_device_ptr(actions[q])) { m->err = "vs_mixed_step: actions must be device memory"; return VS_ERR_ARG; }
+    int rc = mixed_check(m, "vs_mixed_step", false, 0, 0);
+    if (rc) return rc;
     if (hipSetDevice(m->sub[0]->device) != hipSuccess) return VS_ERR_HIP;
-    int rc = mixed_upload(m, actions, env_strides, dim_strides, 0);
+    rc = mixed_upload(m, actions, env_strides, dim_strides, 0);
     if (rc) return rc;
     launch_step_mixed((const Segs*)m->dev, m->total_blocks, m->sub[0]->stream, m->sub[0]->auto_reset, mixed_redraws(m));
     hipError_t e = hipGetLastError();
