@@ -480,9 +480,26 @@ int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_
  * rule per position; ATan2Feat(y, x): (x, -y) / (x^2 + y^2)).  After t = 0 the initial observation takes g_obs[0] + gpol.
  * With a stack of constant features the result equals vs_rollout_vjp's bit for bit.
  * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no linear policy on the handle (an FNN, RNN
- * or playback policy, or none) and a policy population on the handle (VS_ERR_STATE).  FNN / RNN policies have no closed-loop sweep. */
+ * or playback policy, or none) and a policy population on the handle (VS_ERR_STATE).  Feed-forward networks have vs_rollout_vjp_fnn; RNN policies have no closed-loop sweep. */
 int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                           const float* g_state_last, float* d_act, float* d_init);
+/* ... and for rollouts recorded with the handle's current FEED-FORWARD NETWORK (vs_set_policy_fnn) of one or two hidden layers in the
+ * loop: a_t = g(W_out f(.. f(W_1 x_t + b_1) ..) + b_out) + n_t, x_t = the observation rows the policy sees (obs_idx), optionally in the
+ * featurisation [o_0, sin o_1, cos o_1, o_2 ..], n_t constant.  Phi, arguments, layout (ld = vs_ld(h)), stream, L, every convention and
+ * the rule "refused before the first device call, outputs untouched" are vs_rollout_vjp_policy's; d_act is again the TOTAL adjoint
+ * abar_t of the raw action a_t (the output nonlinearity's own derivative is applied only on the way to gpol), so that
+ * d Phi / d theta = sum_t (d pi / d theta)(obs_t)^T abar_t is one batched backward pass of the network over the recorded observations,
+ * left to the caller.  Per step the activations of obs_t = observe(s_t) are recomputed with the rollout kernel's expressions (the
+ * summation order differs, as it does between the rollout kernel's own shapes) and pulled back:
+ *     delta_out = abar_t (.) g'(y_out);  delta_l = (W_{l+1}^T delta_{l+1}) (.) f'(y_l);  gx = W_1^T delta_1
+ * with tanh' = 1 - y^2, sigmoid' = y (1 - y), relu' = [y > 0] (0 at 0), none: 1;  under the featurisation o_1 takes
+ * gx_1 cos o_1 - gx_2 sin o_1;  gpol is gx on the observation rows obs_idx names.  Rows t >= L and lanes >= n_envs contribute nothing
+ * and get zeros, whatever the records hold there.
+ * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no feed-forward network on the handle (a
+ * linear, RNN or playback policy, or none), a policy population on the handle, a network of more than two hidden layers (its weights
+ * and their transposes do not fit the register file) (VS_ERR_STATE). */
+int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, float* d_act, float* d_init);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

@@ -46,7 +46,7 @@ def __getattr__(name):
         from . import sysid
 
         return getattr(sysid, name)
-    if name in ("DifferentiableRollout", "DifferentiablePolicyRollout", "discounted_return"):
+    if name in ("DifferentiableRollout", "DifferentiablePolicyRollout", "DifferentiableNetRollout", "discounted_return"):
         from . import diffsim
 
         return getattr(diffsim, name)

@@ -632,7 +632,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 312; }
+int vs_version(void) { return 313; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1703,18 +1703,26 @@ int vs_pack_traj(vs_handle h, int n_lanes, int t_steps, const int64_t* lengths, 
     return VS_OK;
 }
 
+// What the three reverse-mode sweeps refuse alike, in one order and with the entry point's name in front; `policy` (may be NULL) names
+// what the entry point needs of the handle's policy slot, or returns NULL.  Every refusal comes before the first device call and
+// leaves the outputs untouched.
+static int vjp_checks(vs_handle h, const char* who, int t_steps, const float* d_act, const float* d_init,
+                      const char* (*policy)(vs_handle)) {
+    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, who, "NULL handle or output");
+    if (t_steps < 1) return fail(h, VS_ERR_ARG, who, "t_steps < 1");
+    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, who, "the discrete-action family has no action gradient");
+    if (const char* why = policy ? policy(h) : nullptr) return fail(h, VS_ERR_STATE, who, why);
+    if (h->record_mode != 2) return fail(h, VS_ERR_STATE, who, "needs the records of record mode 2 (vs_set_record_mode)");
+    if (h->auto_reset) return fail(h, VS_ERR_STATE, who, "switch auto-reset off (one rollout per lane, started at a reset)");
+    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, who, "not available with a wrapper pipeline on the handle");
+    if (h->d.traj_t0 != 0) return fail(h, VS_ERR_STATE, who, "set the trajectory offset back to 0 (the sweep reads rows 0 .. t_steps - 1)");
+    if (t_steps > h->traj_cap || !h->d.traj_rec || !h->d.traj_done) return fail(h, VS_ERR_ARG, who, "t_steps exceeds vs_set_traj_capacity");
+    return VS_OK;
+}
+
 int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
                    float* d_init) {
-    // every refusal comes before the first device call and leaves the outputs untouched
-    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, "vs_rollout_vjp: NULL handle or output");
-    if (t_steps < 1) return fail(h, VS_ERR_ARG, "vs_rollout_vjp: t_steps < 1");
-    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: the discrete-action family has no action gradient");
-    if (h->record_mode != 2) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: needs the records of record mode 2 (vs_set_record_mode)");
-    if (h->auto_reset) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: switch auto-reset off (one rollout per lane, started at a reset)");
-    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: not available with a wrapper pipeline on the handle");
-    if (h->d.traj_t0 != 0) return fail(h, VS_ERR_STATE, "vs_rollout_vjp: set the trajectory offset back to 0 (the sweep reads rows 0 .. t_steps - 1)");
-    if (t_steps > h->traj_cap || !h->d.traj_rec || !h->d.traj_done)
-        return fail(h, VS_ERR_ARG, "vs_rollout_vjp: t_steps exceeds vs_set_traj_capacity");
+    if (int rc = vjp_checks(h, "vs_rollout_vjp", t_steps, d_act, d_init, nullptr)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp(h, v, t_steps));
@@ -1724,21 +1732,31 @@ int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_
 
 int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                           const float* g_state_last, float* d_act, float* d_init) {
-    // every refusal comes before the first device call and leaves the outputs untouched
-    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: NULL handle or output");
-    if (t_steps < 1) return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: t_steps < 1");
-    if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: the discrete-action family has no action gradient");
-    if (!h->lin.w) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: no linear policy on the handle (vs_set_policy_linear)");
-    if (h->pop.w) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: not available with a policy population on the handle");
-    if (h->record_mode != 2) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: needs the records of record mode 2 (vs_set_record_mode)");
-    if (h->auto_reset) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: switch auto-reset off (one rollout per lane, started at a reset)");
-    if (h->d.pipe.act_on || h->d.pipe.obs_on) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: not available with a wrapper pipeline on the handle");
-    if (h->d.traj_t0 != 0) return fail(h, VS_ERR_STATE, "vs_rollout_vjp_policy: set the trajectory offset back to 0 (the sweep reads rows 0 .. t_steps - 1)");
-    if (t_steps > h->traj_cap || !h->d.traj_rec || !h->d.traj_done)
-        return fail(h, VS_ERR_ARG, "vs_rollout_vjp_policy: t_steps exceeds vs_set_traj_capacity");
+    const auto policy = [](vs_handle h) -> const char* {
+        if (!h->lin.w) return "no linear policy on the handle (vs_set_policy_linear)";
+        if (h->pop.w) return "not available with a policy population on the handle";
+        return nullptr;
+    };
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_policy", t_steps, d_act, d_init, policy)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_lin(h, v, g_act, t_steps));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, float* d_act, float* d_init) {
+    const auto policy = [](vs_handle h) -> const char* {
+        if (!h->fnn.w) return "no feed-forward network policy on the handle (vs_set_policy_fnn)";
+        if (h->pop.w) return "not available with a policy population on the handle";
+        if (h->fnn.n_hidden > 2) return "the sweep takes networks of one or two hidden layers";
+        return nullptr;
+    };
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_fnn", t_steps, d_act, d_init, policy)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
+    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_fnn(h, v, g_act, t_steps));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -15,6 +15,7 @@
 //   k_rollout_play_sens  vs_step_policy   playback rollout + discrepancy with its gradient and Gauss-Newton matrix w.r.t. domain parameters
 //   k_rollout_vjp   vs_rollout_vjp    reverse-mode sweep over a recorded rollout: gradients w.r.t. its actions and initial state
 //   k_rollout_vjp_lin  vs_rollout_vjp_policy  the same sweep with the handle's linear policy in the loop (closed-loop adjoints)
+//   k_rollout_vjp_fnn  vs_rollout_vjp_fnn     ... with the handle's feed-forward network of one or two hidden layers in the loop
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2601,6 +2602,247 @@ __global__ __launch_bounds__(64) void k_rollout_vjp_lin(Task T, Dev d, Vjp V, co
     for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
 }
 
+// ------------------------------------------------------------- reverse-mode sweep with a feed-forward network in the loop
+// vs_rollout_vjp_fnn: k_rollout_vjp for rollouts that k_rollout_fnn recorded -- a_t = g(W_out f(.. f(W_1 x_t + b_1) ..) + b_out) + n_t
+// with the handle's network of one or two hidden layers (Fnn: the same packed weights, observation view and featurisation) and n_t
+// constant.  The contract of the adjoints is k_rollout_vjp_lin's: d_act[t] = abar_t, the total adjoint of the raw action; gpol [O],
+// the network's pull-back onto the observation it saw, rides on g_obs[t + 1] into vjp_step; nothing of the handle is written.
+// A network's Jacobian is matrix-shaped, so the workgroup of 64 envs has k_rollout_fnn's TWO lane mappings:
+//   * wave 0, "lane = env": load_record_inputs, vjp_step, vjp_observe and the lane-length logic of k_rollout_vjp_lin, unchanged.  Per
+//     step t it leaves abar_t [A] and the policy's input row of obs_t = E::observe(s_t) -- built as k_rollout_fnn builds it: obs_idx /
+//     n_vis / ident, the feat row [o_0, sin o_1, cos o_1, o_2 ..] through sincos_fast -- in LDS, and takes gx [in_dim] back: under feat
+//     o_1 gets gx_1 cos o_1 - gx_2 sin o_1, then obs_idx by wave-uniform selects gives the next gpol.  A lane with t >= L (lanes >= n
+//     and the lanes of a partial last workgroup have L = 0) leaves a zero row and a zero adjoint by select, reads no cotangent and no
+//     record, writes d_act[t] = 0 and keeps gpol = 0.
+//   * waves 1 .. 4, "lane = hidden unit", 16 envs each, one after the other: the weights stay in VGPRs for the whole launch -- unit
+//     j's rows of W_1 and W_2 for the forward pass and, for W_2^T delta, ROW j of the packed Wt_2 [in][64], which is the contiguous
+//     column of W_2 that lane j needs (64 + 64 + 12 + A + 2 registers with two hidden layers).  Per env the activations of obs_t are
+//     recomputed with the forward kernel's expressions (tanh_fast, the bare v_rcp_f32 sigmoid, fmaxf; the sums run in four partial
+//     accumulators, so the bits may differ from the recording launch as its two shapes differ from each other), then
+//         delta_out = abar (.) g'(y_out)      delta_l = (W_{l+1}^T delta_{l+1}) (.) f'(y_l)      gx = W_1^T delta_1
+//     with the derivatives of the functions that ran, taken from their values: tanh 1 - y^2, sigmoid y (1 - y), relu y > 0 (0 at 0,
+//     as torch has it), none 1.  An activation vector or delta_2 is uniform over the lanes where it is consumed: it goes through the
+//     env's LDS row and comes back as broadcast ds_read_b128; W_out^T delta_out is A FMAs per lane (lane j holds W_out[.][j]); the
+//     narrow products W_out y and W_1^T delta_1 are a product per lane and a DPP wave reduction each.  Padding units carry zero
+//     weights in every matrix they touch, so their deltas are 0.
+// Two LDS-only barriers per step (rows and adjoints in, gx out).  The two roles have a loop each, so that the weight registers are
+// not live in the env wave: five waves are two per SIMD at most, 256 VGPRs each, and neither role spills.
+constexpr int FNNB_WAVES = 5;                     // the env wave + the network waves
+constexpr int FNNB_EPW = 64 / (FNNB_WAVES - 1);   // envs per network wave
+__device__ __forceinline__ float fnn_nonlin_grad(int kind, float y) {  // kind is wave-uniform; y = fnn_nonlin(kind, z)
+    if (kind == FNN_TANH) return fmaf(-y, y, 1.0f);
+    if (kind == FNN_RELU) return y > 0.f ? 1.0f : 0.f;
+    if (kind == FNN_SIGMOID) return y * (1.0f - y);
+    return 1.0f;
+}
+// sum_k w[k] row[k] over a 64-wide LDS row that is uniform over the wave (broadcast 16-B reads), four partial sums
+__device__ __forceinline__ float fnn_row_dot(const float* w, const float* row) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < FNN_W / 4; ++kk) {
+        const float4 v = reinterpret_cast<const float4*>(row)[kk];
+        acc[kk & 3] = fmaf(w[4 * kk], v.x, acc[kk & 3]);
+        acc[kk & 3] = fmaf(w[4 * kk + 1], v.y, acc[kk & 3]);
+        acc[kk & 3] = fmaf(w[4 * kk + 2], v.z, acc[kk & 3]);
+        acc[kk & 3] = fmaf(w[4 * kk + 3], v.w, acc[kk & 3]);
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+template <class E, int NHID>
+__global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev d, Vjp V, const float* g_act, Fnn P, int t_steps) {
+    static_assert(NHID == 1 || NHID == 2, "hidden layers: deeper networks' weights and transposes do not fit the registers");
+    static_assert(E::O <= MAXO && MAXO + 1 <= FNN_XS, "input row");
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    __shared__ __attribute__((aligned(16))) float l_x[64 * FNN_XS];  // what the policy saw of obs_t: [env][input]
+    __shared__ __attribute__((aligned(16))) float l_g[64 * FNN_XS];  // the network's pull-back onto that row: [env][input]
+    __shared__ float l_ab[64 * MAXA];                                // abar_t: [env][A]
+    __shared__ __attribute__((aligned(16))) float l_h[NHID > 1 ? 64 * FNN_W : 4];  // y_1, then delta_2: [env][unit]
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+
+    if (wave > 0) {
+        // ================================================================================ network waves: lane = hidden unit
+        float w1[FNN_XS], wh[NHID > 1 ? FNN_W : 1], wt[NHID > 1 ? FNN_W : 1], bh[NHID], wo[E::A], bo[E::A];
+#pragma unroll
+        for (int k = 0; k < FNN_XS; ++k) w1[k] = k < P.in_dim ? P.w[P.off_w[0] + k * FNN_W + lane] : 0.f;
+        if constexpr (NHID > 1) {
+#pragma unroll
+            for (int k = 0; k < FNN_W; ++k) wh[k] = P.w[P.off_w[1] + k * FNN_W + lane];  // W_2[lane][k]
+#pragma unroll
+            for (int m = 0; m < FNN_W; ++m) wt[m] = P.w[P.off_w[1] + lane * FNN_W + m];  // W_2[m][lane]: row `lane` of Wt_2
+        }
+#pragma unroll
+        for (int l = 0; l < NHID; ++l) bh[l] = P.w[P.off_b[l] + lane];
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) wo[j] = P.w[P.off_w[NHID] + j * FNN_W + lane], bo[j] = P.w[P.off_b[NHID] + j];
+        const int kind0 = P.hid_nonlin[0], kind1 = P.hid_nonlin[NHID > 1 ? 1 : 0], kindo = P.out_nonlin, in_dim = P.in_dim;
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // (nothing pending at the loop header)
+
+        for (int t = t_steps - 1; t >= 0; --t) {
+            ws_barrier();  // the input rows and adjoints of step t are in LDS
+#pragma unroll 1
+            for (int q = 0; q < FNNB_EPW; ++q) {
+                const int e = (wave - 1) * FNNB_EPW + q;  // wave-uniform: every LDS read below is one address for the wave
+                float x[FNN_XS];
+                Planes<FNN_XS>::load(l_x, 1, e * (FNN_XS / 4), x);
+                // ---- forward, as k_rollout_fnn
+                float z = bh[0];
+#pragma unroll
+                for (int k = 0; k < FNN_XS; ++k) z = fmaf(w1[k], x[k], z);
+                const float y1 = fnn_nonlin(kind0, z);
+                float yl = y1;
+                if constexpr (NHID > 1) {
+                    l_h[e * FNN_W + lane] = y1;
+                    wave_lds_fence();
+                    yl = fnn_nonlin(kind1, bh[1] + fnn_row_dot(wh, l_h + e * FNN_W));
+                }
+                // ---- delta_out = abar (.) g'(y_out), uniform over the wave;  dl = W_out^T delta_out
+                float dl = 0.f;
+#pragma unroll
+                for (int j = 0; j < E::A; ++j) {
+                    const float sum = wave_sum_to_lane63(wo[j] * yl);
+                    const float zo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sum), 63)) + bo[j];
+                    const float dout = l_ab[e * MAXA + j] * fnn_nonlin_grad(kindo, fnn_nonlin(kindo, zo));
+                    dl = fmaf(wo[j], dout, dl);
+                }
+                dl *= fnn_nonlin_grad(NHID > 1 ? kind1 : kind0, yl);
+                float d1 = dl;
+                if constexpr (NHID > 1) {
+                    wave_lds_fence();  // every lane has read the row of y_1
+                    l_h[e * FNN_W + lane] = dl;
+                    wave_lds_fence();
+                    d1 = fnn_row_dot(wt, l_h + e * FNN_W) * fnn_nonlin_grad(kind0, y1);
+                }
+                // ---- gx = W_1^T delta_1: a wave reduction per input
+#pragma unroll
+                for (int k = 0; k < FNN_XS; ++k) {
+                    if (k >= in_dim) continue;  // (wave-uniform; l_g stays 0 there)
+                    const float sum = wave_sum_to_lane63(w1[k] * d1);
+                    if (lane == 63) l_g[e * FNN_XS + k] = sum;
+                }
+            }
+            ws_barrier();  // the pull-backs of step t are in LDS
+        }
+        return;
+    }
+
+    // ==================================================================================== the env wave: lane = env
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    float c[E::K];
+    load_consts<E, false>(d, i, c, 0, E::KS);
+    // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (bits behind t_steps may be stale)
+    int L = 0;
+    if (valid) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = d.traj_done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    float lam[NS], x[NI], out[NI], gob[E::O], gpol[E::O];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = (valid && V.g_last) ? V.g_last[(size_t)k * ld + i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = 0.f;
+#pragma unroll
+    for (int q = 0; q < E::O; ++q) gpol[q] = 0.f;
+    {
+        float zero[FNN_XS];
+#pragma unroll
+        for (int k = 0; k < FNN_XS; ++k) zero[k] = 0.f;
+        Planes<FNN_XS>::store(l_g, 1, lane * (FNN_XS / 4), zero);  // (entries >= in_dim are never written again)
+    }
+
+    for (int t = t_steps - 1; t >= 0; --t) {
+        const bool live = t < L;
+        float xr[FNN_XS], ab[E::A], sn = 0.f, cs = 0.f;
+#pragma unroll
+        for (int k = 0; k < NI; ++k) out[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < FNN_XS; ++k) xr[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) ab[j] = 0.f;
+        if (live) {
+            load_record_inputs<E>(d.traj_rec + (size_t)t * Rec<E, 2>::F * ld, ld, i, x);
+            const float grew = V.g_rew ? V.g_rew[(size_t)t * ld + i] : 0.f;
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[((size_t)(t + 1) * E::O + q) * ld + i] : 0.f) + gpol[q];
+            vjp_step<E>(T, c, x, t, lam, grew, gob, out);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) lam[k] = out[k];
+            // ---- the total adjoint of a_t
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) {
+                ab[j] = g_act ? out[NS + j] + g_act[((size_t)t * E::A + j) * ld + i] : out[NS + j];
+                out[NS + j] = ab[j];
+            }
+            // ---- what the policy saw of obs_t, as in k_rollout_fnn
+            float ob[E::O];
+            E::observe(x, ob);
+            if (P.ident) {
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k) xr[k] = k < E::O ? ob[k] : 0.f;
+            } else {
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k) {
+                    float v = 0.f;
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                    xr[k] = v;
+                }
+            }
+            if (P.feat) {  // [o_0, sin o_1, cos o_1, o_2 ..]
+                sincos_fast(xr[1], &sn, &cs);
+#pragma unroll
+                for (int k = MAXO; k >= 3; --k) xr[k] = xr[k - 1];
+                xr[1] = sn, xr[2] = cs;
+            }
+        }
+        Planes<FNN_XS>::store(l_x, 1, lane * (FNN_XS / 4), xr);
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) l_ab[lane * MAXA + j] = ab[j];
+        ws_barrier();  // the network waves take over
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = out[NS + j];
+        ws_barrier();  // ... and have left gx
+        if (live) {
+            float gx[FNN_XS];
+            Planes<FNN_XS>::load(l_g, 1, lane * (FNN_XS / 4), gx);
+            if (P.feat) {  // back through the featurisation: o_1 takes the sine's and the cosine's share
+                gx[1] = gx[1] * cs - gx[2] * sn;
+#pragma unroll
+                for (int k = 2; k < MAXO; ++k) gx[k] = gx[k + 1];
+            }
+            // ---- gx back to observation rows: the next gpol
+            if (P.ident) {
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) gpol[j] = gx[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) gpol[j] = 0.f;
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k)
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) gpol[j] += (k < P.n_vis && P.obs_idx[k] == j) ? gx[k] : 0.f;  // wave-uniform selects
+            }
+        }
+    }
+    if (L > 0) {  // x is row 0 here: every lane with a rollout ran t = 0 last
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[(size_t)q * ld + i] : 0.f) + gpol[q];
+        vjp_observe<E>(x, gob, lam);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -3632,6 +3874,7 @@ struct Launch {
     static void rollout_play_sens(vs_env* h, int k);                          // ... and its parameter sensitivities (vs_set_rollout_sens)
     static void rollout_vjp(vs_env* h, const Vjp& v, int t_steps);            // vs_rollout_vjp
     static void rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_policy
+    static void rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_fnn
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -3914,6 +4157,17 @@ void Launch<E>::rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int
         hipLaunchKernelGGL((k_rollout_vjp_lin<E>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, g_act, h->lin,
                            t_steps);
     else no_kernel("rollout_vjp_lin");
+}
+
+template <class E>
+void Launch<E>::rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int t_steps) {
+    // 64 envs per workgroup: the env wave and four network waves; one or two hidden layers (the C-ABI admits nothing else)
+    with_int<1, 2>(h->fnn.n_hidden, [&](auto NH) __attribute__((always_inline)) {
+        if constexpr (!std::is_same<E, BobD>::value)
+            hipLaunchKernelGGL((k_rollout_vjp_fnn<E, NH>), dim3((unsigned)(h->d.ld / 64)), dim3(64 * FNNB_WAVES), 0, h->stream, h->task,
+                               h->d, v, g_act, h->fnn, t_steps);
+        else no_kernel("rollout_vjp_fnn");
+    });
 }
 
 template <class E>

@@ -13,7 +13,8 @@ the step, kinks follow the branch taken), domain parameters and the initial hidd
 DifferentiablePolicyRollout is the closed-loop form: a LinearPolicy on a feature stack runs inside the recording launch
 (vs_set_policy_linear), and the backward pass is one closed-loop sweep (vs_rollout_vjp_policy, k_rollout_vjp_lin) -- the action's
 dependence on the observation is part of the adjoint -- followed by one batched torch pass over the recorded observations for the
-gradient of the policy's parameters.
+gradient of the policy's parameters.  DifferentiableNetRollout is the same for a feed-forward network of one or two hidden layers
+(vs_set_policy_fnn, vs_rollout_vjp_fnn, k_rollout_vjp_fnn): backpropagation through time with the network inside the sweep.
 """
 from typing import Optional, Sequence
 
@@ -196,7 +197,111 @@ class _RolloutFn(torch.autograd.Function):
         return None, None, None, d_act, d_init
 
 
-class DifferentiablePolicyRollout(_RecordedBatches):
+class _ClosedLoopRollout(_RecordedBatches):
+    """What the two closed-loop classes share: the call, the recording launch, the outputs and the backward pass.  A subclass sets
+    self.policy (what the caller gave), self._mean (the module whose parameters get gradients: the policy without its exploration
+    noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now."""
+
+    def _check_dims(self, obs_dim, act_dim):
+        A, _, O = self._dims()
+        if obs_dim != O or act_dim != A:
+            raise ShapeErr(msg=f"the policy maps {obs_dim} observation rows to {act_dim} actions, the env has {O} and {A}")
+
+    def _noise_std(self):
+        raise NotImplementedError
+
+    def _set_policy(self, v, params, noise_std):
+        raise NotImplementedError
+
+    def _sweep(self, v, T, g_rew, g_obs, g_act):
+        raise NotImplementedError
+
+    def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0):
+        _, S, _ = self._dims()
+        if not hasattr(init_states, "dim"):
+            raise TypeErr(msg="init_states must be a torch tensor")
+        if init_states.dim() != 2 or init_states.shape[1] != S or init_states.shape[0] < 1:
+            raise ShapeErr(msg=f"init_states must be [N, {S}], got shape {tuple(init_states.shape)}")
+        if int(T) < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        N = init_states.shape[0]
+        params = domain_param_matrix(self._base, [dict()] * N if domain_params is None else domain_params, names)
+        if params.shape[0] != N:
+            raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
+        if not init_states.is_cuda or init_states.dtype != torch.float32:
+            raise TypeErr(msg="init_states must be a float32 tensor on the GPU")
+        noise_std = self._noise_std()                                # (the std may have been updated since the constructor)
+        self._calls += 1
+        setup = (self, self._calls, params, int(T), noise_std, int(noise_seed))
+        obs, rew, act, lengths = _PolicyRolloutFn.apply(setup, init_states, *self._mean.parameters())
+        return obs, rew, act, lengths
+
+    def _record(self, b, setup, n0, n1, init_states, weights):
+        """the recording closed-loop launch of one batch (rollouts n0 .. n1 - 1) on its handle; a handle that still holds these
+        records is left alone"""
+        _, call, params, T, noise_std, noise_seed = setup
+
+        def launch(v):
+            v.set_params(params[n0:n1])
+            self._set_policy(v, weights, noise_std)
+            v.reset(init_state=init_states[n0:n1].detach().cpu().numpy())
+            v.set_traj_offset(0)
+            v.step_policy(T, record=True, noise_seed=noise_seed)
+
+        return self._recorded(b, (call, b), n1 - n0, launch)
+
+    def _forward(self, setup, init_states, weights):
+        A, S, O = self._dims()
+        N, T, dev = init_states.shape[0], setup[3], init_states.device
+        obs = torch.empty(N, T + 1, O, dtype=torch.float32, device=dev)
+        rew = torch.empty(N, T, dtype=torch.float32, device=dev)
+        act = torch.empty(N, T, A, dtype=torch.float32, device=dev)
+        lengths = torch.empty(N, dtype=torch.int64, device=dev)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, setup, n0, n1, init_states, weights)
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                tt = v.traj_tensors(T, n)
+                lengths[n0:n1] = v.rollout_lengths(n, T)[0]
+                obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
+                obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
+                rew[n0:n1] = tt["rew"].t()
+                act[n0:n1] = tt["act"].transpose(0, 1)
+            finally:
+                v.use_stream(None)
+        steps = torch.arange(T + 1, device=dev)
+        inside = (steps[None, :T] < lengths[:, None]).to(torch.float32)
+        obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
+        return obs, rew * inside, act * inside[:, :, None], lengths
+
+    def _backward(self, setup, init_states, weights, grad_obs, grad_rew, grad_act):
+        """(gradients of the policy's parameters, d init_states)"""
+        A, S, O = self._dims()
+        N, T, dev = init_states.shape[0], setup[3], init_states.device
+        abar = torch.empty(N, T, A, dtype=torch.float32, device=dev)
+        seen = torch.empty(N, T, O, dtype=torch.float32, device=dev)
+        d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
+        for b, (n0, n1) in enumerate(self._batches(N)):
+            n = n1 - n0
+            v = self._record(b, setup, n0, n1, init_states, weights)
+            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
+            try:
+                g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
+                da, di = self._sweep(v, T, g[0], g[1], g[2])
+                abar[n0:n1] = lanes_first(da, n)                   # (0 behind a rollout's end: the kernel writes it so)
+                d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
+                seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
+            finally:
+                v.use_stream(None)
+        params = list(self._mean.parameters())
+        with torch.enable_grad():
+            mean = self._mean(seen.detach().reshape(N * T, O))      # one batched pass over the [N T] recorded observations
+            d_params = torch.autograd.grad(mean, params, grad_outputs=abar.reshape(N * T, A).to(device=mean.device, dtype=mean.dtype))
+        return d_params, d_init
+
+
+class DifferentiablePolicyRollout(_ClosedLoopRollout):
     """roll = DifferentiablePolicyRollout(env, policy);  obs, rew, act, lengths = roll(init_states, T, domain_params=None)
 
     Closed-loop rollouts of a LinearPolicy on a FeatureStack that linear_kernel_spec accepts (optionally inside a
@@ -222,104 +327,70 @@ class DifferentiablePolicyRollout(_RecordedBatches):
             raise ValueErr(msg=f"the rollout kernel cannot evaluate {inner.features}: every elementwise feature and const_feat at "
                                "most once, MultFeat of 2 .. 4 rows, ATan2Feat, at most 39 of those two and 128 features in all")
         super().__init__(env, "DifferentiablePolicyRollout", batch_lanes)
-        A, _, O = self._dims()
-        if inner.env_spec.obs_space.flat_dim != O or inner.env_spec.act_space.flat_dim != A:
-            raise ShapeErr(msg=f"the policy maps {inner.env_spec.obs_space.flat_dim} observation rows to "
-                               f"{inner.env_spec.act_space.flat_dim} actions, the env has {O} and {A}")
+        self._check_dims(inner.env_spec.obs_space.flat_dim, inner.env_spec.act_space.flat_dim)
         self.policy, self._mean, self._terms = policy, inner, spec["terms"]
 
-    def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0):
+    def _noise_std(self):
         from .policies import linear_kernel_spec
 
-        _, S, _ = self._dims()
-        if not hasattr(init_states, "dim"):
-            raise TypeErr(msg="init_states must be a torch tensor")
-        if init_states.dim() != 2 or init_states.shape[1] != S or init_states.shape[0] < 1:
-            raise ShapeErr(msg=f"init_states must be [N, {S}], got shape {tuple(init_states.shape)}")
-        if int(T) < 1:
-            raise ValueErr(given=T, ge_constraint="1")
-        N = init_states.shape[0]
-        params = domain_param_matrix(self._base, [dict()] * N if domain_params is None else domain_params, names)
-        if params.shape[0] != N:
-            raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
-        if not init_states.is_cuda or init_states.dtype != torch.float32:
-            raise TypeErr(msg="init_states must be a float32 tensor on the GPU")
-        noise_std = linear_kernel_spec(self.policy)["noise_std"]     # (the std may have been updated since the constructor)
-        self._calls += 1
-        setup = (self, self._calls, params, int(T), noise_std, int(noise_seed))
-        obs, rew, act, lengths = _PolicyRolloutFn.apply(setup, init_states, *self._mean.parameters())
-        return obs, rew, act, lengths
+        return linear_kernel_spec(self.policy)["noise_std"]
 
-    def _record(self, b, setup, n0, n1, init_states, weight):
-        """the recording closed-loop launch of one batch (rollouts n0 .. n1 - 1) on its handle; a handle that still holds these
-        records is left alone"""
-        _, call, params, T, noise_std, noise_seed = setup
+    def _set_policy(self, v, weights, noise_std):
+        v.set_policy_linear(weights[0].detach().to(torch.float32).reshape(-1), self._terms, noise_std=noise_std)
 
-        def launch(v):
-            v.set_params(params[n0:n1])
-            v.set_policy_linear(weight.detach().to(torch.float32).reshape(-1), self._terms, noise_std=noise_std)
-            v.reset(init_state=init_states[n0:n1].detach().cpu().numpy())
-            v.set_traj_offset(0)
-            v.step_policy(T, record=True, noise_seed=noise_seed)
+    def _sweep(self, v, T, g_rew, g_obs, g_act):
+        return v.rollout_vjp_policy(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
 
-        return self._recorded(b, (call, b), n1 - n0, launch)
 
-    def _forward(self, setup, init_states, weight):
-        A, S, O = self._dims()
-        N, T, dev = init_states.shape[0], setup[3], init_states.device
-        obs = torch.empty(N, T + 1, O, dtype=torch.float32, device=dev)
-        rew = torch.empty(N, T, dtype=torch.float32, device=dev)
-        act = torch.empty(N, T, A, dtype=torch.float32, device=dev)
-        lengths = torch.empty(N, dtype=torch.int64, device=dev)
-        for b, (n0, n1) in enumerate(self._batches(N)):
-            n = n1 - n0
-            v = self._record(b, setup, n0, n1, init_states, weight)
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
-                tt = v.traj_tensors(T, n)
-                lengths[n0:n1] = v.rollout_lengths(n, T)[0]
-                obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
-                obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
-                rew[n0:n1] = tt["rew"].t()
-                act[n0:n1] = tt["act"].transpose(0, 1)
-            finally:
-                v.use_stream(None)
-        steps = torch.arange(T + 1, device=dev)
-        inside = (steps[None, :T] < lengths[:, None]).to(torch.float32)
-        obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
-        return obs, rew * inside, act * inside[:, :, None], lengths
+class DifferentiableNetRollout(_ClosedLoopRollout):
+    """roll = DifferentiableNetRollout(env, policy);  obs, rew, act, lengths = roll(init_states, T, domain_params=None)
 
-    def _backward(self, setup, init_states, weight, grad_obs, grad_rew, grad_act):
-        """(gradients of the policy's parameters, d init_states)"""
-        A, S, O = self._dims()
-        N, T, dev = init_states.shape[0], setup[3], init_states.device
-        abar = torch.empty(N, T, A, dtype=torch.float32, device=dev)
-        seen = torch.empty(N, T, O, dtype=torch.float32, device=dev)
-        d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
-        for b, (n0, n1) in enumerate(self._batches(N)):
-            n = n1 - n0
-            v = self._record(b, setup, n0, n1, init_states, weight)
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
-                g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
-                da, di = v.rollout_vjp_policy(T, g_rew=g[0], g_obs=g[1], g_act=g[2])
-                abar[n0:n1] = lanes_first(da, n)                   # (0 behind a rollout's end: the kernel writes it so)
-                d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
-                seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
-            finally:
-                v.use_stream(None)
-        params = list(self._mean.parameters())
-        with torch.enable_grad():
-            mean = self._mean(seen.detach().reshape(N * T, O))      # one batched pass over the [N T] recorded observations
-            d_params = torch.autograd.grad(mean, params, grad_outputs=abar.reshape(N * T, A).to(device=mean.device, dtype=mean.dtype))
-        return d_params, d_init
+    DifferentiablePolicyRollout for a feed-forward network: an FNN or FNNPolicy (its featurisation included) that fnn_kernel_spec
+    accepts, with one or two hidden layers, optionally inside a NormalActNoiseExplStrat.  Another policy raises TypeErr; three or
+    four hidden layers, dropout or a nonlinearity the kernel lacks ValueErr; a network that does not map the env's observation to
+    its action ShapeErr.  Call, return values and what carries gradients are DifferentiablePolicyRollout's: obs, rew and act reach
+    init_states and every parameter of the network -- backpropagation through time over the closed loop.
+    Forward: set_policy_fnn from the module's current weights, reset(init_state), one recording step_policy(T).  Backward: one
+    rollout_vjp_fnn per batch for the action adjoints and d init_states, then ONE batched pass of the network over the recorded
+    [N T] observations for the parameter gradients."""
+
+    def __init__(self, env, policy, batch_lanes: int = 65536):
+        from .policies import FNN, FNNPolicy, NormalActNoiseExplStrat, fnn_kernel_spec
+
+        inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
+        if not isinstance(inner, (FNN, FNNPolicy)):
+            raise TypeErr(msg="DifferentiableNetRollout takes an FNN or FNNPolicy, optionally inside a NormalActNoiseExplStrat, got "
+                              f"{type(inner).__name__}")
+        spec = fnn_kernel_spec(policy)
+        if spec is None:
+            raise ValueErr(msg="the rollout kernel cannot evaluate this network: hidden layers of at most 64 units, tanh / relu / "
+                               "sigmoid / no nonlinearities, no dropout")
+        if len(spec["hidden_sizes"]) > 2:
+            raise ValueErr(msg=f"the closed-loop sweep takes one or two hidden layers, got {len(spec['hidden_sizes'])}")
+        super().__init__(env, "DifferentiableNetRollout", batch_lanes)
+        net = inner.net if isinstance(inner, FNNPolicy) else inner
+        self._check_dims(net.hidden_layers[0].in_features - (1 if spec["feat"] else 0), net.output_layer.out_features)
+        self.policy, self._mean = policy, inner
+        self._arch = {k: spec[k] for k in ("hidden_sizes", "hidden_nonlin", "output_nonlin", "feat")}
+
+    def _noise_std(self):
+        from .policies import fnn_kernel_spec
+
+        return fnn_kernel_spec(self.policy)["noise_std"]
+
+    def _set_policy(self, v, weights, noise_std):
+        flat = torch.cat([w.detach().to(torch.float32).reshape(-1) for w in weights])   # parameters_to_vector's order
+        v.set_policy_fnn(flat, noise_std=noise_std, **self._arch)
+
+    def _sweep(self, v, T, g_rew, g_obs, g_act):
+        return v.rollout_vjp_fnn(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
 
 
 class _PolicyRolloutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, setup, init_states, *params):
         roll = setup[0]
-        obs, rew, act, lengths = roll._forward(setup, init_states.detach(), params[0].detach())
+        obs, rew, act, lengths = roll._forward(setup, init_states.detach(), [p.detach() for p in params])
         ctx.setup = setup
         ctx.save_for_backward(init_states, *params)
         ctx.mark_non_differentiable(lengths)
@@ -328,5 +399,6 @@ class _PolicyRolloutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_obs, grad_rew, grad_act, _grad_lengths):
         init_states, *params = ctx.saved_tensors
-        d_params, d_init = ctx.setup[0]._backward(ctx.setup, init_states.detach(), params[0].detach(), grad_obs, grad_rew, grad_act)
+        d_params, d_init = ctx.setup[0]._backward(ctx.setup, init_states.detach(), [p.detach() for p in params], grad_obs, grad_rew,
+                                                  grad_act)
         return (None, d_init) + tuple(d_params)

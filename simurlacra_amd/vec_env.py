@@ -887,6 +887,19 @@ class VecSimEnv:
                     "vs_rollout_vjp_policy")
         return d_act, d_init
 
+    def rollout_vjp_fnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
+        """rollout_vjp_policy for records made with the feed-forward network of set_policy_fnn that is still on the handle (one or
+        two hidden layers; vs_rollout_vjp_fnn): a_t = net(x_t) + n_t with the exploration noise n_t a constant.  Same cotangents,
+        same returns: d_act[t] is the TOTAL adjoint of the raw action a_t -- the network's parameter gradient is one batched
+        backward pass over the recorded observations with it as grad_outputs --, d_init includes the feedback through the network."""
+        T = int(t_steps)
+        S, A, O, H = (self.dims[k] for k in "SAOH")
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld))))
+        self._check(self._lib.vs_rollout_vjp_fnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
+                    "vs_rollout_vjp_fnn")
+        return d_act, d_init
+
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")
 
