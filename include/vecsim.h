@@ -480,7 +480,7 @@ int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_
  * rule per position; ATan2Feat(y, x): (x, -y) / (x^2 + y^2)).  After t = 0 the initial observation takes g_obs[0] + gpol.
  * With a stack of constant features the result equals vs_rollout_vjp's bit for bit.
  * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no linear policy on the handle (an FNN, RNN
- * or playback policy, or none) and a policy population on the handle (VS_ERR_STATE).  Feed-forward networks have vs_rollout_vjp_fnn; RNN policies have no closed-loop sweep. */
+ * or playback policy, or none) and a policy population on the handle (VS_ERR_STATE).  Feed-forward networks have vs_rollout_vjp_fnn, recurrent policies vs_rollout_vjp_rnn. */
 int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                           const float* g_state_last, float* d_act, float* d_init);
 /* ... and for rollouts recorded with the handle's current FEED-FORWARD NETWORK (vs_set_policy_fnn) of one or two hidden layers in the
@@ -500,6 +500,25 @@ int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const fl
  * and their transposes do not fit the register file) (VS_ERR_STATE). */
 int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, float* d_act, float* d_init);
+/* ... and for rollouts recorded with the handle's current RECURRENT policy (vs_set_policy_rnn: RNN tanh / relu, GRU or LSTM of one or
+ * two layers) in the loop: (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0), p the packed hidden state [Hs] (h of layer 0, 1, .. then, LSTM, c
+ * of layer 0, 1, ..), x_t the observation rows the policy sees (obs_idx), n_t constant.  The differentiated function is
+ *     Phi = sum g_rew r + sum g_obs obs + sum g_act a + g_state_last (s_L, h_L) + g_hid_last p_L
+ * and TWO adjoints run backwards: the env's lambda [S + H] and the policy's eta [Hs].  Arguments, layout (ld = vs_ld(h)), stream, L and
+ * the NULL-is-zero rule of the cotangents are vs_rollout_vjp_fnn's; new: g_hid_last [Hs][ld] (NULL = 0), d_hid [t_steps][Hs][ld] and
+ * d_hid0 [Hs][ld] (either may be NULL: not written).  d_act[t] is the total adjoint abar_t of the raw action; d_hid[t] is the TOTAL
+ * cotangent of p_{t+1} -- everything downstream of step t, g_hid_last at t = L - 1, step t's own output layer not included --, so that
+ *     d Phi / d theta = sum_t (d F / d theta)(x_t, p_t)^T (abar_t, d_hid[t])
+ * is one batched single-step backward pass of the policy over the recorded observations and hidden states (row t of
+ * VS_POLICY_HIDDEN_REC is p_t), left to the caller.  d_hid0 is the cotangent of p_0, d_init includes the feedback through the policy.
+ * Per step the cell is recomputed at the recorded (x_t, p_t) with the rollout kernel's expressions and pulled back with the derivatives
+ * of the functions that ran (tanh 1 - y^2, sigmoid y (1 - y), relu [y > 0]).  Rows t >= L of d_act and d_hid and lanes >= n_envs get
+ * zeros and read no cotangent.
+ * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no recurrent policy on the handle (an FNN,
+ * linear or playback policy, or none), a policy population on the handle, no hidden-state record plane or one whose width differs from
+ * the policy's Hs (VS_ERR_STATE). */
+int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

@@ -46,7 +46,8 @@ def __getattr__(name):
         from . import sysid
 
         return getattr(sysid, name)
-    if name in ("DifferentiableRollout", "DifferentiablePolicyRollout", "DifferentiableNetRollout", "discounted_return"):
+    if name in ("DifferentiableRollout", "DifferentiablePolicyRollout", "DifferentiableNetRollout", "DifferentiableRecurrentRollout",
+                "discounted_return"):
         from . import diffsim
 
         return getattr(diffsim, name)

@@ -632,7 +632,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 313; }
+int vs_version(void) { return 314; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1757,6 +1757,23 @@ int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_fnn(h, v, g_act, t_steps));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0) {
+    const auto policy = [](vs_handle h) -> const char* {
+        if (!h->rnn.w) return "no recurrent policy on the handle (vs_set_policy_rnn)";
+        if (h->pop.w) return "not available with a policy population on the handle";
+        if (!h->d_hrec || h->hrec_width != h->rnn.hs)
+            return "needs the hidden-state record plane at the policy's hidden size (vs_set_policy_hidden_record)";
+        return nullptr;
+    };
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, policy)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
+    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_rnn(h, v, g_act, g_hid_last, d_hid, d_hid0, t_steps));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -16,6 +16,7 @@
 //   k_rollout_vjp   vs_rollout_vjp    reverse-mode sweep over a recorded rollout: gradients w.r.t. its actions and initial state
 //   k_rollout_vjp_lin  vs_rollout_vjp_policy  the same sweep with the handle's linear policy in the loop (closed-loop adjoints)
 //   k_rollout_vjp_fnn  vs_rollout_vjp_fnn     ... with the handle's feed-forward network of one or two hidden layers in the loop
+//   k_rollout_vjp_rnn  vs_rollout_vjp_rnn     ... with the handle's recurrent policy in the loop (a second adjoint for its hidden state)
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2843,6 +2844,346 @@ __global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev
     for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
 }
 
+// --------------------------------------------------------------------- reverse-mode sweep with a recurrent policy in the loop
+// vs_rollout_vjp_rnn: k_rollout_vjp for rollouts that k_rollout_rnn recorded -- (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0) with the
+// handle's recurrent policy (Rnn: the same packed blocks and observation view), p the packed hidden state [hs] and n_t constant.  Two
+// adjoints run backwards through time: the env's lambda [S + H], as in k_rollout_vjp_lin, and the policy's eta [hs].
+//   * Per step t < L: the env part of k_rollout_vjp_lin (observation cotangent g_obs[t + 1] + gpol), abar_t = out[NS + j] + g_act[t][j]
+//     to d_act[t]; eta -- the total cotangent of p_{t+1}: everything downstream of step t, g_hid_last at t = L - 1, step t's own output
+//     layer NOT included -- to d_hid[t]; then (abar_t, eta) is pulled back through F at the recorded (x_t, p_t), p_t = row t of the
+//     hidden-state record plane, x_t = E::observe(s_t) through obs_idx.  That yields the new eta (cotangent of p_t) and gx, which goes
+//     back to observation rows through obs_idx: the next gpol.  After t = 0: vjp_observe with g_obs[0] + gpol, d_init = lambda, d_hid0 = eta.
+//   * F is k_rollout_rnn's arithmetic (rnn_unit_act: the same sums in the same order, tanh_fast, the bare v_rcp_f32 sigmoid), the
+//     derivatives are those of the functions that ran, from the recomputed values: tanh 1 - y^2, sigmoid y (1 - y), relu y > 0.
+//   * Shape of k_rollout_rnn: one wave of 64 envs, lane = env, weights as scalar operands, per-lane vectors as LDS rows [k][64].  With
+//     scalar weights the transposed products W^T delta are lane-local accumulations into LDS rows: no transposed copy, no lane ever
+//     reads another lane's column, no barrier and no fence.  Fused per unit: recompute unit u's gates, form its deltas, scatter them
+//     into the adjoint rows of its inputs; no gate value is stored.  Layer 0's h' (layer 1's input) takes one forward pass first, and
+//     with an output nonlinearity the top layer another one for y_out; an identity output layer needs neither.
+//   * LDS rows of hp units: h_t (L) | layer 0's h' (1 if L = 2) | adjoint of c, updated in place (L, LSTM) | adjoint of h' (L) |
+//     accumulators of the adjoint of h (L).  The last two swap roles after every step: a unit zeroes its adjoint entry when it reads
+//     it, so the rows a step leaves behind are clean.  c_t is read straight from the record plane (each unit reads only its own).
+//     Two LSTM layers of 64: 576 rows = 144 KiB.
+//   * A lane with t >= L (lanes >= n: L = 0) reads no record and no cotangent: its h, c, x, abar and eta are zeros by select, every
+//     delta is 0 times a finite value, d_act[t] and d_hid[t] get 0 and gpol stays 0.  A row t that NO lane of the wave reaches (every
+//     rollout of the wave ended before it) only writes those zeros: a wave-uniform skip.  Nothing of the handle is written.
+template <int G>
+struct RnnAct {
+    float g[G];  // G = 1: h';  3: r, z, n;  4: i, f, g, o
+    float hn;    // GRU: W_hn h + b_hn
+};
+// unit u of a layer from its inputs, as k_rollout_rnn forms it: x (layer 0) or the rows hin (layer 1), the state rows hst
+template <int G>
+__device__ __forceinline__ RnnAct<G> rnn_unit_act(int cell, const __attribute__((address_space(4))) float* wu, bool first,
+                                                  const float (&x)[RNN_XP], const float* hin, const float* hst, int hp) {
+    typedef const __attribute__((address_space(4))) float* cfp;
+    float ai[G], ah[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) ai[g] = 0.f, ah[g] = 0.f;
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < RNN_XP; ++k)
+#pragma unroll
+            for (int g = 0; g < G; ++g) ai[g] = fmaf(wu[k * G + g], x[k], ai[g]);
+    } else {
+        for (int k = 0; k < hp; k += 4) {
+            float v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = hin[(k + q) * 64];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int g = 0; g < G; ++g) ai[g] = fmaf(wu[(k + q) * G + g], v[q], ai[g]);
+        }
+    }
+    const cfp wh = wu + (first ? RNN_XP : hp) * G;
+    for (int k = 0; k < hp; k += 4) {
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = hst[(k + q) * 64];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int g = 0; g < G; ++g) ah[g] = fmaf(wh[(k + q) * G + g], v[q], ah[g]);
+    }
+    const cfp bi = wh + hp * G, bh = bi + G;
+    auto sigm = [](float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); };
+    RnnAct<G> r;
+    r.hn = 0.f;
+    if constexpr (G == 1) {
+        const float v = (ai[0] + bi[0]) + (ah[0] + bh[0]);
+        r.g[0] = cell == RNN_CELL_RELU ? fmaxf(v, 0.f) : tanh_fast(v);
+    } else if constexpr (G == 3) {
+        r.g[0] = sigm((ai[0] + bi[0]) + (ah[0] + bh[0]));
+        r.g[1] = sigm((ai[1] + bi[1]) + (ah[1] + bh[1]));
+        r.hn = ah[2] + bh[2];
+        r.g[2] = tanh_fast((ai[2] + bi[2]) + r.g[0] * r.hn);
+    } else {
+        r.g[0] = sigm((ai[0] + bi[0]) + (ah[0] + bh[0]));
+        r.g[1] = sigm((ai[1] + bi[1]) + (ah[1] + bh[1]));
+        r.g[2] = tanh_fast((ai[2] + bi[2]) + (ah[2] + bh[2]));
+        r.g[3] = sigm((ai[3] + bi[3]) + (ah[3] + bh[3]));
+    }
+    return r;
+}
+// rows of 64 floats of LDS per workgroup (see above)
+__host__ __device__ constexpr int rnn_vjp_rows(int gates, int n_layers, int hp) {
+    return (n_layers + (n_layers > 1 ? 1 : 0) + (gates == 4 ? n_layers : 0) + 2 * n_layers) * hp;
+}
+template <class E, int G>
+__global__ __launch_bounds__(64) void k_rollout_vjp_rnn(Task T, Dev d, Vjp V, const float* g_act, const float* g_hid_last, float* d_hid,
+                                                        float* d_hid0, Rnn P, int t_steps) {
+    static_assert(G == 1 || G == 3 || G == 4, "RNN, GRU or LSTM");
+    static_assert(E::O <= RNN_XP, "input row");
+    extern __shared__ float l_rnnb[];                            // [row][64]
+    typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    const cfp W = (cfp)P.w;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * 64 + lane;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    const int Ln = P.n_layers, H = P.hidden, hp = P.hp, hs = P.hs;
+    const int ns = (G == 4 ? 2 : 1) * Ln;  // state rows (in units of hp)
+    float* const ls = l_rnnb + lane;       // this lane's column
+    float* const hrow = ls;                                            // h_t of every layer
+    float* const frow = hrow + (size_t)(Ln * hp) * 64;                 // layer 0's h' (two layers)
+    float* const cadj = frow + (size_t)(Ln > 1 ? hp : 0) * 64;         // adjoint of c (LSTM)
+    float* adj = cadj + (size_t)(G == 4 ? Ln * hp : 0) * 64;           // adjoint of h' = the h part of eta
+    float* acc = adj + (size_t)(Ln * hp) * 64;                         // accumulators of the adjoint of h
+    for (int r = 0; r < rnn_vjp_rows(G, Ln, hp); ++r) ls[r * 64] = 0.f;
+    float c[E::K];
+    load_consts<E, false>(d, i, c, 0, E::KS);
+    // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (bits behind t_steps may be stale)
+    int L = 0;
+    if (valid) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = d.traj_done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    float lam[NS], x[NI], out[NI], gob[E::O], gpol[E::O];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = (valid && V.g_last) ? V.g_last[(size_t)k * ld + i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = 0.f;
+#pragma unroll
+    for (int q = 0; q < E::O; ++q) gpol[q] = 0.f;
+
+    for (int t = t_steps - 1; t >= 0; --t) {
+        const bool live = t < L;
+        if (__builtin_amdgcn_ballot_w64(live) == 0) {  // wave-uniform: no lane's rollout reaches row t, and every adjoint is still 0
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = 0.f;
+            if (d_hid != nullptr)
+                for (int p = 0; p < hs; ++p) d_hid[((size_t)t * hs + p) * ld + i] = 0.f;
+            continue;
+        }
+        float xv[RNN_XP], ab[E::A];
+#pragma unroll
+        for (int k = 0; k < NI; ++k) out[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < RNN_XP; ++k) xv[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) ab[j] = 0.f;
+        if (live) {
+            load_record_inputs<E>(d.traj_rec + (size_t)t * Rec<E, 2>::F * ld, ld, i, x);
+            const float grew = V.g_rew ? V.g_rew[(size_t)t * ld + i] : 0.f;
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[((size_t)(t + 1) * E::O + q) * ld + i] : 0.f) + gpol[q];
+            vjp_step<E>(T, c, x, t, lam, grew, gob, out);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) lam[k] = out[k];
+            // ---- the total adjoint of a_t
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) {
+                ab[j] = g_act ? out[NS + j] + g_act[((size_t)t * E::A + j) * ld + i] : out[NS + j];
+                out[NS + j] = ab[j];
+            }
+            // ---- what the policy saw of obs_t, as in k_rollout_rnn
+            float ob[E::O];
+            E::observe(x, ob);
+            if (P.ident) {
+#pragma unroll
+                for (int k = 0; k < RNN_XP; ++k) xv[k] = k < E::O ? ob[k] : 0.f;
+            } else {
+#pragma unroll
+                for (int k = 0; k < RNN_XP; ++k) {
+                    float v = 0.f;
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                    xv[k] = v;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = out[NS + j];
+        // ---- eta: g_hid_last joins at the lane's last step; the cotangent of p_{t+1} goes to d_hid[t]
+        const bool inj = g_hid_last != nullptr && t == L - 1;
+        if (d_hid != nullptr || __builtin_amdgcn_ballot_w64(inj) != 0) {
+            for (int q = 0, p = 0; q < ns; ++q)
+                for (int j = 0; j < H; ++j, ++p) {
+                    float* r = q < Ln ? adj + (size_t)(q * hp + j) * 64 : cadj + (size_t)((q - Ln) * hp + j) * 64;
+                    float v = *r;
+                    if (inj) {
+                        v += g_hid_last[(size_t)p * ld + i];
+                        *r = v;
+                    }
+                    if (d_hid) d_hid[((size_t)t * hs + p) * ld + i] = live ? v : 0.f;
+                }
+        }
+        // ---- p_t: the h rows into LDS (c_t is read where it is used)
+        const float* const hr = P.hrec + (size_t)t * (size_t)hs * ld + i;
+        for (int l = 0; l < Ln; ++l)
+            for (int j = 0; j < H; ++j) hrow[(l * hp + j) * 64] = live ? hr[(size_t)(l * H + j) * ld] : 0.f;
+        // ---- forward: layer 0's h' for layer 1, and y_out where the output nonlinearity needs it
+        float dout[E::A];
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) dout[j] = ab[j];
+        const bool need_y = P.out_nonlin != FNN_ID;
+        {
+            float yo[E::A];
+#pragma unroll
+            for (int j = 0; j < E::A; ++j) yo[j] = 0.f;
+            for (int l = 0; l < (need_y ? Ln : Ln - 1); ++l) {
+                const float* hst = hrow + (size_t)(l * hp) * 64;
+                for (int u = 0; u < H; ++u) {
+                    const RnnAct<G> a = rnn_unit_act<G>(P.cell, W + P.off[l] + u * P.blk[l], l == 0, xv, frow, hst, hp);
+                    float hv;
+                    if constexpr (G == 1) {
+                        hv = a.g[0];
+                    } else if constexpr (G == 3) {
+                        hv = (1.0f - a.g[1]) * a.g[2] + a.g[1] * hst[u * 64];
+                    } else {
+                        const float cu = live ? hr[(size_t)((Ln + l) * H + u) * ld] : 0.f;
+                        hv = a.g[3] * tanh_fast(a.g[1] * cu + a.g[0] * a.g[2]);
+                    }
+                    if (l < Ln - 1) {
+                        frow[u * 64] = hv;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < E::A; ++j) yo[j] = fmaf(W[P.off_o + j * hp + u], hv, yo[j]);
+                    }
+                }
+            }
+            if (need_y) {
+#pragma unroll
+                for (int j = 0; j < E::A; ++j)
+                    dout[j] = ab[j] * fnn_nonlin_grad(P.out_nonlin, fnn_nonlin(P.out_nonlin, yo[j] + W[P.off_o + E::A * hp + j]));
+            }
+        }
+        // ---- backward, top layer first: per unit recompute, deltas, scatter
+        float gx[RNN_XP];
+#pragma unroll
+        for (int k = 0; k < RNN_XP; ++k) gx[k] = 0.f;
+        for (int l = Ln - 1; l >= 0; --l) {
+            const float* hst = hrow + (size_t)(l * hp) * 64;
+            float* const ain = adj + (size_t)((l > 0 ? l - 1 : 0) * hp) * 64;  // adjoint of this layer's input rows (l > 0)
+            float* const ah = acc + (size_t)(l * hp) * 64;
+            const int inp = l == 0 ? RNN_XP : hp;
+            for (int u = 0; u < H; ++u) {
+                const cfp wu = W + P.off[l] + u * P.blk[l];
+                const RnnAct<G> a = rnn_unit_act<G>(P.cell, wu, l == 0, xv, frow, hst, hp);
+                float dh = adj[(l * hp + u) * 64];
+                adj[(l * hp + u) * 64] = 0.f;  // (read once: the rows are clean when they become the accumulators)
+                if (l == Ln - 1) {
+#pragma unroll
+                    for (int j = 0; j < E::A; ++j) dh = fmaf(W[P.off_o + j * hp + u], dout[j], dh);
+                }
+                float di[G], dg[G];  // deltas of the pre-activations: the input part and the hidden part
+                if constexpr (G == 1) {
+                    const float y = a.g[0];
+                    di[0] = dg[0] = dh * (P.cell == RNN_CELL_RELU ? (y > 0.f ? 1.0f : 0.f) : fmaf(-y, y, 1.0f));
+                } else if constexpr (G == 3) {
+                    const float r = a.g[0], z = a.g[1], n = a.g[2], hu = hst[u * 64];
+                    const float dn = dh * (1.0f - z) * fmaf(-n, n, 1.0f);
+                    di[0] = dg[0] = dn * a.hn * (r * (1.0f - r));
+                    di[1] = dg[1] = dh * (hu - n) * (z * (1.0f - z));
+                    di[2] = dn;
+                    dg[2] = dn * r;
+                    ah[u * 64] = fmaf(dh, z, ah[u * 64]);
+                } else {
+                    const float ig = a.g[0], fg = a.g[1], gg = a.g[2], og = a.g[3];
+                    const float cu = live ? hr[(size_t)((Ln + l) * H + u) * ld] : 0.f;
+                    const float tc = tanh_fast(fg * cu + ig * gg);
+                    const float dc = fmaf(dh * og, fmaf(-tc, tc, 1.0f), cadj[(l * hp + u) * 64]);
+                    cadj[(l * hp + u) * 64] = dc * fg;
+                    di[0] = dg[0] = dc * gg * (ig * (1.0f - ig));
+                    di[1] = dg[1] = dc * cu * (fg * (1.0f - fg));
+                    di[2] = dg[2] = dc * ig * fmaf(-gg, gg, 1.0f);
+                    di[3] = dg[3] = dh * tc * (og * (1.0f - og));
+                }
+                if (l == 0) {
+#pragma unroll
+                    for (int k = 0; k < RNN_XP; ++k)
+#pragma unroll
+                        for (int g = 0; g < G; ++g) gx[k] = fmaf(wu[k * G + g], di[g], gx[k]);
+                } else {
+                    for (int k = 0; k < hp; k += 4) {
+                        float v[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) v[q] = ain[(k + q) * 64];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+#pragma unroll
+                            for (int g = 0; g < G; ++g) v[q] = fmaf(wu[(k + q) * G + g], di[g], v[q]);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) ain[(k + q) * 64] = v[q];
+                    }
+                }
+                const cfp wh = wu + inp * G;
+                for (int k = 0; k < hp; k += 4) {
+                    float v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = ah[(k + q) * 64];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int g = 0; g < G; ++g) v[q] = fmaf(wh[(k + q) * G + g], dg[g], v[q]);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) ah[(k + q) * 64] = v[q];
+                }
+            }
+        }
+        {  // the accumulators are the new eta; the rows it leaves are zero again
+            float* const sw = adj;
+            adj = acc;
+            acc = sw;
+        }
+        // ---- gx back to observation rows: the next gpol
+        if (live) {
+            if (P.ident) {
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) gpol[j] = gx[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < E::O; ++j) gpol[j] = 0.f;
+#pragma unroll
+                for (int k = 0; k < RNN_XP; ++k)
+#pragma unroll
+                    for (int j = 0; j < E::O; ++j) gpol[j] += (k < P.n_vis && P.obs_idx[k] == j) ? gx[k] : 0.f;  // wave-uniform selects
+            }
+        }
+    }
+    if (L > 0) {  // x is row 0 here: every lane with a rollout ran t = 0 last
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) gob[q] = (V.g_obs ? V.g_obs[(size_t)q * ld + i] : 0.f) + gpol[q];
+        vjp_observe<E>(x, gob, lam);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
+    if (d_hid0)
+        for (int q = 0, p = 0; q < ns; ++q)
+            for (int j = 0; j < H; ++j, ++p)
+                d_hid0[(size_t)p * ld + i] = q < Ln ? adj[(q * hp + j) * 64] : cadj[((q - Ln) * hp + j) * 64];
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -3875,6 +4216,8 @@ struct Launch {
     static void rollout_vjp(vs_env* h, const Vjp& v, int t_steps);            // vs_rollout_vjp
     static void rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_policy
     static void rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_fnn
+    static void rollout_vjp_rnn(vs_env* h, const Vjp& v, const float* g_act, const float* g_hid_last, float* d_hid, float* d_hid0,
+                                int t_steps);                                               // vs_rollout_vjp_rnn
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -4167,6 +4510,27 @@ void Launch<E>::rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int
             hipLaunchKernelGGL((k_rollout_vjp_fnn<E, NH>), dim3((unsigned)(h->d.ld / 64)), dim3(64 * FNNB_WAVES), 0, h->stream, h->task,
                                h->d, v, g_act, h->fnn, t_steps);
         else no_kernel("rollout_vjp_fnn");
+    });
+}
+
+template <class E>
+void Launch<E>::rollout_vjp_rnn(vs_env* h, const Vjp& v, const float* g_act, const float* g_hid_last, float* d_hid, float* d_hid0,
+                                int t_steps) {
+    // one wave of 64 envs per workgroup, as rollout_rnn; the LDS rows are the only per-shape resource (at most 144 KiB)
+    Rnn P = h->rnn;
+    P.hrec = h->d_hrec;
+    with_int<1, 3, 4>(rnn_gates(P.cell), [&](auto G) __attribute__((always_inline)) {
+        if constexpr (!std::is_same<E, BobD>::value) {
+            const size_t lds = (size_t)rnn_vjp_rows(G, P.n_layers, P.hp) * 64 * sizeof(float);
+            auto kern = k_rollout_vjp_rnn<E, G>;
+            // beyond the 64 KiB a kernel gets by default the limit is raised; refused, there is no launch and the entry point reports
+            // this error (it is the runtime's last one)
+            if (lds > 64 * 1024 &&
+                hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return;
+            hipLaunchKernelGGL(kern, dim3((unsigned)(h->d.ld / 64)), dim3(64), lds, h->stream, h->task, h->d, v, g_act, g_hid_last, d_hid,
+                               d_hid0, P, t_steps);
+        } else no_kernel("rollout_vjp_rnn");
     });
 }
 

@@ -15,6 +15,9 @@ DifferentiablePolicyRollout is the closed-loop form: a LinearPolicy on a feature
 dependence on the observation is part of the adjoint -- followed by one batched torch pass over the recorded observations for the
 gradient of the policy's parameters.  DifferentiableNetRollout is the same for a feed-forward network of one or two hidden layers
 (vs_set_policy_fnn, vs_rollout_vjp_fnn, k_rollout_vjp_fnn): backpropagation through time with the network inside the sweep.
+DifferentiableRecurrentRollout is the form for RNNPolicy / GRUPolicy / LSTMPolicy (vs_set_policy_rnn, vs_rollout_vjp_rnn,
+k_rollout_vjp_rnn): the sweep carries a second adjoint for the policy's hidden state, and the parameter pass is one batched
+single-step pass over the recorded observations and hidden states.
 """
 from typing import Optional, Sequence
 
@@ -198,9 +201,11 @@ class _RolloutFn(torch.autograd.Function):
 
 
 class _ClosedLoopRollout(_RecordedBatches):
-    """What the two closed-loop classes share: the call, the recording launch, the outputs and the backward pass.  A subclass sets
+    """What the closed-loop classes share: the call, the recording launch, the outputs and the backward pass.  A subclass sets
     self.policy (what the caller gave), self._mean (the module whose parameters get gradients: the policy without its exploration
-    noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now."""
+    noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now.
+    A policy with more than the action adjoint to pull back (a hidden state) also says what it keeps of a batch's sweep (_keep)
+    and how the parameter gradients come from it (_param_grads)."""
 
     def _check_dims(self, obs_dim, act_dim):
         A, _, O = self._dims()
@@ -214,7 +219,20 @@ class _ClosedLoopRollout(_RecordedBatches):
         raise NotImplementedError
 
     def _sweep(self, v, T, g_rew, g_obs, g_act):
+        """(d_act, d_init, anything else the sweep returns) of one batch"""
         raise NotImplementedError
+
+    def _keep(self, v, T, n, more):
+        """what _param_grads needs of a batch beyond abar and the observations; `more`: the sweep's further returns"""
+        return None
+
+    def _param_grads(self, seen, abar, kept):
+        """gradients of self._mean's parameters: one batched pass over the [N T] recorded observations"""
+        N, T, O = seen.shape
+        with torch.enable_grad():
+            mean = self._mean(seen.detach().reshape(N * T, O))
+            return torch.autograd.grad(mean, list(self._mean.parameters()),
+                                       grad_outputs=abar.reshape(N * T, -1).to(device=mean.device, dtype=mean.dtype))
 
     def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0):
         _, S, _ = self._dims()
@@ -282,23 +300,21 @@ class _ClosedLoopRollout(_RecordedBatches):
         abar = torch.empty(N, T, A, dtype=torch.float32, device=dev)
         seen = torch.empty(N, T, O, dtype=torch.float32, device=dev)
         d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
+        kept = []
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, setup, n0, n1, init_states, weights)
             v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
             try:
                 g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
-                da, di = self._sweep(v, T, g[0], g[1], g[2])
+                da, di, *more = self._sweep(v, T, g[0], g[1], g[2])
                 abar[n0:n1] = lanes_first(da, n)                   # (0 behind a rollout's end: the kernel writes it so)
                 d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
                 seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
+                kept.append(self._keep(v, T, n, more))
             finally:
                 v.use_stream(None)
-        params = list(self._mean.parameters())
-        with torch.enable_grad():
-            mean = self._mean(seen.detach().reshape(N * T, O))      # one batched pass over the [N T] recorded observations
-            d_params = torch.autograd.grad(mean, params, grad_outputs=abar.reshape(N * T, A).to(device=mean.device, dtype=mean.dtype))
-        return d_params, d_init
+        return self._param_grads(seen, abar, kept), d_init
 
 
 class DifferentiablePolicyRollout(_ClosedLoopRollout):
@@ -384,6 +400,74 @@ class DifferentiableNetRollout(_ClosedLoopRollout):
 
     def _sweep(self, v, T, g_rew, g_obs, g_act):
         return v.rollout_vjp_fnn(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
+
+
+class DifferentiableRecurrentRollout(_ClosedLoopRollout):
+    """roll = DifferentiableRecurrentRollout(env, policy);  obs, rew, act, lengths = roll(init_states, T, domain_params=None)
+
+    DifferentiableNetRollout for a recurrent policy: an RNNPolicy (tanh / relu), GRUPolicy or LSTMPolicy that rnn_kernel_spec accepts
+    (one or two layers of at most 64 units), optionally inside a NormalActNoiseExplStrat.  Another policy raises TypeErr; dropout or
+    a shape the kernel lacks ValueErr; a policy that does not map the env's observation to its action ShapeErr.  Call, return
+    values and what carries gradients are DifferentiableNetRollout's: backpropagation through time over the closed loop, the
+    policy's hidden state included.  Every rollout starts from init_hidden(), a constant.
+    Forward: set_policy_rnn from the module's current weights (that zeroes the hidden state), set_policy_hidden_record(Hs),
+    reset(init_state), one recording step_policy(T).  Backward: one rollout_vjp_rnn per batch for the adjoints of the actions and of
+    the hidden states and d init_states, then ONE batched single-step pass of the policy over the recorded [N T] observations and
+    hidden states -- not sequential in time, 2^20 rows at a time -- for the parameter gradients."""
+
+    _PASS_ROWS = 1 << 20  # rows of the batched parameter pass at a time (the device RNN library's tensors are indexed with 32 bits)
+
+    def __init__(self, env, policy, batch_lanes: int = 65536):
+        from .policies import NormalActNoiseExplStrat, _RNNPolicyBase, rnn_kernel_spec
+
+        inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
+        if not isinstance(inner, _RNNPolicyBase):
+            raise TypeErr(msg="DifferentiableRecurrentRollout takes an RNNPolicy, GRUPolicy or LSTMPolicy, optionally inside a "
+                              f"NormalActNoiseExplStrat, got {type(inner).__name__}")
+        spec = rnn_kernel_spec(policy)
+        if spec is None:
+            raise ValueErr(msg="the rollout kernel cannot evaluate this recurrent policy: one or two layers of at most 64 units, "
+                               "tanh / relu / sigmoid / no output nonlinearity, no dropout")
+        super().__init__(env, "DifferentiableRecurrentRollout", batch_lanes)
+        self._check_dims(inner.rnn_layers.input_size, inner.output_layer.out_features)
+        self.policy, self._mean = policy, inner
+        self._arch = {k: spec[k] for k in ("cell", "n_layers", "hidden_size", "output_nonlin")}
+        self._hs = inner.hidden_size
+
+    def _noise_std(self):
+        from .policies import rnn_kernel_spec
+
+        return rnn_kernel_spec(self.policy)["noise_std"]
+
+    def _set_policy(self, v, weights, noise_std):
+        flat = torch.cat([w.detach().to(torch.float32).reshape(-1) for w in weights])   # parameters_to_vector's order
+        v.set_policy_rnn(flat, noise_std=noise_std, **self._arch)                       # (hidden state: zeros = init_hidden())
+        v.set_policy_hidden_record(self._hs)
+
+    def _sweep(self, v, T, g_rew, g_obs, g_act):
+        return v.rollout_vjp_rnn(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
+
+    def _keep(self, v, T, n, more):
+        """(cotangents of p_{t+1} [n, T, Hs], recorded p_t [n, T, Hs])"""
+        return lanes_first(more[0], n), lanes_first(v.hidden_record_tensor()[:T], n)
+
+    def _param_grads(self, seen, abar, kept):
+        N, T, O = seen.shape
+        seen = seen.detach()
+        params, total = list(self._mean.parameters()), None
+        lanes = max(1, self._PASS_ROWS // T)  # whole rollouts per pass (the rows are independent: any split gives the same sum)
+        n0 = 0
+        for d_hid, hid in kept:  # batch by batch, sliced from what the batch kept: no second copy of all [N T] rows
+            for l0 in range(0, d_hid.shape[0], lanes):
+                at, rows = slice(l0, min(l0 + lanes, d_hid.shape[0])), slice(n0 + l0, n0 + min(l0 + lanes, d_hid.shape[0]))
+                with torch.enable_grad():
+                    act, p_new = self._mean(seen[rows].reshape(-1, O), hid[at].detach().reshape(-1, self._hs))
+                    g = torch.autograd.grad((act, p_new), params, grad_outputs=(
+                        abar[rows].reshape(-1, abar.shape[2]).to(device=act.device, dtype=act.dtype),
+                        d_hid[at].reshape(-1, self._hs).to(device=p_new.device, dtype=p_new.dtype)))
+                total = g if total is None else tuple(a + b for a, b in zip(total, g))
+            n0 += d_hid.shape[0]
+        return total
 
 
 class _PolicyRolloutFn(torch.autograd.Function):

@@ -149,6 +149,7 @@ class VecSimEnv:
         self._h = h
         self.ld = int(self._lib.vs_ld(h))
         self._traj_cap = 0
+        self._rnn_hs = 0  # the packed hidden size of the recurrent policy on the handle (0: none)
 
     # ------------------------------------------------------------------------------------------------ helpers
     @staticmethod
@@ -899,6 +900,30 @@ class VecSimEnv:
         self._check(self._lib.vs_rollout_vjp_fnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
                     "vs_rollout_vjp_fnn")
         return d_act, d_init
+
+    def rollout_vjp_rnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None, g_hid_last=None):
+        """rollout_vjp_policy for records made with the recurrent policy of set_policy_rnn that is still on the handle, with the
+        hidden-state record plane on at the policy's packed hidden size Hs (set_policy_hidden_record; vs_rollout_vjp_rnn):
+        (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0).  One more cotangent, g_hid_last [Hs, ld], on the final hidden state p_L.  Returns
+        (d_act [T, A, ld], d_init [S + H, ld], d_hid [T, Hs, ld], d_hid0 [Hs, ld]): d_act[t] is the total adjoint of the raw
+        action a_t and d_hid[t] the total cotangent of p_{t+1} (step t's own output layer not included) -- the parameter gradient
+        is one batched single-step backward pass of the policy over the recorded (obs_t, p_t) with the two as grad_outputs --,
+        d_hid0 is the cotangent of the initial hidden state, d_init includes the feedback through the policy."""
+        import torch
+
+        T = int(t_steps)
+        S, A, O, H = (self.dims[k] for k in "SAOH")
+        Hs = self._rnn_hs
+        if not Hs:
+            raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld)),
+                                                    ("g_hid_last", g_hid_last, (Hs, self.ld))))
+        d_hid = torch.empty(T, Hs, self.ld, dtype=torch.float32, device=d_act.device)
+        d_hid0 = torch.empty(Hs, self.ld, dtype=torch.float32, device=d_act.device)
+        self._check(self._lib.vs_rollout_vjp_rnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr()),
+                                                 C.c_void_p(d_hid.data_ptr()), C.c_void_p(d_hid0.data_ptr())), "vs_rollout_vjp_rnn")
+        return d_act, d_init, d_hid, d_hid0
 
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")
