@@ -500,6 +500,23 @@ int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const fl
  * and their transposes do not fit the register file) (VS_ERR_STATE). */
 int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, float* d_act, float* d_init);
+/* The parameter gradient that vs_rollout_vjp_fnn leaves to the caller, as one device pass over the same records:
+ *     d Phi / d theta = sum over the rows t < L of every lane i < n_envs of (d pi / d theta)(x_t)^T abar_t
+ * for the handle's current feed-forward network of one or two hidden layers, i.e. per row
+ *     dW_out += delta_out y_last^T, db_out += delta_out;  dW_l += delta_l y_{l-1}^T, db_l += delta_l  (y_0 = x_t)
+ * with delta_out = abar_t (.) g'(y_out), delta_l = (W_{l+1}^T delta_{l+1}) (.) f'(y_l) and the activations recomputed with the rollout
+ * kernel's expressions, as in vs_rollout_vjp_fnn.  x_t is built from the RECORDED observation of row t (obs_idx, featurisation): the
+ * row the policy saw.  L is the lane's length as vs_rollout_vjp takes it from the done bits of rows 0 .. t_steps - 1.
+ *   abar      [t_steps][A][ld]   device: d_act as vs_rollout_vjp_fnn returned it (ld = vs_ld(h)).  Rows t >= L, lanes >= n_envs and
+ *                                anything behind row t_steps are never read into the arithmetic: they may hold anything, NaN included
+ *   d_params  [n_params]         device, out: the gradient in the order of the parameter vector vs_set_policy_fnn took (per Linear
+ *                                weight [out][in], then bias); accumulate != 0: added to what is there, one fp32 add per entry
+ * Runs on the handle's stream and writes nothing of the handle.  The sum is deterministic: no atomics, every partial sum is added in
+ * a fixed order that depends on (ld, t_steps, device) only, so two calls on the same inputs return the same bits.  A workspace for
+ * the partial sums belongs to the network on the handle: allocated at the first call, freed when the policy is replaced or removed.
+ * Refused with nothing written: everything vs_rollout_vjp_fnn refuses, with the same codes; NULL abar or d_params, n_params other
+ * than the network's parameter count (VS_ERR_ARG). */
+int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate);
 /* ... and for rollouts recorded with the handle's current RECURRENT policy (vs_set_policy_rnn: RNN tanh / relu, GRU or LSTM of one or
  * two layers) in the loop: (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0), p the packed hidden state [Hs] (h of layer 0, 1, .. then, LSTM, c
  * of layer 0, 1, ..), x_t the observation rows the policy sees (obs_idx), n_t constant.  The differentiated function is

@@ -541,8 +541,9 @@ static int drop_pop(vs_handle h) {
 }
 
 static int drop_fnn(vs_handle h) {
-    if (int rc = dfree(h, h->fnn.w)) return rc;
+    if (int rc = dfree(h, h->fnn.w, h->fnn_pg_part, h->fnn_pg_map)) return rc;  // (the workspace of vs_fnn_param_grad is the network's)
     h->fnn = Fnn{};
+    h->fnn_pg_wgs = 0;
     return VS_OK;
 }
 
@@ -632,7 +633,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 314; }
+int vs_version(void) { return 315; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1703,12 +1704,13 @@ int vs_pack_traj(vs_handle h, int n_lanes, int t_steps, const int64_t* lengths, 
     return VS_OK;
 }
 
-// What the three reverse-mode sweeps refuse alike, in one order and with the entry point's name in front; `policy` (may be NULL) names
-// what the entry point needs of the handle's policy slot, or returns NULL.  Every refusal comes before the first device call and
-// leaves the outputs untouched.
+// What the three reverse-mode sweeps and vs_fnn_param_grad refuse alike, in one order and with the entry point's name in front;
+// `policy` (may be NULL) names what the entry point needs of the handle's policy slot, or returns NULL; d_act / d_init are the two
+// pointers the entry point cannot do without, `null_what` how it words their refusal.  Every refusal comes before the first device
+// call and leaves the outputs untouched.
 static int vjp_checks(vs_handle h, const char* who, int t_steps, const float* d_act, const float* d_init,
-                      const char* (*policy)(vs_handle)) {
-    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, who, "NULL handle or output");
+                      const char* (*policy)(vs_handle), const char* null_what = "NULL handle or output") {
+    if (!h || !d_act || !d_init) return fail(h, VS_ERR_ARG, who, null_what);
     if (t_steps < 1) return fail(h, VS_ERR_ARG, who, "t_steps < 1");
     if (h->type == VS_ENV_BOB_D) return fail(h, VS_ERR_STATE, who, "the discrete-action family has no action gradient");
     if (const char* why = policy ? policy(h) : nullptr) return fail(h, VS_ERR_STATE, who, why);
@@ -1745,18 +1747,63 @@ int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const fl
     return VS_OK;
 }
 
+// what vs_rollout_vjp_fnn and vs_fnn_param_grad need of the policy slot
+static const char* fnn_sweep_policy(vs_handle h) {
+    if (!h->fnn.w) return "no feed-forward network policy on the handle (vs_set_policy_fnn)";
+    if (h->pop.w) return "not available with a policy population on the handle";
+    if (h->fnn.n_hidden > 2) return "the sweep takes networks of one or two hidden layers";
+    return nullptr;
+}
+
 int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, float* d_act, float* d_init) {
-    const auto policy = [](vs_handle h) -> const char* {
-        if (!h->fnn.w) return "no feed-forward network policy on the handle (vs_set_policy_fnn)";
-        if (h->pop.w) return "not available with a policy population on the handle";
-        if (h->fnn.n_hidden > 2) return "the sweep takes networks of one or two hidden layers";
-        return nullptr;
-    };
-    if (int rc = vjp_checks(h, "vs_rollout_vjp_fnn", t_steps, d_act, d_init, policy)) return rc;
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_fnn", t_steps, d_act, d_init, fnn_sweep_policy)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_fnn(h, v, g_act, t_steps));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+// workgroups of k_fnn_param_grad: a function of (ld, t_steps, device) only, so that the bits of a result do not depend on earlier
+// calls -- a wave per tile while there are fewer tiles than wave slots, else two workgroups per compute unit, each wave a run of tiles
+static int fnn_param_grad_wgs(const vs_env* h, int t_steps) {
+    const int64_t tiles = (int64_t)(h->d.ld / 64) * t_steps;
+    return (int)std::min<int64_t>((tiles + FNNG_WAVES - 1) / FNNG_WAVES, 2 * (int64_t)h->n_cu);
+}
+
+int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate) {
+    const char* who = "vs_fnn_param_grad";
+    if (int rc = vjp_checks(h, who, t_steps, abar, d_params, fnn_sweep_policy, "NULL handle, abar or d_params")) return rc;
+    if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, who, "n_params is not the parameter count of the network on the handle");
+    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    const Fnn& f = h->fnn;
+    const int psize = (int)h->pol_map.size(), n_wg = fnn_param_grad_wgs(h, t_steps);
+    if (psize != f.off_b[f.n_hidden] + 8 || psize > FNNG_PMAX) return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_fnn's");
+    HIPCHK(h, hipSetDevice(h->device));
+    // ---- the workspace belongs to the network on the handle: first use, or a grid larger than every one before
+    if (!h->fnn_pg_map) {
+        int* map = nullptr;
+        HIPCHK(h, hipMalloc((void**)&map, (size_t)psize * sizeof(int)));
+        hipError_t e = hipMemcpy(map, h->pol_map.data(), (size_t)psize * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
+        h->fnn_pg_map = map;
+    }
+    if (n_wg > h->fnn_pg_wgs) {
+        if (h->fnn_pg_part) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
+        if (int rc = dfree(h, h->fnn_pg_part)) return rc;
+        h->fnn_pg_wgs = 0;
+        HIPCHK(h, hipMalloc((void**)&h->fnn_pg_part, (size_t)n_wg * psize * sizeof(float)));
+        h->fnn_pg_wgs = n_wg;
+    }
+    const EnvInfo& ei = ENV_INFO[h->type];
+    const FnnRows rows{h->d.traj_rec, h->d.traj_done, record_width(h->type, 2), ei.O, ei.A, h->d.n, h->d.ld};
+    if (f.n_hidden == 1)
+        hipLaunchKernelGGL((k_fnn_param_grad<1>), dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->fnn_pg_part);
+    else
+        hipLaunchKernelGGL((k_fnn_param_grad<2>), dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->fnn_pg_part);
+    hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream,
+                       (const float*)h->fnn_pg_part, n_wg, psize, (const int*)h->fnn_pg_map, d_params, accumulate != 0 ? 1 : 0);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -17,6 +17,7 @@
 //   k_rollout_vjp_lin  vs_rollout_vjp_policy  the same sweep with the handle's linear policy in the loop (closed-loop adjoints)
 //   k_rollout_vjp_fnn  vs_rollout_vjp_fnn     ... with the handle's feed-forward network of one or two hidden layers in the loop
 //   k_rollout_vjp_rnn  vs_rollout_vjp_rnn     ... with the handle's recurrent policy in the loop (a second adjoint for its hidden state)
+//   k_fnn_param_grad / k_fnn_param_reduce  vs_fnn_param_grad   the network's parameter gradients from the records and the sweep's d_act
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -2844,6 +2845,262 @@ __global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev
     for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
 }
 
+// ------------------------------------------------------------------------ parameter gradients of a feed-forward network policy
+// vs_fnn_param_grad: what the sweep above leaves to the caller -- d Phi / d theta = sum over the rows (t < L_i, i < n) of
+//     dW_out += delta_out y_last^T   db_out += delta_out     dW_2 += delta_2 y_1^T   db_2 += delta_2     dW_1 += delta_1 x^T   db_1 += delta_1
+// with abar = d_act as the sweep wrote it (lanes-last) and the deltas of k_rollout_vjp_fnn's network waves: the same recompute, the
+// same expressions (fnn_nonlin, fnn_nonlin_grad, fnn_row_dot), plus an outer-product accumulation.  No serial chain in time: every
+// (t, env) row is independent, so the launch fills the chip.
+//   * The input row is built from the RECORDED OBSERVATION (columns 0 .. O - 1 of the record row, run-time widths), not from
+//     E::observe of the recorded state: k_rollout_fnn stores into the record the very `ob` it builds the policy's row from (no wrapper
+//     pipeline: vjp_checks refuses one), so the row is what the policy saw bit for bit, the kernel needs nothing of the family and has
+//     two instantiations instead of two per family.  obs_idx / n_vis / ident and the feat row through sincos_fast as in k_rollout_fnn.
+//   * Workgroups of FNNG_WAVES = 4 waves, lane = hidden unit.  A wave owns a contiguous run of tiles (64 lanes x one step, lane-group
+//     major, so that a lane's length L -- the first done bit, as in the sweep -- is worked out once per lane group): it loads the
+//     tile's observations and abar with lane = env, only where t < L and i < n (nothing else is ever read into the arithmetic), leaves
+//     rows and adjoints in its own LDS rows, and walks the live envs of the tile (a ballot: wave-uniform skips, no multiply by zero)
+//     with lane = unit.  A tile no lane reaches is skipped before its loads.
+//   * Per env: forward and deltas as the sweep's, then  aWo[j] += delta_out_j y_last,  aW2[k] += delta_2 y_1[k] (y_1's row comes back
+//     as broadcast ds_read_b128: 64 FMAs, one forward layer's cost),  aW1[k] += delta_1 x[k]  and the biases: lane j's accumulators
+//     are COLUMN j of the packed Wt blocks, i.e. the partial vector has the layout of Fnn::w.
+//   * Deterministic, no atomics: the four waves add their registers into one LDS vector in wave order, the workgroup stores it as row
+//     blockIdx.x of the workspace [n_wg][psize], and k_fnn_param_reduce adds the rows in a fixed order (four interleaved partial sums),
+//     maps packed slot -> torch index with the setter's own index map (padding: -1, never written) and stores or, with `accumulate`,
+//     adds with one fp32 add per entry.  The grid depends on (ld, t_steps, device) only.
+constexpr int FNNG_WAVES = 4;
+constexpr int FNNG_PMAX = (MAXO + 1) * FNN_W + FNN_W + FNN_W * FNN_W + FNN_W + MAXA * FNN_W + 8;  // the packed vector of two hidden layers
+struct FnnRows {            // the records k_fnn_param_grad reads
+    const float* rec;       // Dev::traj_rec (record mode 2)
+    const uint32_t* done;   // Dev::traj_done
+    int F, O, A;            // floats per record row, observation and action width of the family
+    int n, ld;
+};
+template <int NHID>
+__global__ __launch_bounds__(64 * FNNG_WAVES) void k_fnn_param_grad(FnnRows R, const float* abar, Fnn P, int t_steps, int psize,
+                                                                    float* part) {
+    static_assert(NHID == 1 || NHID == 2, "hidden layers");
+    __shared__ __attribute__((aligned(16))) float l_x[FNNG_WAVES][64 * FNN_XS];  // the tile's input rows: [env][input]
+    __shared__ float l_ab[FNNG_WAVES][64 * MAXA];                               // abar: [env][A]
+    __shared__ __attribute__((aligned(16))) float l_y[FNNG_WAVES][FNN_W];        // y_1 of the running env
+    __shared__ __attribute__((aligned(16))) float l_d[FNNG_WAVES][FNN_W];        // delta_2 of the running env
+    __shared__ float l_sum[NHID > 1 ? FNNG_PMAX : FNNG_PMAX - FNN_W * FNN_W - FNN_W];  // the workgroup's partial vector
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int A = R.A, in_dim = P.in_dim;
+
+    float w1[FNN_XS], wh[NHID > 1 ? FNN_W : 1], wt[NHID > 1 ? FNN_W : 1], bh[NHID], wo[MAXA], bo[MAXA];
+#pragma unroll
+    for (int k = 0; k < FNN_XS; ++k) w1[k] = k < in_dim ? P.w[P.off_w[0] + k * FNN_W + lane] : 0.f;
+    if constexpr (NHID > 1) {
+#pragma unroll
+        for (int k = 0; k < FNN_W; ++k) wh[k] = P.w[P.off_w[1] + k * FNN_W + lane];  // W_2[lane][k]
+#pragma unroll
+        for (int m = 0; m < FNN_W; ++m) wt[m] = P.w[P.off_w[1] + lane * FNN_W + m];  // W_2[m][lane]: row `lane` of Wt_2
+    }
+#pragma unroll
+    for (int l = 0; l < NHID; ++l) bh[l] = P.w[P.off_b[l] + lane];
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) {
+        wo[j] = j < A ? P.w[P.off_w[NHID] + j * FNN_W + lane] : 0.f;
+        bo[j] = j < A ? P.w[P.off_b[NHID] + j] : 0.f;
+    }
+    const int kind0 = P.hid_nonlin[0], kind1 = P.hid_nonlin[NHID > 1 ? 1 : 0], kindo = P.out_nonlin;
+    float aW1[FNN_XS], aW2[NHID > 1 ? FNN_W : 1], aWo[MAXA], ab1 = 0.f, ab2 = 0.f, abo[MAXA];
+#pragma unroll
+    for (int k = 0; k < FNN_XS; ++k) aW1[k] = 0.f;
+#pragma unroll
+    for (int k = 0; k < (NHID > 1 ? FNN_W : 1); ++k) aW2[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) aWo[j] = abo[j] = 0.f;
+
+    // ---- the wave's run of tiles: tile = lane group * t_steps + step
+    const size_t ld = (size_t)R.ld;
+    const int tiles = (R.ld / 64) * t_steps;
+    const int n_waves = (int)gridDim.x * FNNG_WAVES;
+    const int chunk = (tiles + n_waves - 1) / n_waves;
+    const int gw = (int)blockIdx.x * FNNG_WAVES + wave;
+    const long long first = (long long)gw * chunk;
+    const int tile0 = first < tiles ? (int)first : tiles;
+    const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
+    const int NQ = R.F / 4, H2 = (R.F % 4) >= 2 ? 1 : 0;
+    int g_of_L = -1, L = 0;
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform
+        const int i = g * 64 + lane;
+        if (g != g_of_L) {
+            // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (k_rollout_vjp_fnn's)
+            g_of_L = g;
+            L = 0;
+            if (i < R.n) {
+                L = t_steps;
+                for (int w = 0; w * 32 < t_steps; ++w) {
+                    uint32_t m = R.done[(size_t)w * ld + i];
+                    const int rem = t_steps - w * 32;
+                    if (rem < 32) m &= (1u << rem) - 1u;
+                    if (m) {
+                        L = w * 32 + __ffs((int)m);
+                        break;
+                    }
+                }
+            }
+        }
+        const bool live = t < L;
+        const unsigned long long mask = __ballot(live);
+        if (mask == 0ull) continue;  // no lane of the tile reaches step t: nothing is loaded
+        wave_lds_fence();            // the walk of the previous tile has read its rows
+        {
+            float xr[FNN_XS], ab[MAXA];
+#pragma unroll
+            for (int k = 0; k < FNN_XS; ++k) xr[k] = 0.f;
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) ab[j] = 0.f;
+            if (live) {
+                const float* row = R.rec + (size_t)t * R.F * ld;
+                float ob[MAXO];
+#pragma unroll
+                for (int c = 0; c < MAXO; ++c) {  // column c of the record planes (Planes<F>, F at run time)
+                    ob[c] = 0.f;
+                    if (c < R.O) {
+                        const size_t at = c < 4 * NQ ? (size_t)(c / 4) * 4 * ld + 4 * (size_t)i + (c & 3)
+                                          : (H2 && c < 4 * NQ + 2) ? (size_t)NQ * 4 * ld + 2 * (size_t)i + (c - 4 * NQ)
+                                                                   : ((size_t)NQ * 4 + H2 * 2) * ld + i;
+                        ob[c] = row[at];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < MAXA; ++j)
+                    if (j < A) ab[j] = abar[((size_t)t * A + j) * ld + i];
+                // ---- what the policy saw of obs_t, as in k_rollout_fnn
+                if (P.ident) {
+#pragma unroll
+                    for (int k = 0; k < MAXO; ++k) xr[k] = ob[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < MAXO; ++k) {
+                        float v = 0.f;
+#pragma unroll
+                        for (int j = 0; j < MAXO; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                        xr[k] = v;
+                    }
+                }
+                if (P.feat) {  // [o_0, sin o_1, cos o_1, o_2 ..]
+                    float sn, cs;
+                    sincos_fast(xr[1], &sn, &cs);
+#pragma unroll
+                    for (int k = MAXO; k >= 3; --k) xr[k] = xr[k - 1];
+                    xr[1] = sn, xr[2] = cs;
+                }
+            }
+            Planes<FNN_XS>::store(l_x[wave], 1, lane * (FNN_XS / 4), xr);
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) l_ab[wave][lane * MAXA + j] = ab[j];
+        }
+        wave_lds_fence();
+        // ---- the tile's live envs one after the other, lane = unit: every LDS read below is one address for the wave
+#pragma unroll 1
+        for (int e = 0; e < 64; ++e) {
+            if (!((mask >> e) & 1ull)) continue;  // t >= L, lane >= n: skipped, not multiplied by zero
+            float x[FNN_XS];
+            Planes<FNN_XS>::load(l_x[wave], 1, e * (FNN_XS / 4), x);
+            // ---- forward, as k_rollout_vjp_fnn
+            float z = bh[0];
+#pragma unroll
+            for (int k = 0; k < FNN_XS; ++k) z = fmaf(w1[k], x[k], z);
+            const float y1 = fnn_nonlin(kind0, z);
+            float yl = y1;
+            if constexpr (NHID > 1) {
+                wave_lds_fence();  // every lane has read the rows of the env before
+                l_y[wave][lane] = y1;
+                wave_lds_fence();
+                yl = fnn_nonlin(kind1, bh[1] + fnn_row_dot(wh, l_y[wave]));
+            }
+            // ---- delta_out = abar (.) g'(y_out), uniform over the wave;  dl = W_out^T delta_out
+            float dl = 0.f;
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) {
+                if (j >= A) continue;  // (wave-uniform)
+                const float sum = wave_sum_to_lane63(wo[j] * yl);
+                const float zo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sum), 63)) + bo[j];
+                const float dout = l_ab[wave][e * MAXA + j] * fnn_nonlin_grad(kindo, fnn_nonlin(kindo, zo));
+                dl = fmaf(wo[j], dout, dl);
+                aWo[j] = fmaf(dout, yl, aWo[j]);
+                abo[j] += dout;
+            }
+            dl *= fnn_nonlin_grad(NHID > 1 ? kind1 : kind0, yl);
+            float d1 = dl;
+            if constexpr (NHID > 1) {
+                ab2 += dl;
+#pragma unroll
+                for (int kk = 0; kk < FNN_W / 4; ++kk) {  // dW_2[lane][.] += delta_2[lane] y_1[.]
+                    const float4 v = reinterpret_cast<const float4*>(l_y[wave])[kk];
+                    aW2[4 * kk] = fmaf(dl, v.x, aW2[4 * kk]);
+                    aW2[4 * kk + 1] = fmaf(dl, v.y, aW2[4 * kk + 1]);
+                    aW2[4 * kk + 2] = fmaf(dl, v.z, aW2[4 * kk + 2]);
+                    aW2[4 * kk + 3] = fmaf(dl, v.w, aW2[4 * kk + 3]);
+                }
+                l_d[wave][lane] = dl;
+                wave_lds_fence();
+                d1 = fnn_row_dot(wt, l_d[wave]) * fnn_nonlin_grad(kind0, y1);
+            }
+            ab1 += d1;
+#pragma unroll
+            for (int k = 0; k < FNN_XS; ++k) aW1[k] = fmaf(d1, x[k], aW1[k]);
+        }
+    }
+
+    // ---- the four waves into one vector, in wave order; the workgroup's row of the workspace
+    for (int w = 0; w < FNNG_WAVES; ++w) {
+        if (wave == w) {
+            auto put = [&](int at, float v) __attribute__((always_inline)) { l_sum[at] = w == 0 ? v : l_sum[at] + v; };
+#pragma unroll
+            for (int k = 0; k < FNN_XS; ++k)
+                if (k < in_dim) put(P.off_w[0] + k * FNN_W + lane, aW1[k]);
+            put(P.off_b[0] + lane, ab1);
+            if constexpr (NHID > 1) {
+#pragma unroll
+                for (int k = 0; k < FNN_W; ++k) put(P.off_w[1] + k * FNN_W + lane, aW2[k]);
+                put(P.off_b[1] + lane, ab2);
+            }
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j)
+                if (j < A) put(P.off_w[NHID] + j * FNN_W + lane, aWo[j]);
+            if (lane < 8) {  // the output biases (uniform over the lanes) and the block's padding
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < MAXA; ++j) v = (j < A && lane == j) ? abo[j] : v;
+                put(P.off_b[NHID] + lane, v);
+            }
+        }
+        __syncthreads();
+    }
+    for (int p = (int)threadIdx.x; p < psize; p += 64 * FNNG_WAVES) part[(size_t)blockIdx.x * psize + p] = l_sum[p];
+}
+
+// d_params[map[p]] (+)= sum over the workgroups' rows of packed slot p, in a fixed order; slots of the padding (map < 0) are dropped
+// (a template only so that the translation unit that launches it is the one that holds it; NSUM: interleaved partial sums)
+template <int NSUM>
+__global__ __launch_bounds__(BLOCK) void k_fnn_param_reduce(const float* part, int n_wg, int psize, const int* map, float* d_params,
+                                                            int accumulate) {
+    const int p = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (p >= psize) return;
+    static_assert(NSUM == 4, "four interleaved partial sums");
+    const int q = map[p];
+    if (q < 0) return;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int w = 0;
+    for (; w + 4 <= n_wg; w += 4) {
+        a0 += part[(size_t)w * psize + p];
+        a1 += part[(size_t)(w + 1) * psize + p];
+        a2 += part[(size_t)(w + 2) * psize + p];
+        a3 += part[(size_t)(w + 3) * psize + p];
+    }
+    if (w < n_wg) a0 += part[(size_t)w * psize + p];
+    if (w + 1 < n_wg) a1 += part[(size_t)(w + 1) * psize + p];
+    if (w + 2 < n_wg) a2 += part[(size_t)(w + 2) * psize + p];
+    const float s = (a0 + a1) + (a2 + a3);
+    d_params[q] = accumulate ? d_params[q] + s : s;
+}
+
 // --------------------------------------------------------------------- reverse-mode sweep with a recurrent policy in the loop
 // vs_rollout_vjp_rnn: k_rollout_vjp for rollouts that k_rollout_rnn recorded -- (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0) with the
 // handle's recurrent policy (Rnn: the same packed blocks and observation view), p the packed hidden state [hs] and n_t constant.  Two
@@ -4164,6 +4421,9 @@ struct vs_env {
     float* d_pbuf = nullptr;      // DomainRandWrapperBuffer parameter sets
     float* d_ring = nullptr;      // ActDelayWrapper ring (Pipe::ring)
     vs::Fnn fnn{};                // vs_set_policy_fnn: the network vs_step_policy evaluates (fnn.w == nullptr: none)
+    float* fnn_pg_part = nullptr; // vs_fnn_param_grad: the workgroups' partial vectors [fnn_pg_wgs][packed size], allocated on first use,
+    int* fnn_pg_map = nullptr;    // ... pol_map on the device; both go with the network (drop_fnn)
+    int fnn_pg_wgs = 0;
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)

@@ -205,7 +205,10 @@ class _ClosedLoopRollout(_RecordedBatches):
     self.policy (what the caller gave), self._mean (the module whose parameters get gradients: the policy without its exploration
     noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now.
     A policy with more than the action adjoint to pull back (a hidden state) also says what it keeps of a batch's sweep (_keep)
-    and how the parameter gradients come from it (_param_grads)."""
+    and how the parameter gradients come from it (_param_grads).  A subclass whose _keep already does the parameter pass on the
+    device sets _needs_rows to False: the [N, T, .] copies of abar and of the observations are then not made."""
+
+    _needs_rows = True  # _param_grads reads abar [N, T, A] and the recorded observations [N, T, O]
 
     def _check_dims(self, obs_dim, act_dim):
         A, _, O = self._dims()
@@ -222,8 +225,9 @@ class _ClosedLoopRollout(_RecordedBatches):
         """(d_act, d_init, anything else the sweep returns) of one batch"""
         raise NotImplementedError
 
-    def _keep(self, v, T, n, more):
-        """what _param_grads needs of a batch beyond abar and the observations; `more`: the sweep's further returns"""
+    def _keep(self, v, T, n, more, da, kept):
+        """what _param_grads needs of a batch beyond abar and the observations; `more`: the sweep's further returns, da: its
+        action adjoints [T, A, ld] as returned (lanes last), kept: what the batches before this one returned here"""
         return None
 
     def _param_grads(self, seen, abar, kept):
@@ -297,8 +301,9 @@ class _ClosedLoopRollout(_RecordedBatches):
         """(gradients of the policy's parameters, d init_states)"""
         A, S, O = self._dims()
         N, T, dev = init_states.shape[0], setup[3], init_states.device
-        abar = torch.empty(N, T, A, dtype=torch.float32, device=dev)
-        seen = torch.empty(N, T, O, dtype=torch.float32, device=dev)
+        rows = self._needs_rows
+        abar = torch.empty(N, T, A, dtype=torch.float32, device=dev) if rows else None
+        seen = torch.empty(N, T, O, dtype=torch.float32, device=dev) if rows else None
         d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
         kept = []
         for b, (n0, n1) in enumerate(self._batches(N)):
@@ -308,10 +313,11 @@ class _ClosedLoopRollout(_RecordedBatches):
             try:
                 g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
                 da, di, *more = self._sweep(v, T, g[0], g[1], g[2])
-                abar[n0:n1] = lanes_first(da, n)                   # (0 behind a rollout's end: the kernel writes it so)
                 d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
-                seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
-                kept.append(self._keep(v, T, n, more))
+                if rows:
+                    abar[n0:n1] = lanes_first(da, n)               # (0 behind a rollout's end: the kernel writes it so)
+                    seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
+                kept.append(self._keep(v, T, n, more, da, kept))
             finally:
                 v.use_stream(None)
         return self._param_grads(seen, abar, kept), d_init
@@ -367,12 +373,21 @@ class DifferentiableNetRollout(_ClosedLoopRollout):
     its action ShapeErr.  Call, return values and what carries gradients are DifferentiablePolicyRollout's: obs, rew and act reach
     init_states and every parameter of the network -- backpropagation through time over the closed loop.
     Forward: set_policy_fnn from the module's current weights, reset(init_state), one recording step_policy(T).  Backward: one
-    rollout_vjp_fnn per batch for the action adjoints and d init_states, then ONE batched pass of the network over the recorded
-    [N T] observations for the parameter gradients."""
+    rollout_vjp_fnn per batch for the action adjoints and d init_states, and the parameter gradients by param_pass:
+      "kernel"  one fnn_param_grad per batch (vs_fnn_param_grad), straight on the sweep's action adjoints and the handle's records:
+                the first batch writes the flat gradient, later batches add to it; no [N, T, .] copy of the adjoints or of the
+                observations is made.  Deterministic: backward() twice returns the same bits;
+      "torch"   ONE batched torch pass of the network over the recorded [N T] observations.
+    A network with a parameter that is not float32 takes the torch pass whatever is asked (self.param_pass says which one runs);
+    any other value raises ValueErr.  The torch pass hands the network the recorded observations in its parameters' dtype: nothing
+    changes for a float32 network, and a float64 FNN or FNNPolicy, whose backward pass used to fail on the float32 rows
+    (a dtype mismatch in the first Linear), now gets float64 gradients."""
 
-    def __init__(self, env, policy, batch_lanes: int = 65536):
+    def __init__(self, env, policy, batch_lanes: int = 65536, param_pass: str = "kernel"):
         from .policies import FNN, FNNPolicy, NormalActNoiseExplStrat, fnn_kernel_spec
 
+        if param_pass not in ("kernel", "torch"):
+            raise ValueErr(msg=f"param_pass is 'kernel' or 'torch', got {param_pass!r}")
         inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
         if not isinstance(inner, (FNN, FNNPolicy)):
             raise TypeErr(msg="DifferentiableNetRollout takes an FNN or FNNPolicy, optionally inside a NormalActNoiseExplStrat, got "
@@ -388,6 +403,25 @@ class DifferentiableNetRollout(_ClosedLoopRollout):
         self._check_dims(net.hidden_layers[0].in_features - (1 if spec["feat"] else 0), net.output_layer.out_features)
         self.policy, self._mean = policy, inner
         self._arch = {k: spec[k] for k in ("hidden_sizes", "hidden_nonlin", "output_nonlin", "feat")}
+        fp32 = all(p.dtype == torch.float32 for p in inner.parameters())
+        self.param_pass = param_pass if fp32 else "torch"
+        self._needs_rows = self.param_pass == "torch"
+
+    def _keep(self, v, T, n, more, da, kept):
+        """the running flat gradient: the first batch writes it, every later batch adds to what the batch before returned"""
+        if self.param_pass != "kernel":
+            return None
+        flat = kept[-1] if kept else None
+        return v.fnn_param_grad(T, da, out=flat, accumulate=flat is not None)
+
+    def _param_grads(self, seen, abar, kept):
+        if self.param_pass != "kernel":  # (the rows in the parameters' dtype: a no-op for a float32 network, whose pass is unchanged)
+            return super()._param_grads(seen.to(next(self._mean.parameters()).dtype), abar, kept)
+        flat, grads, at = kept[-1], [], 0
+        for p in self._mean.parameters():  # parameters_to_vector's order
+            grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
+            at += p.numel()
+        return tuple(grads)
 
     def _noise_std(self):
         from .policies import fnn_kernel_spec
@@ -447,7 +481,7 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
     def _sweep(self, v, T, g_rew, g_obs, g_act):
         return v.rollout_vjp_rnn(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
 
-    def _keep(self, v, T, n, more):
+    def _keep(self, v, T, n, more, da, kept):
         """(cotangents of p_{t+1} [n, T, Hs], recorded p_t [n, T, Hs])"""
         return lanes_first(more[0], n), lanes_first(v.hidden_record_tensor()[:T], n)
 

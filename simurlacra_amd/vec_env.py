@@ -601,6 +601,7 @@ class VecSimEnv:
         featurisation [o_0, sin o_1, cos o_1, o_2 ..]; obs_idx: the observation rows the policy sees (ObsPartialWrapper);
         noise_std: exploration noise per action dimension.  params=None removes the network."""
         self._rnn_hs = 0  # (a network replaces a recurrent policy)
+        self._fnn_n_params = 0
         if params is None:
             self._check(self._lib.vs_set_policy_fnn(self._h, None, None, 0), "vs_set_policy_fnn")
             return
@@ -620,6 +621,7 @@ class VecSimEnv:
         flat = self._flat_params(params)
         self._check(self._lib.vs_set_policy_fnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_fnn")
+        self._fnn_n_params = int(flat.size)  # (what fnn_param_grad returns)
 
     _RNN_CELLS = {"tanh": L.VS_RNN_TANH, "relu": L.VS_RNN_RELU, "gru": L.VS_RNN_GRU, "lstm": L.VS_RNN_LSTM}
 
@@ -900,6 +902,37 @@ class VecSimEnv:
         self._check(self._lib.vs_rollout_vjp_fnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
                     "vs_rollout_vjp_fnn")
         return d_act, d_init
+
+    def fnn_param_grad(self, t_steps, abar, out=None, accumulate=False):
+        """The parameter gradient that goes with rollout_vjp_fnn, in one device pass over the same records (vs_fnn_param_grad):
+        sum over the rows t < L of the lanes < n_envs of (d net / d theta)(x_t)^T abar[t], x_t the recorded observation as the
+        network saw it.  abar [t_steps, A, ld] is rollout_vjp_fnn's d_act as returned (lanes last); what it holds behind a lane's
+        end and at lanes >= n_envs is never read.  Returns the flat float32 gradient in parameters_to_vector's order on the
+        handle's device: a new tensor, or `out` [n_params], to which accumulate=True adds instead of overwriting.  Deterministic:
+        two calls on the same inputs return the same bits."""
+        import torch
+
+        T, A = int(t_steps), self.dims["A"]
+        n_params = getattr(self, "_fnn_n_params", 0)
+        if not n_params:
+            raise ValueErr(msg="no feed-forward network set (set_policy_fnn)")
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        if not hasattr(abar, "data_ptr") or not abar.is_cuda or abar.dtype != torch.float32 or not abar.is_contiguous():
+            raise TypeErr(msg="abar must be a contiguous float32 tensor on the GPU")
+        if tuple(abar.shape) != (T, A, self.ld):
+            raise ShapeErr(msg=f"abar must be {(T, A, self.ld)}, got {tuple(abar.shape)}")
+        if out is None:
+            if accumulate:
+                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
+            out = torch.empty(n_params, dtype=torch.float32, device=abar.device)
+        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
+        elif tuple(out.shape) != (n_params,):
+            raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
+        self._check(self._lib.vs_fnn_param_grad(self._h, T, C.c_void_p(abar.data_ptr()), C.c_void_p(out.data_ptr()), n_params,
+                                                int(bool(accumulate))), "vs_fnn_param_grad")
+        return out
 
     def rollout_vjp_rnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None, g_hid_last=None):
         """rollout_vjp_policy for records made with the recurrent policy of set_policy_rnn that is still on the handle, with the
