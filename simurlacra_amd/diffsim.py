@@ -87,11 +87,8 @@ class _RecordedBatches:
         v = slot[0]
         if slot[1] == token:
             return v
-        v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-        try:
+        with v.on_current_stream():
             launch(v)
-        finally:
-            v.use_stream(None)
         slot[1] = token
         return v
 
@@ -150,15 +147,12 @@ class DifferentiableRollout(_RecordedBatches):
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, (call, b), actions[n0:n1].contiguous(), init_states[n0:n1], params[n0:n1])
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
+            with v.on_current_stream():
                 tt = v.traj_tensors(T, n)
                 lengths[n0:n1] = v.rollout_lengths(n, T)[0]
                 obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
                 obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
                 rew[n0:n1] = tt["rew"].t()
-            finally:
-                v.use_stream(None)
         steps = torch.arange(T + 1, device=actions.device)
         obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
         rew = rew * (steps[None, :T] < lengths[:, None]).to(rew.dtype)
@@ -172,15 +166,12 @@ class DifferentiableRollout(_RecordedBatches):
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, (call, b), actions[n0:n1].contiguous(), init_states[n0:n1], params[n0:n1])
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
+            with v.on_current_stream():
                 g_rew = None if grad_rew is None else lanes_last(grad_rew[n0:n1].to(torch.float32), v.ld)
                 g_obs = None if grad_obs is None else lanes_last(grad_obs[n0:n1].to(torch.float32), v.ld)
                 da, di = v.rollout_vjp(T, g_rew=g_rew, g_obs=g_obs)
                 d_act[n0:n1] = lanes_first(da, n)
                 d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
-            finally:
-                v.use_stream(None)
         return d_act, d_init
 
 
@@ -282,16 +273,13 @@ class _ClosedLoopRollout(_RecordedBatches):
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, setup, n0, n1, init_states, weights)
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
+            with v.on_current_stream():
                 tt = v.traj_tensors(T, n)
                 lengths[n0:n1] = v.rollout_lengths(n, T)[0]
                 obs[n0:n1, :T] = tt["obs"].transpose(0, 1)
                 obs[n0:n1, T] = v.tensor(L.VS_OBS)[:, :n].t()       # (a lane that ended early is frozen at its last state)
                 rew[n0:n1] = tt["rew"].t()
                 act[n0:n1] = tt["act"].transpose(0, 1)
-            finally:
-                v.use_stream(None)
         steps = torch.arange(T + 1, device=dev)
         inside = (steps[None, :T] < lengths[:, None]).to(torch.float32)
         obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
@@ -309,8 +297,7 @@ class _ClosedLoopRollout(_RecordedBatches):
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, setup, n0, n1, init_states, weights)
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
+            with v.on_current_stream():
                 g = [None if x is None else lanes_last(x[n0:n1].to(torch.float32), v.ld) for x in (grad_rew, grad_obs, grad_act)]
                 da, di, *more = self._sweep(v, T, g[0], g[1], g[2])
                 d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
@@ -318,8 +305,6 @@ class _ClosedLoopRollout(_RecordedBatches):
                     abar[n0:n1] = lanes_first(da, n)               # (0 behind a rollout's end: the kernel writes it so)
                     seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
                 kept.append(self._keep(v, T, n, more, da, kept))
-            finally:
-                v.use_stream(None)
         return self._param_grads(seen, abar, kept), d_init
 
 

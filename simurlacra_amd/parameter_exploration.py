@@ -203,45 +203,10 @@ class ParameterExploringSampler:
             return False
         return any(spec is not None for spec in fused_policy_specs(self.policy, fuse_wrappers(self.env), inner_env(self.env).name))
 
-    def sample(self, param_sets, init_states: Optional[List[np.ndarray]] = None) -> ParameterSamplingResult:
-        """Every parameter vector (rows of param_sets, [P, n_params]) on the same num_rollouts_per_param rollouts (eval=True)"""
-        params = torch.as_tensor(param_sets).detach()
-        if params.dim() == 1:
-            params = params.unsqueeze(0)
-        if params.dim() != 2 or params.shape[0] < 1:
-            raise ValueErr(msg=f"param_sets must be [num_sets, num_params], got shape {tuple(params.shape)}")
-        params = params.to(torch.float32)
-        dps = draw_domain_params(self._dr_wrapper, self.num_domains)
-        inits = draw_init_states(inner_env(self.env).init_space, self.num_init_states_per_domain, init_states)
-        work = param_work_list(dps, inits)
-        self._sampler._sample_count += 1  # (one Philox key per sample() call, as ParallelRolloutSampler.sample)
-        R = len(work)
-        stride, batches = population_lane_layout(params.shape[0], R, self._batch_lanes)
-        rollouts = self._sample_fused(params, work, stride, batches) if self._fused() else self._sample_loop(params, work, stride)
-        return ParameterSamplingResult([ParameterSample(params=params[s].clone(), rollouts=rollouts[s])
-                                        for s in range(params.shape[0])])
-
-    def _sample_fused(self, params, work, stride, batches):
-        """one population batch per group of whole sets; rollout r of set s is lane lane_of(s, r, stride) of the call"""
-        R = len(work)
-        out = []
-        for s0, nb in batches:
-            lane_set = population_lane_set(nb, stride)
-            work_b = [_PAD] * (nb * stride)
-            for k in range(nb):
-                work_b[k * stride:k * stride + R] = work
-            real = population_real_lanes(nb, R, stride)
-            ros = self._sampler._run_batch(work_b, lane_of(s0, 0, stride), True,
-                                           population=dict(params=params[s0:s0 + nb], lane_set=lane_set, real=real))
-            out += [ros[k * R:(k + 1) * R] for k in range(nb)]
-        return out
-
-    def sample_returns(self, param_sets, init_states: Optional[List[np.ndarray]] = None, gamma: float = 1.0) -> PopulationReturns:
-        """sample() for the algorithms that consume the returns per parameter set only (HC, PEPG, NES, CEM, REPS): the same draws,
-        work list, lanes, batches and Philox keys, but every batch stays on the device as a PackedRollouts and its discounted
-        returns come from vs_returns_scan -- no StepSequence is built and nothing is copied to the host.  Needs a policy the fused
-        kernel evaluates (ValueErr otherwise)."""
-        # (sample()'s own preamble, statement for statement: sample() itself stays as it is)
+    def _begin_call(self, param_sets, init_states):
+        """what sample() and sample_returns() share: (params [P, n_params] float32, the work list of ONE set, stride, batches --
+        population_lane_layout's) after the call's draws of domain parameters and init states; counts the call (one Philox key
+        per call, as ParallelRolloutSampler.sample)"""
         params = torch.as_tensor(param_sets).detach()
         if params.dim() == 1:
             params = params.unsqueeze(0)
@@ -252,17 +217,42 @@ class ParameterExploringSampler:
         inits = draw_init_states(inner_env(self.env).init_space, self.num_init_states_per_domain, init_states)
         work = param_work_list(dps, inits)
         self._sampler._sample_count += 1
+        return (params, work) + population_lane_layout(params.shape[0], len(work), self._batch_lanes)
+
+    def _population_batches(self, params, work, stride, batches, packed_out):
+        """one population batch per group of whole sets; rollout r of set s is lane lane_of(s, r, stride) of the call.  Yields
+        (number of sets, real lanes, what _run_batch returned) of every batch"""
         R = len(work)
-        stride, batches = population_lane_layout(params.shape[0], R, self._batch_lanes)
-        rets, lens, packed = [], [], []
         for s0, nb in batches:
             work_b = [_PAD] * (nb * stride)
             for k in range(nb):
                 work_b[k * stride:k * stride + R] = work
             real = population_real_lanes(nb, R, stride)
-            p = self._sampler._run_batch(work_b, lane_of(s0, 0, stride), True, packed_out=True,
-                                         population=dict(params=params[s0:s0 + nb], lane_set=population_lane_set(nb, stride),
-                                                         real=real))
+            yield nb, real, self._sampler._run_batch(work_b, lane_of(s0, 0, stride), True, packed_out=packed_out,
+                                                     population=dict(params=params[s0:s0 + nb],
+                                                                     lane_set=population_lane_set(nb, stride), real=real))
+
+    def sample(self, param_sets, init_states: Optional[List[np.ndarray]] = None) -> ParameterSamplingResult:
+        """Every parameter vector (rows of param_sets, [P, n_params]) on the same num_rollouts_per_param rollouts (eval=True)"""
+        params, work, stride, batches = self._begin_call(param_sets, init_states)
+        if self._fused():
+            R = len(work)
+            rollouts = [ros[k * R:(k + 1) * R] for nb, _, ros in self._population_batches(params, work, stride, batches, False)
+                        for k in range(nb)]
+        else:
+            rollouts = self._sample_loop(params, work, stride)
+        return ParameterSamplingResult([ParameterSample(params=params[s].clone(), rollouts=rollouts[s])
+                                        for s in range(params.shape[0])])
+
+    def sample_returns(self, param_sets, init_states: Optional[List[np.ndarray]] = None, gamma: float = 1.0) -> PopulationReturns:
+        """sample() for the algorithms that consume the returns per parameter set only (HC, PEPG, NES, CEM, REPS): the same draws,
+        work list, lanes, batches and Philox keys, but every batch stays on the device as a PackedRollouts and its discounted
+        returns come from vs_returns_scan -- no StepSequence is built and nothing is copied to the host.  Needs a policy the fused
+        kernel evaluates (ValueErr otherwise)."""
+        params, work, stride, batches = self._begin_call(param_sets, init_states)
+        R = len(work)
+        rets, lens, packed = [], [], []
+        for nb, real, p in self._population_batches(params, work, stride, batches, True):
             real_t = torch.as_tensor(real, dtype=torch.int64, device=p.lengths.device)  # the padding lanes drop out by index
             rets.append(p.discounted_returns(gamma).index_select(0, real_t).view(nb, R))
             lens.append(p.lengths.index_select(0, real_t).view(nb, R))

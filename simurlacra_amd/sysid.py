@@ -70,13 +70,9 @@ def check_playback_env(env, who: str):
 
 def vec_env_like(base, n: int, act_norm: bool):
     """a handle of n lanes built with the constructor arguments of the env `base`, auto-reset off"""
-    from .vec_env import VecSimEnv
+    from .vec_env import vec_env_of
 
-    ctor = dict(base._ctor)
-    for k in ("num_envs", "load_experimental_tholds", "mass"):
-        ctor.pop(k, None)
-    dev = ctor.pop("device", 0)
-    v = VecSimEnv(base.name, n, ctor.pop("dt"), ctor.pop("max_steps"), task_args=ctor.pop("task_args") or None, device=dev, **ctor)
+    v = vec_env_of(base, n)
     v.set_act_norm(act_norm)
     v.set_auto_reset(False)
     return v
@@ -236,31 +232,30 @@ class TrajectoryMatchSampler:
             nc = p1 - p0
             n = nc * R
             v = self._vec_for(n)
-            v.use_stream(torch.cuda.current_stream(v.device).cuda_stream)
-            try:
-                if sens or getattr(v, "_sens_n", 0):
-                    v.set_rollout_sens(sens)                         # (evaluate(): the plain kernel, no extra call)
-                v.set_params(np.repeat(mat[p0:p1], R, axis=0))      # lane p * R + r: candidate p
-                v.reset(init_state=np.tile(self._init, (nc, 1)))     # ... from segment r's recorded state (zeroes the sums)
-                done_t = v.tensor(L.VS_DONE)[0, :n]
-                t = 0
-                while t < t_max:
-                    k = min(self._chunk, t_max - t)
-                    v.step_policy(k, record=False)
-                    t += k
-                    if t < t_max and bool(done_t.bool().all()):  # one scalar sync per launch
-                        break
-                lens = torch.as_tensor(np.tile(self._len, nc).astype(np.int64), device=done_t.device)
-                losses.append(v.rollout_loss().clone().reshape(nc, R))
-                steps.append(torch.minimum(v.tensor(L.VS_STEPCOUNT)[0, :n].to(torch.int64), lens).reshape(nc, R))
-                if sens:
-                    grads.append(v.rollout_grad().clone().reshape(nc, R, len(sens)))
-                    if gauss_newton:
-                        gns.append(v.rollout_gn().reshape(nc, R, len(sens), len(sens)))
-            finally:
-                if sens:
-                    v.set_rollout_sens(None)
-                v.use_stream(None)
+            with v.on_current_stream():
+                try:
+                    if sens or getattr(v, "_sens_n", 0):
+                        v.set_rollout_sens(sens)                         # (evaluate(): the plain kernel, no extra call)
+                    v.set_params(np.repeat(mat[p0:p1], R, axis=0))      # lane p * R + r: candidate p
+                    v.reset(init_state=np.tile(self._init, (nc, 1)))     # ... from segment r's recorded state (zeroes the sums)
+                    done_t = v.tensor(L.VS_DONE)[0, :n]
+                    t = 0
+                    while t < t_max:
+                        k = min(self._chunk, t_max - t)
+                        v.step_policy(k, record=False)
+                        t += k
+                        if t < t_max and bool(done_t.bool().all()):  # one scalar sync per launch
+                            break
+                    lens = torch.as_tensor(np.tile(self._len, nc).astype(np.int64), device=done_t.device)
+                    losses.append(v.rollout_loss().clone().reshape(nc, R))
+                    steps.append(torch.minimum(v.tensor(L.VS_STEPCOUNT)[0, :n].to(torch.int64), lens).reshape(nc, R))
+                    if sens:
+                        grads.append(v.rollout_grad().clone().reshape(nc, R, len(sens)))
+                        if gauss_newton:
+                            gns.append(v.rollout_gn().reshape(nc, R, len(sens), len(sens)))
+                finally:
+                    if sens:
+                        v.set_rollout_sens(None)
         return losses, steps, grads, gns
 
     def evaluate(self, domain_params, names: Optional[Sequence[str]] = None) -> TrajectoryMatchResult:

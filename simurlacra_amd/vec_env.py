@@ -6,6 +6,7 @@ environment instances of one family, one per wavefront lane on an MI355X.  Contr
 initial states, masks) are NumPy arrays; hot-path data (actions in, observations / rewards / done flags out) are
 device buffers exposed zero-copy as torch tensors.  There is no CPU implementation behind this class.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -973,6 +974,18 @@ class VecSimEnv:
             arg = C.c_void_p(int(stream_ptr) or HIP_STREAM_LEGACY)
         self._check(self._lib.vs_set_stream(self._h, arg), "vs_set_stream")
 
+    @contextlib.contextmanager
+    def on_current_stream(self):
+        """`with v.on_current_stream():` -- the handle launches on torch's current stream inside the block, so that its kernels
+        and the torch ops that read its buffers are ordered, and on its own stream again afterwards (also when the block raises)"""
+        import torch
+
+        self.use_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        try:
+            yield self
+        finally:
+            self.use_stream(None)
+
     # ------------------------------------------------------------------------------------------------ data access
     def _rows(self, which):
         if which in (L.VS_ROLLOUT_GRAD, L.VS_ROLLOUT_GN, L.VS_ROLLOUT_SENS):  # sized by set_rollout_sens
@@ -1088,6 +1101,22 @@ class VecSimEnv:
             rc = self._lib.vs_time_step_kernel(self._h, 1, None, 0, 0, int(k_steps), int(bool(record)), int(iters), C.byref(ms))
         self._check(rc, "vs_time_step_kernel")
         return float(ms.value)
+
+
+def ctor_args_of(env_ctor):
+    """(dt, max_steps, keyword arguments) of VecSimEnv from the recorded constructor arguments (`_ctor`) of a pysim env object:
+    what only the env object takes (num_envs, load_experimental_tholds, mass) is left out"""
+    ctor = dict(env_ctor)
+    for k in ("num_envs", "load_experimental_tholds", "mass"):
+        ctor.pop(k, None)
+    dev = ctor.pop("device", 0)
+    return ctor.pop("dt"), ctor.pop("max_steps"), dict(task_args=ctor.pop("task_args") or None, device=dev, **ctor)
+
+
+def vec_env_of(base, n):
+    """a handle of n lanes built with the constructor arguments of the env object `base`"""
+    dt, max_steps, kwargs = ctor_args_of(base._ctor)
+    return VecSimEnv(base.name, n, dt, max_steps, **kwargs)
 
 
 class MixedVecSimEnv:

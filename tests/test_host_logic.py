@@ -496,3 +496,53 @@ def test_packed_rollouts_indexing():
     rows[p.step_rows(), 3] = torch.arange(total, dtype=torch.float32)   # rewards 0 .. 7 on the step rows, 0 on the final entries
     assert p.undiscounted_returns().tolist() == [3.0, 3.0, 22.0]
     assert p.actions[p.step_rows()].shape == (total, 1)  # the dense, reference-style concatenation
+
+
+# ---------------------------------------------------------------------------------------------------- sampler launch loop
+@pytest.mark.parametrize("T_cap, kw, done_from, launches, done_calls, steps", [
+    (1, {}, None, [(0, 1)], 1, 1),
+    (128, {}, None, [(0, 128)], 1, 128),
+    (129, {}, None, [(0, 128), (128, 1)], 2, 129),
+    (640, {}, 2, [(0, 128), (128, 128)], 2, 256),                                        # done from its 2nd call: stops there
+    (640, dict(check_every=4, check_after_last=False), 1, [(128 * i, 128) for i in range(4)], 1, 512),
+    (512, dict(check_every=4, check_after_last=False), 1, [(128 * i, 128) for i in range(4)], 0, 512),  # none after the last
+])
+def test_fused_launches_call_log(T_cap, kw, done_from, launches, done_calls, steps):
+    """the one launch loop of the sampler's fused paths: trajectory offset, launch length and done() checks of the policy
+    cadence (every launch, the last one too) and of the DummyPolicy cadence (every fourth launch, not after the last)"""
+    from simurlacra_amd.sampling import _fused_launches
+
+    log = []
+
+    class Handle:
+        def set_traj_offset(self, t):
+            log.append(("offset", t))
+
+    def done():
+        log.append(("done",))
+        return done_from is not None and sum(e == ("done",) for e in log) >= done_from
+
+    assert _fused_launches(Handle(), T_cap, 128, lambda k: log.append(("launch", k)), done, **kw) == steps
+    assert log[-1] == ("offset", 0)
+    offsets = [e[1] for e in log[:-1] if e[0] == "offset"]
+    assert list(zip(offsets, [e[1] for e in log if e[0] == "launch"])) == launches
+    assert log.count(("done",)) == done_calls
+    for i, e in enumerate(log[:-1]):  # every launch right behind its own offset
+        if e[0] == "launch":
+            assert log[i - 1][0] == "offset"
+
+
+def test_dummy_policy_chunk_rule():
+    from simurlacra_amd.sampling import _dummy_chunk
+
+    assert [_dummy_chunk(128, T) for T in (600, 4000, 10000)] == [128, 500, 1024]
+
+
+def test_ctor_args_of_strips_what_only_the_env_object_takes():
+    from simurlacra_amd.vec_env import ctor_args_of
+
+    ctor = dict(dt=0.01, max_steps=500, task_args=dict(), device=1, long=True, wild_init="False",
+                num_envs=7, load_experimental_tholds=True, mass=0.3)
+    assert ctor_args_of(ctor) == (0.01, 500, dict(task_args=None, device=1, long=True, wild_init="False"))
+    assert len(ctor) == 9  # the env's own record is left alone
+    assert ctor_args_of(dict(dt=0.02, max_steps=300, task_args=dict(Q=[1, 2])))[2] == dict(task_args=dict(Q=[1, 2]), device=0)
