@@ -462,6 +462,28 @@ int vs_set_rollout_sens(vs_handle h, const int32_t* param_idx, int n_params);
  * discrete-action family (VS_ERR_STATE). */
 int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
                    float* d_init);
+/* The same sweep with the gradient with respect to DOMAIN PARAMETERS next to it: for the n_params chosen parameters theta_j =
+ * vs_param_name(type, param_idx[j]) of every lane's own VS_PARAMS,
+ *   d_params  [n_params][ld]   out: d Phi / d theta_j, Phi as for vs_rollout_vjp
+ * -- what system identification by gradient needs of the simulator for ANY loss written over the observations of a recorded rollout
+ * (vs_set_rollout_sens has the forward form, for the weighted squared discrepancy against a target table only).  Arguments, layout
+ * (ld = vs_ld(h)), stream, L, the NULL-is-zero rule of the cotangents and "writes nothing of the handle" are vs_rollout_vjp's, and
+ * d_act and d_init are vs_rollout_vjp's bit for bit.  n_params is 1 .. VS_SENS_MAX_PARAMS; the kernel carries NP = 1, 2 or 4
+ * tangents, n_params = 3 runs 4 with an unseeded column.  As in vs_set_rollout_sens the tangents run through _calc_constants on
+ * the lane's raw parameters (the constants' values are the lane's stored ones) and the dynamics.  dp[j] = 0; then for t = L - 1 .. 0,
+ * BEFORE lambda is updated (it holds the adjoint of (s_{t+1}, h_{t+1})), the dynamics and observe are differentiated at the recorded
+ * (s_t, h_t) and the applied action (ActNormWrapper's map and the clip in float: constants) and, for every j, in fp32 in this order
+ *     for k < S: dp[j] = fmaf(lambda[k], d s'_k / d theta_j, dp[j]);  for k < H: dp[j] = fmaf(lambda[S + k], d h'_k / d theta_j, dp[j]);
+ *     for q < O: dp[j] = fmaf(g_obs[t + 1][q], d obs'_q / d theta_j, dp[j])
+ * then the step of vs_rollout_vjp.  d_params[j] = dp[j]; lanes >= n_envs get 0.  Cotangent rows behind a lane's end are not read.
+ * Conventions, as for vs_set_rollout_sens: the reward, the bounds of the action and state spaces, the clip, the initial state and the
+ * initial hidden state are constants with respect to the parameters -- g_rew and g_obs[0] add nothing to d_params --, and kinks
+ * (clip, dead zone, Coulomb friction's sign) follow the branch taken.  More than VS_SENS_MAX_PARAMS parameters are further calls
+ * over the same records.
+ * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; NULL d_params or param_idx, n_params outside
+ * 1 .. VS_SENS_MAX_PARAMS, an index outside the family's parameter list or repeated (VS_ERR_ARG). */
+int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last,
+                          const int32_t* param_idx, int n_params, float* d_act, float* d_init, float* d_params);
 /* The same sweep for CLOSED-LOOP rollouts: rows 0 .. t_steps - 1 were recorded by vs_step_policy with the handle's current linear
  * policy (vs_set_policy_linear) in the loop, a_t = W phi(obs_t) + n_t, where n_t -- the exploration noise, if any -- is a constant the
  * recorded raw action already contains.  The caller answers for the policy on the handle being the one that made the records.

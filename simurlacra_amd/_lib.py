@@ -105,6 +105,7 @@ _SIGNATURES = {
     "vs_set_rollout_target": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "vs_set_rollout_sens": (C.c_int, [_P, _P, C.c_int]),
     "vs_rollout_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "vs_rollout_vjp_params": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "vs_rollout_vjp_policy": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vs_rollout_vjp_fnn": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vs_fnn_param_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int]),

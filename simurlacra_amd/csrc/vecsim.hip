@@ -633,7 +633,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 315; }
+int vs_version(void) { return 316; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1728,6 +1728,32 @@ int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp(h, v, t_steps));
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last,
+                          const int32_t* param_idx, int n_params, float* d_act, float* d_init, float* d_params) {
+    const char* who = "vs_rollout_vjp_params";
+    if (int rc = vjp_checks(h, who, t_steps, d_act, d_init, nullptr)) return rc;
+    // the index checks of vs_set_rollout_sens
+    if (!d_params) return fail(h, VS_ERR_ARG, who, "NULL d_params");
+    if (n_params < 1 || n_params > VS_SENS_MAX_PARAMS) return fail(h, VS_ERR_ARG, who, "n_params outside 1 .. VS_SENS_MAX_PARAMS");
+    if (!param_idx) return fail(h, VS_ERR_ARG, who, "NULL param_idx");
+    const EnvInfo& ei = ENV_INFO[h->type];
+    VjpDp q{};
+    q.d_params = d_params;
+    q.n = n_params;
+    for (int j = 0; j < SENS_MAXP; ++j) q.idx[j] = -1;
+    for (int j = 0; j < n_params; ++j) {
+        if (param_idx[j] < 0 || param_idx[j] >= ei.P) return fail(h, VS_ERR_ARG, who, "a parameter index outside the family's list");
+        for (int l = 0; l < j; ++l)
+            if (param_idx[l] == param_idx[j]) return fail(h, VS_ERR_ARG, who, "a parameter index is repeated");
+        q.idx[j] = param_idx[j];
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
+    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_dp(h, v, q, t_steps));
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -14,6 +14,7 @@
 //   k_step_jac      vs_step_jac       step + Jacobians by forward-mode dual numbers
 //   k_rollout_play_sens  vs_step_policy   playback rollout + discrepancy with its gradient and Gauss-Newton matrix w.r.t. domain parameters
 //   k_rollout_vjp   vs_rollout_vjp    reverse-mode sweep over a recorded rollout: gradients w.r.t. its actions and initial state
+//   k_rollout_vjp_dp  vs_rollout_vjp_params  the same sweep with the gradient w.r.t. chosen domain parameters next to it
 //   k_rollout_vjp_lin  vs_rollout_vjp_policy  the same sweep with the handle's linear policy in the loop (closed-loop adjoints)
 //   k_rollout_vjp_fnn  vs_rollout_vjp_fnn     ... with the handle's feed-forward network of one or two hidden layers in the loop
 //   k_rollout_vjp_rnn  vs_rollout_vjp_rnn     ... with the handle's recurrent policy in the loop (a second adjoint for its hidden state)
@@ -2413,6 +2414,139 @@ __global__ __launch_bounds__(64) void k_rollout_vjp(Task T, Dev d, Vjp V, int t_
     for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
 }
 
+// --------------------------------------------------------------- reverse-mode sweep with domain-parameter gradients
+// vs_rollout_vjp_params: k_rollout_vjp that also contracts the adjoint with d(step)/d(theta) for NP chosen domain parameters theta,
+// so that any loss over the observations and rewards of a recorded rollout reaches the lane's parameters.  Same shape: one env per
+// lane, one wave per workgroup, no LDS, no barrier, nothing of the handle written; L as in k_rollout_vjp.
+//   * Prologue: k_rollout_play_sens's dual constants -- the lane's raw parameters as Dual<NP>, tangent j seeded 1 on parameter
+//     idx[j] (-1: an unseeded column), E::calc_consts<Dual<NP>>, every constant's VALUE replaced by the lane's stored float constant;
+//     dp[NP] = 0.
+//   * Per step t = L - 1 .. 0, with lambda still the adjoint of (s_{t+1}, h_{t+1}):
+//     (a) parameter pass: E::dynamics<Dual<NP>, Dual<NP>> and E::observe<Dual<NP>> on the recorded (s_t, h_t) with zero tangents and
+//         the applied action as float with zero tangent (k_rollout_play_sens's statements: ActNorm map, limit_act), then for each j
+//             for k < S: dp[j] = fmaf(lambda[k], s'[k].d[j], dp[j]);   for k < H: dp[j] = fmaf(lambda[S + k], h'[k].d[j], dp[j]);
+//             for q < O: dp[j] = fmaf(g_obs[t + 1][q], obs'[q].d[j], dp[j])
+//     (b) state pass: vjp_step<E>, k_rollout_vjp's call -- d_act and d_init are the same bits.
+//     One after the other the two passes share registers: the peak is the larger of them plus the K * NP constant tangents.
+//   * The reward, the bounds of the spaces, limit_act, the initial state and the initial hidden state are constants with respect to
+//     the parameters (vecsim_envs.h), so g_rew adds nothing to dp and g_obs[0] neither.
+//   * Epilogue: dp[j] for j < n (n = 3 runs NP = 4 with an unseeded column); lanes >= n_envs have L = 0 and store 0.
+// Every loop over tangents, rows and constants is fully unrolled (see k_rollout_play_sens).
+struct VjpDp {
+    float* d_params;     // [n][ld]
+    int n;               // parameters asked for: 1 .. SENS_MAXP
+    int idx[SENS_MAXP];  // parameter index of tangent j, -1 for j >= n
+};
+
+template <class E, int NP>
+__global__ __launch_bounds__(64) void k_rollout_vjp_dp(Task T, Dev d, Vjp V, VjpDp Q, int t_steps) {
+    using D = Dual<NP>;
+    constexpr int NS = E::S + E::H, NI = NS + E::A;
+    constexpr int HN = E::H > 0 ? E::H : 1;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const size_t ld = d.ld;
+    const bool valid = i < d.n;
+    float c[E::K];
+    load_consts<E, false>(d, i, c, 0, E::KS);
+    // ---- the dual constants (k_rollout_play_sens's)
+    D cD[E::K];
+    {
+        D pD[E::P];
+#pragma unroll
+        for (int k = 0; k < E::P; ++k) {
+            pD[k].v = d.params[(size_t)k * ld + i];
+#pragma unroll
+            for (int j = 0; j < NP; ++j) pD[k].d[j] = Q.idx[j] == k ? 1.f : 0.f;
+        }
+        E::template calc_consts<D>(T, pD, cD);
+#pragma unroll
+        for (int k = 0; k < E::KS; ++k) cD[k].v = c[k];
+    }
+    float alo[E::A], ahi[E::A];
+    E::act_bounds(c, alo, ahi);
+    // ---- the lane's length (k_rollout_vjp's)
+    int L = 0;
+    if (valid) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = d.traj_done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    float lam[NS], x[NI], out[NI], gob[E::O], dp[NP];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) lam[k] = (valid && V.g_last) ? V.g_last[(size_t)k * ld + i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) dp[j] = 0.f;
+
+    for (int t = t_steps - 1; t >= 0; --t) {
+#pragma unroll
+        for (int k = 0; k < NI; ++k) out[k] = 0.f;
+        if (t < L) {
+            load_record_inputs<E>(d.traj_rec + (size_t)t * Rec<E, 2>::F * ld, ld, i, x);
+            const float grew = V.g_rew ? V.g_rew[(size_t)t * ld + i] : 0.f;
+#pragma unroll
+            for (int q = 0; q < E::O; ++q) gob[q] = V.g_obs ? V.g_obs[((size_t)(t + 1) * E::O + q) * ld + i] : 0.f;
+            // ---- (a) parameter pass
+            {
+                D sD[E::S], hD[HN], aD[E::A], oD[E::O];
+#pragma unroll
+                for (int j = 0; j < E::S; ++j) sD[j] = D(x[j]);
+#pragma unroll
+                for (int j = 0; j < E::H; ++j) hD[j] = D(x[E::S + j]);
+                {
+                    // ActNormWrapper's map as in step_one, then the clip
+                    const bool nrm = (T.flags & VS_FLAG_ACT_NORM) != 0;
+                    float an[E::A], a_app[E::A];
+#pragma unroll
+                    for (int j = 0; j < E::A; ++j) {
+                        float m = alo[j] + (x[NS + j] + 1.0f) * (ahi[j] - alo[j]) * 0.5f;
+                        an[j] = nrm ? m : x[NS + j];
+                    }
+                    E::limit_act(c, alo, ahi, an, a_app);
+#pragma unroll
+                    for (int j = 0; j < E::A; ++j) aD[j] = D(a_app[j]);
+                }
+                E::template dynamics<D, D>(T, cD, sD, hD, aD, (const D*)nullptr);
+                E::observe(sD, oD);
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {
+#pragma unroll
+                    for (int k = 0; k < E::S; ++k) dp[j] = fmaf(lam[k], sD[k].d[j], dp[j]);
+#pragma unroll
+                    for (int k = 0; k < E::H; ++k) dp[j] = fmaf(lam[E::S + k], hD[k].d[j], dp[j]);
+#pragma unroll
+                    for (int q = 0; q < E::O; ++q) dp[j] = fmaf(gob[q], oD[q].d[j], dp[j]);
+                }
+            }
+            // ---- (b) state pass
+            vjp_step<E>(T, c, x, t, lam, grew, gob, out);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) lam[k] = out[k];
+        }
+#pragma unroll
+        for (int j = 0; j < E::A; ++j) V.d_act[((size_t)t * E::A + j) * ld + i] = out[NS + j];
+    }
+    if (L > 0) {  // x is row 0 here: every lane with a rollout ran t = 0 last
+#pragma unroll
+        for (int q = 0; q < E::O; ++q) gob[q] = V.g_obs ? V.g_obs[(size_t)q * ld + i] : 0.f;
+        vjp_observe<E>(x, gob, lam);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * ld + i] = lam[k];
+    const int nq = Q.n;  // (wave-uniform) nq <= NP
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+        if (j < nq) Q.d_params[(size_t)j * ld + i] = dp[j];
+}
+
 // ------------------------------------------------------------------- reverse-mode sweep with a linear policy in the loop
 // vs_rollout_vjp_policy: k_rollout_vjp for rollouts that k_rollout_lin recorded -- a_t = W phi(obs_t) + n_t with the handle's linear
 // policy (Lin: the same packed weights, slot order, kinds, xterm and observation view) and n_t constant (the exploration noise is in the
@@ -4474,6 +4608,7 @@ struct Launch {
     static void rollout_play(vs_env* h, int k, int rec);                      // ... playback of recorded actions (+ discrepancy)
     static void rollout_play_sens(vs_env* h, int k);                          // ... and its parameter sensitivities (vs_set_rollout_sens)
     static void rollout_vjp(vs_env* h, const Vjp& v, int t_steps);            // vs_rollout_vjp
+    static void rollout_vjp_dp(vs_env* h, const Vjp& v, const VjpDp& q, int t_steps);       // vs_rollout_vjp_params
     static void rollout_vjp_lin(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_policy
     static void rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_fnn
     static void rollout_vjp_rnn(vs_env* h, const Vjp& v, const float* g_act, const float* g_hid_last, float* d_hid, float* d_hid0,
@@ -4751,6 +4886,17 @@ void Launch<E>::rollout_vjp(vs_env* h, const Vjp& v, int t_steps) {
     if constexpr (!std::is_same<E, BobD>::value)
         hipLaunchKernelGGL((k_rollout_vjp<E>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, t_steps);
     else no_kernel("rollout_vjp");
+}
+
+template <class E>
+void Launch<E>::rollout_vjp_dp(vs_env* h, const Vjp& v, const VjpDp& q, int t_steps) {
+    // the shape of rollout_vjp; NP = 1, 2 or 4 tangents as in rollout_play_sens (n = 3 runs 4)
+    with_int<1, 2, 4>(q.n <= 2 ? q.n : 4, [&](auto NP) __attribute__((always_inline)) {
+        if constexpr (!std::is_same<E, BobD>::value)
+            hipLaunchKernelGGL((k_rollout_vjp_dp<E, NP>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, q,
+                               t_steps);
+        else no_kernel("rollout_vjp_dp");
+    });
 }
 
 template <class E>

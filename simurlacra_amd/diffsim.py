@@ -8,7 +8,10 @@ trajectory optimisation on the return, initial-state estimation next to the para
 written in torch over the observations and rewards of a rollout.
 
 Conventions are those of the kernel: the raw action is the variable (ActNormWrapper's map, the clip and the dead zone are inside
-the step, kinks follow the branch taken), domain parameters and the initial hidden state are constants.
+the step, kinks follow the branch taken), domain parameters and the initial hidden state are constants.  DifferentiableRollout
+also takes the domain parameters as a torch tensor: the backward pass is then the sweep that carries their gradient next to the
+others (vs_rollout_vjp_params, k_rollout_vjp_dp) -- system identification with any loss written in torch over the observations.
+The reward, the bounds of the spaces and the initial state are constants with respect to the parameters.
 
 DifferentiablePolicyRollout is the closed-loop form: a LinearPolicy on a feature stack runs inside the recording launch
 (vs_set_policy_linear), and the backward pass is one closed-loop sweep (vs_rollout_vjp_policy, k_rollout_vjp_lin) -- the action's
@@ -101,7 +104,12 @@ class DifferentiableRollout(_RecordedBatches):
     from) are float32 tensors on the env's device.  Returns obs [N, T + 1, O] (row k: the observation after k steps), rew [N, T]
     and lengths [N] (int64: the steps a rollout took before its episode ended); rows behind a rollout's end are 0.  obs and rew
     carry gradients to actions and init_states; domain_params -- a list of N dicts or an [N, n_names] array with names=, as for
-    TrajectoryMatchSampler.param_matrix; None: the env's own -- gets none.  More than batch_lanes rollouts run in batches."""
+    TrajectoryMatchSampler.param_matrix; None: the env's own -- gets none.  domain_params may also be a float32 torch tensor
+    [N, len(names)] with names= (distinct names): when it requires grad, obs and rew carry gradients to it as well -- through
+    _calc_constants and the dynamics; the reward's own dependence on a parameter, the bounds of the spaces and the initial state are
+    constants, as for TrajectoryMatchSampler.evaluate_grad.  Up to VS_SENS_MAX_PARAMS names are one backward sweep
+    (rollout_vjp_params), more run as further sweeps of that many over the same records.  A tensor that does not require grad
+    takes the plain sweep.  More than batch_lanes rollouts run in batches."""
 
     def __init__(self, env, batch_lanes: int = 65536):
         super().__init__(env, "DifferentiableRollout", batch_lanes)
@@ -128,6 +136,16 @@ class DifferentiableRollout(_RecordedBatches):
         if tuple(init_states.shape) != (actions.shape[0], S):
             raise ShapeErr(msg=f"init_states must be [{actions.shape[0]}, {S}], got shape {tuple(init_states.shape)}")
         N = actions.shape[0]
+        ptensor = domain_params if isinstance(domain_params, torch.Tensor) else None
+        if ptensor is not None:
+            if names is None:
+                raise ShapeErr(msg="domain_params as a tensor needs names=, one per column")
+            if ptensor.dim() != 2 or tuple(ptensor.shape) != (N, len(names)):
+                raise ShapeErr(msg=f"domain_params must be [{N}, {len(names)}] (one column per name), got shape {tuple(ptensor.shape)}")
+            if ptensor.dtype != torch.float32:
+                raise TypeErr(msg=f"domain_params must be a float32 tensor, got {ptensor.dtype}")
+            if len(set(names)) != len(names):
+                raise ValueErr(msg=f"domain_params: a name is repeated in {list(names)}")
         params = domain_param_matrix(self._base, [dict()] * N if domain_params is None else domain_params, names)
         if params.shape[0] != N:
             raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
@@ -135,7 +153,8 @@ class DifferentiableRollout(_RecordedBatches):
             if not x.is_cuda or x.dtype != torch.float32:
                 raise TypeErr(msg=f"{name} must be a float32 tensor on the GPU")
         self._calls += 1
-        obs, rew, lengths = _RolloutFn.apply(self, self._calls, params, actions, init_states)
+        wrt = tuple(names) if ptensor is not None else None
+        obs, rew, lengths = _RolloutFn.apply(self, self._calls, params, wrt, ptensor, actions, init_states)
         return obs, rew, lengths
 
     def _forward(self, call, params, actions, init_states):
@@ -158,28 +177,39 @@ class DifferentiableRollout(_RecordedBatches):
         rew = rew * (steps[None, :T] < lengths[:, None]).to(rew.dtype)
         return obs, rew, lengths
 
-    def _backward(self, call, params, actions, init_states, grad_obs, grad_rew):
+    def _backward(self, call, params, actions, init_states, grad_obs, grad_rew, wrt=None):
+        """(d actions, d init_states, d domain parameters [N, len(wrt)] or None); wrt: the names whose gradient is asked for"""
         A, S, O = self._dims()
         N, T = actions.shape[0], actions.shape[1]
         d_act = torch.empty(N, T, A, dtype=torch.float32, device=actions.device)
         d_init = torch.empty(N, S, dtype=torch.float32, device=actions.device)
+        d_par = torch.empty(N, len(wrt), dtype=torch.float32, device=actions.device) if wrt else None
+        P = L.VS_SENS_MAX_PARAMS
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, (call, b), actions[n0:n1].contiguous(), init_states[n0:n1], params[n0:n1])
             with v.on_current_stream():
                 g_rew = None if grad_rew is None else lanes_last(grad_rew[n0:n1].to(torch.float32), v.ld)
                 g_obs = None if grad_obs is None else lanes_last(grad_obs[n0:n1].to(torch.float32), v.ld)
-                da, di = v.rollout_vjp(T, g_rew=g_rew, g_obs=g_obs)
+                if wrt:  # passes of P names over the same records; d_act and d_init are the same in each: the first one's are taken
+                    da, di, dp = v.rollout_vjp_params(T, wrt[:P], g_rew=g_rew, g_obs=g_obs)
+                    d_par[n0:n1, :P] = lanes_first(dp, n)
+                    for j0 in range(P, len(wrt), P):
+                        d_par[n0:n1, j0:j0 + P] = lanes_first(v.rollout_vjp_params(T, wrt[j0:j0 + P], g_rew=g_rew, g_obs=g_obs)[2], n)
+                else:
+                    da, di = v.rollout_vjp(T, g_rew=g_rew, g_obs=g_obs)
                 d_act[n0:n1] = lanes_first(da, n)
                 d_init[n0:n1] = lanes_first(di[:S], n)             # (the initial hidden state is a constant)
-        return d_act, d_init
+        return d_act, d_init, d_par
 
 
 class _RolloutFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, roll, call, params, actions, init_states):
+    def forward(ctx, roll, call, params, wrt, ptensor, actions, init_states):
+        # params [N, P] is the matrix the handles get (ptensor's values are in it already); ptensor only ties the graph to wrt
         obs, rew, lengths = roll._forward(call, params, actions.detach(), init_states.detach())
-        ctx.roll, ctx.call, ctx.params = roll, call, params
+        ctx.roll, ctx.call, ctx.params, ctx.wrt = roll, call, params, wrt
+        ctx.pdev = None if ptensor is None else ptensor.device
         ctx.save_for_backward(actions, init_states)
         ctx.mark_non_differentiable(lengths)
         return obs, rew, lengths
@@ -187,8 +217,9 @@ class _RolloutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_obs, grad_rew, _grad_lengths):
         actions, init_states = ctx.saved_tensors
-        d_act, d_init = ctx.roll._backward(ctx.call, ctx.params, actions.detach(), init_states.detach(), grad_obs, grad_rew)
-        return None, None, None, d_act, d_init
+        wrt = ctx.wrt if ctx.needs_input_grad[4] else None
+        d_act, d_init, d_par = ctx.roll._backward(ctx.call, ctx.params, actions.detach(), init_states.detach(), grad_obs, grad_rew, wrt)
+        return None, None, None, None, None if d_par is None else d_par.to(ctx.pdev), d_act, d_init
 
 
 class _ClosedLoopRollout(_RecordedBatches):

@@ -749,10 +749,8 @@ class VecSimEnv:
             raise ValueErr(msg="no rollout target set (set_rollout_target)")
         return torch.as_tensor(_DevArray(ptr, (self.ld,), "<f4", self), device=f"cuda:{self.device}")[: self.n_envs]
 
-    def set_rollout_sens(self, params=None):
-        """Sensitivities of the trajectory discrepancy (vs_set_rollout_sens): params is a sequence of up to VS_SENS_MAX_PARAMS
-        distinct domain-parameter names or indices; step_policy then also sums rollout_grad() and rollout_gn().  Needs a playback
-        policy and a rollout target, auto-reset off and no wrapper pipeline.  None or an empty sequence turns them off."""
+    def _param_indices(self, params):
+        """indices of a sequence of domain-parameter names or indices (one name or index stands for itself; None: none)"""
         idx = []
         for k in ([] if params is None else ([params] if isinstance(params, (str, int, np.integer)) else list(params))):
             if isinstance(k, str):
@@ -760,6 +758,13 @@ class VecSimEnv:
                     raise ValueErr(msg=f"unsupported domain parameter {k!r} for env {self.name}")
                 k = self.param_names.index(k)
             idx.append(int(k))
+        return idx
+
+    def set_rollout_sens(self, params=None):
+        """Sensitivities of the trajectory discrepancy (vs_set_rollout_sens): params is a sequence of up to VS_SENS_MAX_PARAMS
+        distinct domain-parameter names or indices; step_policy then also sums rollout_grad() and rollout_gn().  Needs a playback
+        policy and a rollout target, auto-reset off and no wrapper pipeline.  None or an empty sequence turns them off."""
+        idx = self._param_indices(params)
         arr = np.ascontiguousarray(np.asarray(idx, dtype=np.int32))
         rc = self._lib.vs_set_rollout_sens(self._h, arr.ctypes.data_as(C.c_void_p) if idx else None, len(idx))
         self._check(rc, "vs_set_rollout_sens")
@@ -876,6 +881,26 @@ class VecSimEnv:
         self._check(self._lib.vs_rollout_vjp(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
                     "vs_rollout_vjp")
         return d_act, d_init
+
+    def rollout_vjp_params(self, t_steps, params, g_rew=None, g_obs=None, g_last=None):
+        """rollout_vjp with the gradient with respect to domain parameters next to it (vs_rollout_vjp_params): params is a sequence
+        of 1 .. VS_SENS_MAX_PARAMS distinct names or indices, resolved as set_rollout_sens resolves them; cotangents as for
+        rollout_vjp (g_last: g_state_last).  Returns (d_act [T, A, ld], d_init [S + H, ld], d_params [len(params), ld]) on the
+        device: d_act and d_init are rollout_vjp's bits, d_params[j] is the gradient with respect to the lane's own parameter j.
+        The reward, the bounds of the spaces and the initial state are constants with respect to the parameters."""
+        import torch
+
+        T = int(t_steps)
+        S, O, H = (self.dims[k] for k in "SOH")
+        idx = self._param_indices(params)
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_last", g_last, (S + H, self.ld))))
+        arr = np.ascontiguousarray(np.asarray(idx, dtype=np.int32))
+        d_params = torch.empty(max(len(idx), 1), self.ld, dtype=torch.float32, device=d_act.device)
+        self._check(self._lib.vs_rollout_vjp_params(self._h, T, *ptrs, arr.ctypes.data_as(C.c_void_p) if idx else None, len(idx),
+                                                    C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr()),
+                                                    C.c_void_p(d_params.data_ptr())), "vs_rollout_vjp_params")
+        return d_act, d_init, d_params
 
     def rollout_vjp_policy(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
         """The sweep of rollout_vjp for closed-loop records (vs_rollout_vjp_policy): rows 0 .. t_steps - 1 were recorded by
