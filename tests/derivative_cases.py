@@ -1,0 +1,211 @@
+"""
+What the GPU tests of the derivative kernels share (test_gpu_rollout_vjp*, test_gpu_trajectory_grad, test_gpu_policy_vjp, test_gpu_fnn_vjp,
+test_gpu_rnn_vjp, test_gpu_fnn_param_grad): the families' tables and shapes, the edge lanes, the fp64 open-loop rollout, the mode-2
+recording launch loop, the playback cotangents and the project's tolerance.  Not a test module: import it by bare name.
+
+The project's tolerance (test_step_jacobians_against_finite_differences) is 3e-3 |g| + 3e-4 max |g_smooth|, an entry smooth where the
+central differences of the fp64 oracle at relative steps 1e-6 and 1e-5 agree to 1e-4.  `max |g_smooth|` needs entries of ONE unit, and
+the derivative tests have two kinds of arrays, hence two rules -- both intended, neither a special case of the other:
+
+  * per lane (smooth_per_lane, tolerance_per_lane, within_per_lane, worst_of): gradients with respect to action and state columns,
+    [N, T A + S (+ hidden entries)], each column scaled by ACT_IN / INIT_SCALE.  The lanes differ by orders of magnitude (an edge lane
+    against one at rest), so the maximum is taken over a lane's own row; a lane without a smooth entry gets the floor 1.0.  Users:
+    test_gpu_rollout_vjp, test_gpu_policy_vjp, test_gpu_fnn_vjp, test_gpu_rnn_vjp (the last per block of columns).
+  * global (smooth_global, within_global): derivatives per unit relative change of a domain parameter, d / d log theta, [N, G] and
+    [N, G, G].  That unit is one per FAMILY -- the +-5 % lanes are of one size -- so there is one maximum over the whole array; without a
+    mask every entry counts, and with nothing smooth the result is (0.0, 0.0).  Users: test_gpu_rollout_vjp_params,
+    test_gpu_trajectory_grad.
+"""
+from typing import NamedTuple
+
+import numpy as np
+
+from oracle import cpu_ref
+
+FAMILIES = ["omo", "bob", "qq-su", "qcp-su", "pend", "qbb"]
+KW = {"omo": dict(dt=0.02), "bob": dict(dt=0.01), "qq-su": dict(dt=0.004), "qcp-su": dict(dt=0.002), "pend": dict(dt=0.01),
+      "qbb": dict(dt=0.01)}
+# action sizes strictly inside every lane's action box (and outside the dead zones): |a| in [0.3, 0.6] of these
+ACT_IN = {"omo": 10.0, "bob": 10.0, "qq-su": 4.0, "qcp-su": 5.0, "pend": 3.0, "qbb": 2.5}
+# the parameters differentiated (indices into vs_param_name): masses, lengths, motor constants, dampings -- none is 0 at nominal
+WRT = {"omo": [0, 1, 2], "bob": [0, 1, 3, 6], "qq-su": [1, 2, 6, 8], "qcp-su": [1, 8, 12, 13], "pend": [0, 1, 2, 3],
+       "qbb": [1, 4, 9, 10]}
+# full initial states well inside the state space: uniform in +- these
+INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
+              "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
+# 150 lanes (three waves, the last one partial), T = 24 steps in launches of 7 + 1 + 16 against one uncut launch, lanes 0 .. 9 at the edge
+N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
+# what a derivative call must leave untouched on the handle
+STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG")
+# a tanh output nonlinearity: the pre-activation is +-TANH_OUT_AMP around +-TANH_OUT_AT
+TANH_OUT_AT, TANH_OUT_AMP = float(np.arctanh(0.7)), 0.24
+
+
+# ------------------------------------------------------------------------------------------------------------ the inputs
+def edge_states(name, init, n_edge=N_EDGE):
+    """lanes 0 .. n_edge - 1 start at the edge of the state space, moving out: they end early"""
+    init = init.copy()
+    e = slice(0, n_edge)
+    if name == "qbb":      # ball near the plate's edge, rolling outwards
+        init[e, 2], init[e, 6] = 0.13, 0.45
+    elif name == "qq-su":  # arm near its end stop, turning outwards
+        init[e, 0], init[e, 2] = 2.0, 5.0
+    elif name == "bob":    # ball near the beam's end
+        init[e, 0], init[e, 2] = 0.98, 3.0
+    elif name == "omo":
+        init[e, 0], init[e, 1] = 0.98, 5.0
+    elif name == "qcp-su":
+        init[e, 0], init[e, 2] = 0.25, 0.6
+    else:  # pend
+        init[e, 0], init[e, 1] = 12.5, 5.0
+    return init
+
+
+def draw_params_and_init(ref, name, rng):
+    """the first two draws of every case(): params [N, P] float32 (+-5 % per lane and parameter around nominal) and init [N, S] float32
+    (uniform in +-INIT_SCALE, lanes 0 .. N_EDGE - 1 at the edge)"""
+    nominal = ref.nominal_params(1).astype(np.float32)[0]
+    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
+    init = edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
+    return params, init
+
+
+def frozen(c, *more):
+    """the case with every array in it (and in `more`) read-only: the tests leave their inputs unchanged"""
+    for v in list(c.values()) + list(more):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+def playback_case(name):
+    """the inputs of a family's playback rollouts, all float32: params [N, P], init [N, S], acts [N, T, A] strictly inside the box and
+    outside the dead zones, and the cotangents g_rew [N, T], g_obs [N, T + 1, O], g_last [N, S + H] -> (the case, not yet frozen, and
+    the generator it was drawn from, for a caller that draws more)"""
+    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
+    rng = np.random.default_rng(23)
+    params, init = draw_params_and_init(ref, name, rng)
+    acts = (ACT_IN[name] * rng.uniform(0.3, 0.6, (N, T, ref.A)) * rng.choice([-1.0, 1.0], (N, T, ref.A))).astype(np.float32)
+    c = dict(ref=ref, params=params, init=init, acts=acts, g_rew=rng.normal(size=(N, T)).astype(np.float32),
+             g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
+    return c, rng
+
+
+# ------------------------------------------------------------------------------------------------------- the fp64 oracle
+class Rollout(NamedTuple):
+    states: np.ndarray   # [T + 1, N, S]
+    hiddens: np.ndarray  # [T + 1, N, H]
+    obs: np.ndarray      # [T + 1, N, O]
+    rew: np.ndarray      # [T, N]
+    done: np.ndarray     # [T, N]
+
+
+def oracle_rollout(ref, params, state0, hidden0, acts):
+    """the fp64 oracle along acts [N, T, A] (it does not freeze at done: the caller sums a lane up to its own number of steps)"""
+    st, hid = state0.copy(), hidden0.copy()
+    states, hiddens, obs, rew, done = [st], [hid], [ref.observe(st)], [], []
+    with np.errstate(all="ignore"):
+        for t in range(acts.shape[1]):
+            out = ref.step(st, hid, acts[:, t], params, np.full(st.shape[0], t))
+            st, hid = out["state"], out["hidden"]
+            states.append(st), hiddens.append(hid), obs.append(out["obs"]), rew.append(out["rew"]), done.append(out["done"])
+    return Rollout(np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done))
+
+
+def lengths_of(done):
+    """[N]: 1 + the first step whose done flag is set, T if none is (done [T, N])"""
+    return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
+
+
+def action_window(name, output_nonlin):
+    """(lo, hi) of |a| under a network policy made as the FNN and RNN test modules make theirs: section 8e's box, or the tanh output's"""
+    return (0.51, 0.83) if output_nonlin == "tanh" else (0.30 * ACT_IN[name], 0.60 * ACT_IN[name])
+
+
+def check_net_keeps_the_box(c, acts, length):
+    """the oracle's actions [T, N, A] inside the lanes' lengths lie in the window of the case's network c["net"]"""
+    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
+    a = np.abs(acts)
+    lo, hi = action_window(c["name"], c["net"]["output_nonlin"])
+    assert (np.where(inside, a, lo) >= lo).all() and (np.where(inside, a, lo) <= hi).all(), c["name"]
+
+
+# ------------------------------------------------------------------------------------------------------------ the device
+def dev(x):
+    import torch
+
+    return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
+
+
+def record_mode2(e, capacity, params, set_policy, init, splits, **step_kw):
+    """rows 0 .. sum(splits) - 1 of the handle e hold the rollouts under the policy that set_policy(e) installs, from init under params,
+    recorded in mode 2 by step_policy(k, record=True, **step_kw) in launches of `splits` steps -> e"""
+    e.set_auto_reset(False)
+    e.set_record_mode(2)
+    e.set_traj_capacity(capacity)
+    e.set_params(params)
+    set_policy(e)
+    e.reset(init_state=init)
+    t0 = 0
+    for k in splits:
+        e.set_traj_offset(t0)
+        e.step_policy(k, record=True, **step_kw)
+        t0 += k
+    e.set_traj_offset(0)
+    return e
+
+
+def case_cotangents(vs, c, e, t_steps=T, last="g_state_last"):
+    """g_rew, g_obs and g_last of the case on the device, lanes last, cut to the handle's lanes and to t_steps; `last`: the keyword
+    the entry point has for g_last"""
+    return {"g_rew": vs.lanes_last(dev(c["g_rew"][:e.n_envs, :t_steps]), e.ld),
+            "g_obs": vs.lanes_last(dev(c["g_obs"][:e.n_envs, :t_steps + 1]), e.ld), last: vs.lanes_last(dev(c["g_last"][:e.n_envs]), e.ld)}
+
+
+def scaled(vs, c, d_act, d_init, n=N):
+    """d_act [T, A, ld] and d_init [S + H, ld] of the device -> [n, T A + S] float64 per unit of the inputs' scales (ACT_IN, INIT_SCALE)"""
+    ref, name = c["ref"], c["name"]
+    d_act, d_init = vs.lanes_first(d_act, n).cpu().numpy(), vs.lanes_first(d_init, n).cpu().numpy()
+    got = np.concatenate([d_act.reshape(n, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
+    assert np.isfinite(got).all()
+    return got.astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------- the tolerance, per lane
+def smooth_per_lane(g1, g2):
+    mag = np.maximum(np.abs(g1), np.abs(g2))
+    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max(axis=1, keepdims=True))
+
+
+def tolerance_per_lane(want, smooth):
+    top = np.where(smooth, np.abs(want), 0.0).max(axis=1, keepdims=True)
+    return 3e-3 * np.abs(want) + 3e-4 * np.where(smooth.any(axis=1, keepdims=True), top, 1.0)
+
+
+def within_per_lane(got, want, smooth):
+    """the project's tolerance per lane on the smooth entries -> (share of bad entries, worst error / tolerance); with no smooth entry
+    at all the worst is the maximum of nothing: an error, not a pass"""
+    tol = tolerance_per_lane(want, smooth)
+    err = np.abs(got - want)
+    bad = smooth & (err > tol)
+    return float(bad.mean()), float((err[smooth] / tol[smooth]).max())
+
+
+def worst_of(got, want, smooth):
+    """worst error / tolerance over ALL entries, the tolerance per lane"""
+    return float((np.abs(got - want) / tolerance_per_lane(want, smooth)).max())
+
+
+# -------------------------------------------------------------------------------------- the tolerance, one unit per family
+def smooth_global(g1, g2):
+    mag = np.maximum(np.abs(g1), np.abs(g2))
+    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max())
+
+
+def within_global(got, want, smooth=None):
+    """the project's tolerance on (smooth) entries -> (share of bad entries, worst error / tolerance)"""
+    smooth = np.ones(want.shape, dtype=bool) if smooth is None else smooth
+    tol = 3e-3 * np.abs(want) + 3e-4 * (np.abs(want[smooth]).max() if smooth.any() else 1.0)
+    err = np.abs(got - want)
+    bad = smooth & (err > tol)
+    return float(bad.mean()), float((err[smooth] / tol[smooth]).max()) if smooth.any() else 0.0

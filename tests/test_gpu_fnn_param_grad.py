@@ -2,7 +2,7 @@
 vs_fnn_param_grad / k_fnn_param_grad + k_fnn_param_reduce: the parameter gradient of a feed-forward network policy over the recorded
 rows of a handle, VecSimEnv.fnn_param_grad and DifferentiableNetRollout(param_pass="kernel").
 
-Shapes, networks and seeds are those of test_gpu_fnn_vjp.py (whose helpers are imported): 150 lanes (64 + 64 + 22), T = 24, +-5 % per-lane
+Shapes, networks and seeds are those of test_gpu_fnn_vjp.py (whose cases are imported): 150 lanes (64 + 64 + 22), T = 24, +-5 % per-lane
 parameters, lanes 0 .. 9 end early.  abar is random and dense and is fed directly.
 
 Reference: test_fnn_param_grad_host.param_grad_fp64 -- the sum restated in fp64 over the RECORDED observations and lengths (held to
@@ -38,10 +38,9 @@ torch = pytest.importorskip("torch")
 
 import test_fnn_param_grad_host as host  # noqa: E402  (the fp64 reference and its error bound)
 import test_gpu_fnn_vjp as fv  # noqa: E402  (cases, networks, seeds)
-from test_gpu_fnn_vjp import ACT_IN, KW, MAX_STEPS, N, N_EDGE, T, dev  # noqa: E402
+from derivative_cases import ACT_IN, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, dev, record_mode2  # noqa: E402
 
 TABLE = ["omo-1-relu", "omo-63x7-relu", "qq-su-16", "qq-su-64x64-feat", "qcp-su-32x33", "qbb-31x64-tanh-out", "pend-view-8-sigmoid"]
-STATE_BUFFERS = fv.STATE_BUFFERS
 
 
 @pytest.fixture(scope="module")
@@ -68,19 +67,14 @@ def recorded(vs, key, n=N, t=T, lanes=None, spec=None, noise_seed=0, cap=None):
     name = c["name"]
     pick = (lambda x: np.resize(x, (n,) + x.shape[1:])) if lanes is None else (lambda x: np.resize(x[lanes], (n,) + x.shape[1:]))
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(t if cap is None else cap)
-    e.set_params(pick(c["params"]))
-    if spec is None:
-        fv.set_net(e, c["net"])
-    else:
-        e.set_policy_fnn(**spec)
-    e.reset(init_state=pick(c["init"]))
-    e.set_traj_offset(0)
-    e.step_policy(t, record=True, noise_seed=noise_seed)
-    e.set_traj_offset(0)
-    return e
+
+    def policy(e):
+        if spec is None:
+            fv.set_net(e, c["net"])
+        else:
+            e.set_policy_fnn(**spec)
+
+    return record_mode2(e, t if cap is None else cap, pick(c["params"]), policy, pick(c["init"]), (t,), noise_seed=noise_seed)
 
 
 def abar_of(key, n, t, seed=0):

@@ -2,8 +2,8 @@
 vs_rollout_vjp_fnn / k_rollout_vjp_fnn: the reverse-mode sweep over CLOSED-LOOP recorded rollouts with a feed-forward network of one or
 two hidden layers in the loop, VecSimEnv.rollout_vjp_fnn and DifferentiableNetRollout.
 
-Shapes, cotangents, scales and the tolerance rule are those of test_gpu_policy_vjp.py (whose helpers are imported): 150 lanes (64 + 64 +
-22: a partial last workgroup), T = 24, max_steps = 50, +-5 % per-lane parameters, lanes 0 .. 9 start at the edge of the state space and
+Shapes, cotangents, scales and the per-lane tolerance rule are those of test_gpu_policy_vjp.py, both from derivative_cases.py: 150 lanes
+(64 + 64 + 22: a partial last workgroup), T = 24, max_steps = 50, +-5 % per-lane parameters, lanes 0 .. 9 start at the edge of the state space and
 end early, random cotangents on all four inputs; per lane 3e-3 |g| + 3e-4 max |g| against central differences of the fp64 closed loop at
 relative steps 1e-6 and 1e-5 (oracle.cpu_ref for the step, the NumPy network below for the policy).  Here EVERY entry must be smooth (the
 two step sizes agree; asserted from the oracle alone) and every entry is held to the tolerance: none is excluded.
@@ -32,8 +32,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_policy_vjp as lin  # noqa: E402  (shapes, scales, the tolerance rule and the cotangent helpers of section 8e)
-from test_gpu_policy_vjp import ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, T, dev, lengths_of, smooth_of, tolerance  # noqa: E402
+from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, TANH_OUT_AMP, TANH_OUT_AT,  # noqa: E402
+                              check_net_keeps_the_box, dev, draw_params_and_init, frozen, lengths_of, record_mode2, scaled,
+                              smooth_per_lane, tolerance_per_lane, worst_of)
 
 # case -> (family, hidden sizes, hidden nonlinearities, output nonlinearity, feat, obs_idx, seed, gain of the output layer)
 CASES = {
@@ -51,7 +52,6 @@ ORACLE_CASES = ["qq-su-16", "qq-su-64x64-feat", "qcp-su-32x33", "qbb-31x64-tanh-
 DEGENERATE = {"omo": "omo-63x7-relu", "bob": "bob-8", "qq-su": "qq-su-64x64-feat", "qcp-su": "qcp-su-32x33", "pend": "pend-8",
               "qbb": "qbb-31x64-tanh-out"}
 FUNCS = {"tanh": np.tanh, "relu": lambda z: np.maximum(z, 0.0), "sigmoid": lambda z: 1.0 / (1.0 + np.exp(-z)), None: lambda z: z}
-TANH_OUT_AT, TANH_OUT_AMP = float(np.arctanh(0.7)), 0.24
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +93,7 @@ def flat_params(net):
 
 
 def closed_loop(ref, params, state0, hidden0, net, offs, open_acts=None):
-    """lin.closed_loop with the network as the policy: a_t = net(obs_t) + offs[:, t] -> ..., and the hidden pre-activations
+    """test_gpu_policy_vjp's closed_loop with the network as the policy: a_t = net(obs_t) + offs[:, t] -> ..., and the hidden pre-activations
     [T][layer][n, h]"""
     st, hid = state0.copy(), hidden0.copy()
     ob = ref.observe(st)
@@ -144,27 +144,22 @@ def make_net(ref, name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, par
 
 @functools.lru_cache(maxsize=None)
 def case(key):
-    """the inputs of a case, float32 and left unchanged by the tests (lin.case's, with a network for the stack)"""
+    """the inputs of a case, float32 and left unchanged by the tests (test_gpu_policy_vjp's case, with a network for the stack)"""
     name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, seed, gain = CASES[key]
     ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
     rng = np.random.default_rng(100 + seed)
-    nominal = ref.nominal_params(1).astype(np.float32)[0]
-    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
-    init = lin.edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
+    params, init = draw_params_and_init(ref, name, rng)
     h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
     net = make_net(ref, name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, params.astype(np.float64), init.astype(np.float64), h0,
                    rng, T, gain)
     c = dict(name=name, ref=ref, params=params, init=init, h0=h0, net=net,
              g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
              g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
-    for v in list(c.values()) + net["W"] + net["b"]:
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return c
+    return frozen(c, *net["W"], *net["b"])
 
 
 def phi(c, state0, offs, length, open_acts=None):
-    """lin.phi for the network's closed loop"""
+    """test_gpu_policy_vjp's phi for the network's closed loop"""
     states, hiddens, obs, rew, _, acts, _ = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"], c["net"], offs, open_acts)
     k = np.arange(T + 1)[:, None]
     n = np.arange(state0.shape[0])
@@ -177,7 +172,7 @@ def phi(c, state0, offs, length, open_acts=None):
 
 
 def reference(c, offs0):
-    """lin.reference: central differences of Phi at relative steps 1e-6 and 1e-5 [N, T A + S] (offsets first, step-major), the lane
+    """test_gpu_policy_vjp's reference: central differences of Phi at relative steps 1e-6 and 1e-5 [N, T A + S] (offsets first, step-major), the lane
     lengths, the oracle's actions [T, N, A], d_init [N, S] of the OPEN loop along them, and the hidden pre-activations"""
     ref, name = c["ref"], c["name"]
     s0 = c["init"].astype(np.float64)
@@ -211,11 +206,6 @@ def oracle_reference(key):
     return reference(c, np.zeros((N, T, c["ref"].A)))
 
 
-def worst_of(got, want, smooth):
-    """worst error / tolerance over ALL entries, the tolerance per lane"""
-    return float((np.abs(got - want) / tolerance(want, smooth)).max())
-
-
 def set_net(e, net, noise_std=None):
     e.set_policy_fnn(flat_params(net), list(net["hidden"]), hidden_nonlin=list(net["hidden_nonlin"]), output_nonlin=net["output_nonlin"],
                      feat=net["feat"], obs_idx=net["obs_idx"], noise_std=noise_std)
@@ -226,24 +216,17 @@ def recorded(vs, key, splits=(T,), noise_seed=0, n=N, shape=None, net=None, spec
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(T)
-    e.set_params(np.resize(c["params"], (n, c["params"].shape[1])))
-    if spec is None:
-        set_net(e, c["net"] if net is None else net)
-    else:  # what fnn_kernel_spec made of a torch policy
-        e.set_policy_fnn(**spec)
-    if shape is not None:
-        e.set_policy_shape(shape)
-    e.reset(init_state=np.resize(c["init"], (n, c["init"].shape[1])))
-    t0 = 0
-    for k in splits:
-        e.set_traj_offset(t0)
-        e.step_policy(k, record=True, noise_seed=noise_seed)
-        t0 += k
-    e.set_traj_offset(0)
-    return e
+
+    def policy(e):
+        if spec is None:
+            set_net(e, c["net"] if net is None else net)
+        else:  # what fnn_kernel_spec made of a torch policy
+            e.set_policy_fnn(**spec)
+        if shape is not None:
+            e.set_policy_shape(shape)
+
+    return record_mode2(e, T, np.resize(c["params"], (n, c["params"].shape[1])), policy, np.resize(c["init"], (n, c["init"].shape[1])), splits,
+                        noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True, n=N):
@@ -254,22 +237,6 @@ def cotangents(vs, key, e, with_act=True, n=N):
     if with_act:
         out["g_act"] = vs.lanes_last(dev(rs(c["g_act"])), e.ld)
     return out
-
-
-def scaled(vs, c, d_act, d_init, n=N):
-    ref, name = c["ref"], c["name"]
-    d_act, d_init = vs.lanes_first(d_act, n).cpu().numpy(), vs.lanes_first(d_init, n).cpu().numpy()
-    got = np.concatenate([d_act.reshape(n, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
-    assert np.isfinite(got).all()
-    return got.astype(np.float64)
-
-
-def check_policy_keeps_the_box(c, acts, length):
-    net, name = c["net"], c["name"]
-    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
-    a = np.abs(acts)
-    lo, hi = (0.51, 0.83) if net["output_nonlin"] == "tanh" else (0.30 * ACT_IN[name], 0.60 * ACT_IN[name])
-    assert (np.where(inside, a, lo) >= lo).all() and (np.where(inside, a, lo) <= hi).all(), name
 
 
 def check_no_unit_near_a_kink(c, pres, length):
@@ -284,7 +251,7 @@ def check_no_unit_near_a_kink(c, pres, length):
 def feedback_seen(c, f1, smooth, open_init, length):
     """share of the full-length lanes on which a d_init that lacks the feedback is off by more than 10 x the tolerance"""
     init_cols = slice(T * c["ref"].A, None)
-    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance(f1, smooth)[:, init_cols]
+    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance_per_lane(f1, smooth)[:, init_cols]
     return float(gap.any(axis=1)[length == T].mean())
 
 
@@ -297,9 +264,9 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     c = case(key)
     ref = c["ref"]
     f1, f2, length, acts, open_init, pres = oracle_reference(key)
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone: every entry, none excluded
-    check_policy_keeps_the_box(c, acts, length)
+    check_net_keeps_the_box(c, acts, length)
     check_no_unit_near_a_kink(c, pres, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
     seen = feedback_seen(c, f1, smooth, open_init, length)
@@ -312,7 +279,7 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     _, oi = e.rollout_vjp(T, **{k: v for k, v in cot.items() if k != "g_act"})
     open_got = vs.lanes_first(oi, N).cpu().numpy()[:, :ref.S].astype(np.float64) * np.array(INIT_SCALE[c["name"]])
     init_cols = slice(T * ref.A, None)
-    differs = (np.abs(got[:, init_cols] - open_got) > 10.0 * tolerance(f1, smooth)[:, init_cols]).any(axis=1)
+    differs = (np.abs(got[:, init_cols] - open_got) > 10.0 * tolerance_per_lane(f1, smooth)[:, init_cols]).any(axis=1)
     assert e.error_count() == 0
     e.close()
     worst = worst_of(got, f1, smooth)
@@ -339,7 +306,7 @@ def test_exploration_noise_is_an_additive_constant(vs):
     offs = (act - mlp(c["net"], obs.reshape(T * N, ref.O))[0].reshape(T, N, ref.A)).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
     f1, f2, length, acts, _, _ = reference(c, np.ascontiguousarray(offs))
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert smooth.all()
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_fnn(T, **cotangents(vs, key, e)))
@@ -368,9 +335,6 @@ def test_a_constant_network_reduces_to_the_open_loop_sweep(vs, name):
 
 
 # ------------------------------------------------------------------------------------------------------------- 4. edges
-STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG")
-
-
 @pytest.mark.parametrize("key", ["qq-su-64x64-feat", "qcp-su-32x33"])
 def test_edges(vs, key):
     L = vs._lib
@@ -419,7 +383,7 @@ def test_records_from_both_forward_shapes(vs):
         assert e.error_count() == 0
         e.close()
     rep = lambda x: np.resize(x, (n,) + x.shape[1:])  # noqa: E731  (lane k repeats lane k % N of the case)
-    tol = tolerance(rep(f1), rep(smooth_of(f1, f2)))
+    tol = tolerance_per_lane(rep(f1), rep(smooth_per_lane(f1, f2)))
     worst = float((np.abs(res[0] - res[1]) / tol).max())
     print(f"{key}: 64-env against matrix-core records, worst difference / tolerance {worst:.3f}")
     assert worst <= 1.0, worst
@@ -575,7 +539,7 @@ def test_autograd(vs, name):
     tc = torch_case(name)
     gw, gs, length = oracle_loss_gradients(name)
     for pair in (gw, gs):
-        assert smooth_of(*pair).all()
+        assert smooth_per_lane(*pair).all()
     env = getattr(vs, ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = vs.FNNPolicy(env.spec, hidden_sizes=list(AUTOGRAD[name]), hidden_nonlin=torch.tanh, featurize=False)
     roll = vs.DifferentiableNetRollout(env, policy)
@@ -604,7 +568,7 @@ def test_autograd(vs, name):
     got_w = (flat_grad(g1[:-1]) * scale)[which].reshape(1, -1)
     got_s = g1[-1].cpu().numpy().astype(np.float64) * np.array(INIT_SCALE[name])
     for what, got, (f1, f2) in (("parameters", got_w, gw), ("init_states", got_s, gs)):
-        worst = worst_of(got, f1, smooth_of(f1, f2))
+        worst = worst_of(got, f1, smooth_per_lane(f1, f2))
         print(f"{name} {what}: worst error / tolerance {worst:.3f}")
         assert worst <= 1.0, (name, what, worst)
     # ---- two steps of plain gradient descent on the parameters (in units of |theta|) lower the oracle's loss; the step size moves no

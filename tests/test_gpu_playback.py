@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from derivative_cases import edge_states  # noqa: E402
 from simurlacra_amd.policies import PlaybackPolicy, TimePolicy  # noqa: E402
 
 FAMILIES = ["omo", "qq-su", "qcp-su", "qbb"]
@@ -144,18 +145,6 @@ def test_auto_reset_restarts_the_recording(vs, name, mode):
 
 
 # ------------------------------------------------------------------------------------------------------- 3. discrepancy
-def edge_states(name, init):
-    """initial states of which some end the episode early: lanes 0 .. 19 start at the edge of the state space, moving out"""
-    init = init.copy()
-    if name == "qbb":      # ball near the plate's edge, rolling outwards
-        init[:20, 2], init[:20, 6] = 0.13, 0.45
-    elif name == "qq-su":  # arm near its end stop, turning outwards
-        init[:20, 0], init[:20, 2] = 2.0, 5.0
-    else:                  # ball-on-beam: ball near the beam's end
-        init[:20, 0], init[:20, 2] = 0.98, 3.0
-    return init
-
-
 @pytest.mark.parametrize("name", ["qq-su", "qbb", "bob"])
 def test_discrepancy(vs, name):
     L = vs._lib
@@ -166,7 +155,7 @@ def test_discrepancy(vs, name):
     weights = np.linspace(0.5, 2.0, O).astype(np.float32)
     # ---- the target: the playback kernel itself, with records, under the scaled parameters
     gen = handle(vs, name, "map", table)
-    init = edge_states(name, gen.get(L.VS_STATE))
+    init = edge_states(name, gen.get(L.VS_STATE), n_edge=20)  # lanes 0 .. 19 start at the edge of the state space and end early
     gen.set_params(np.tile(scaled, (N, 1)))
     gen.reset(init_state=init)
     tr_g = run(gen, (T,))

@@ -28,12 +28,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-KW = {"omo": dict(dt=0.02), "bob": dict(dt=0.01), "qq-su": dict(dt=0.004), "qcp-su": dict(dt=0.002), "pend": dict(dt=0.01),
-      "qbb": dict(dt=0.01)}
-ACT_IN = {"omo": 10.0, "bob": 10.0, "qq-su": 4.0, "qcp-su": 5.0, "pend": 3.0, "qbb": 2.5}
-INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
-              "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
-N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
+from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, case_cotangents, dev,  # noqa: E402
+                              draw_params_and_init, frozen, lengths_of, record_mode2, scaled, smooth_per_lane, tolerance_per_lane,
+                              within_per_lane)
 
 ELEM = ("identity", "squared", "cubic", "sig", "bell", "sin", "cos", "sinsin", "sincos")
 SMALL = ("identity", "sin", "const", ("mult", (0, 1)))
@@ -59,25 +56,6 @@ def vs():
     import simurlacra_amd
 
     return simurlacra_amd
-
-
-def edge_states(name, init):
-    """lanes 0 .. N_EDGE - 1 start at the edge of the state space, moving out: they end early"""
-    init = init.copy()
-    e = slice(0, N_EDGE)
-    if name == "qbb":
-        init[e, 2], init[e, 6] = 0.13, 0.45
-    elif name == "qq-su":
-        init[e, 0], init[e, 2] = 2.0, 5.0
-    elif name == "bob":
-        init[e, 0], init[e, 2] = 0.98, 3.0
-    elif name == "omo":
-        init[e, 0], init[e, 1] = 0.98, 5.0
-    elif name == "qcp-su":
-        init[e, 0], init[e, 2] = 0.25, 0.6
-    else:  # pend
-        init[e, 0], init[e, 1] = 12.5, 5.0
-    return init
 
 
 # ------------------------------------------------------------------------------------------------ the fp64 feature stack
@@ -118,10 +96,6 @@ def closed_loop(ref, params, state0, hidden0, terms, obs_idx, W, offs, open_acts
     return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done), np.stack(acts)
 
 
-def lengths_of(done):
-    return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
-
-
 def make_weights(ref, name, terms, obs_idx, params, s0, h0, rng, n_steps):
     """W [A, F] float32 (see the module docstring)"""
     n_vis = ref.O if obs_idx is None else len(obs_idx)
@@ -154,18 +128,12 @@ def case(key):
     name, terms, obs_idx = CASES[key]
     ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
     rng = np.random.default_rng(29)
-    nominal = ref.nominal_params(1).astype(np.float32)[0]
-    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
-    init = edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
+    params, init = draw_params_and_init(ref, name, rng)
     h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
     W = make_weights(ref, name, terms, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T)
-    c = dict(name=name, terms=terms, obs_idx=obs_idx, ref=ref, params=params, init=init, h0=h0, W=W,
-             g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
-             g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
-    for v in c.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return c
+    return frozen(dict(name=name, terms=terms, obs_idx=obs_idx, ref=ref, params=params, init=init, h0=h0, W=W,
+                       g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
+                       g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32)))
 
 
 def phi(c, state0, offs, length, open_acts=None):
@@ -217,63 +185,24 @@ def oracle_reference(key):
     return reference(c, np.zeros((N, T, c["ref"].A)))
 
 
-def smooth_of(g1, g2):
-    mag = np.maximum(np.abs(g1), np.abs(g2))
-    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max(axis=1, keepdims=True))
-
-
-def tolerance(want, smooth):
-    top = np.where(smooth, np.abs(want), 0.0).max(axis=1, keepdims=True)
-    return 3e-3 * np.abs(want) + 3e-4 * np.where(smooth.any(axis=1, keepdims=True), top, 1.0)
-
-
-def within(got, want, smooth):
-    """the project's tolerance per lane on the smooth entries -> (share of bad entries, worst error / tolerance)"""
-    tol = tolerance(want, smooth)
-    err = np.abs(got - want)
-    bad = smooth & (err > tol)
-    return float(bad.mean()), float((err[smooth] / tol[smooth]).max())
-
-
-def dev(x):
-    return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
-
-
 def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0):
     """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case, recorded in mode 2 by step_policy in the given launches"""
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(T)
-    e.set_params(c["params"])
-    e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
-    e.reset(init_state=c["init"])
-    t0 = 0
-    for k in splits:
-        e.set_traj_offset(t0)
-        e.step_policy(k, record=True, noise_seed=noise_seed)
-        t0 += k
-    e.set_traj_offset(0)
-    return e
+
+    def linear(e):
+        e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
+
+    return record_mode2(e, T, c["params"], linear, c["init"], splits, noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True):
     c = case(key)
-    out = dict(g_rew=vs.lanes_last(dev(c["g_rew"]), e.ld), g_obs=vs.lanes_last(dev(c["g_obs"]), e.ld),
-               g_state_last=vs.lanes_last(dev(c["g_last"]), e.ld))
+    out = case_cotangents(vs, c, e)
     if with_act:
         out["g_act"] = vs.lanes_last(dev(c["g_act"]), e.ld)
     return out
-
-
-def scaled(vs, c, d_act, d_init):
-    ref, name = c["ref"], c["name"]
-    d_act, d_init = vs.lanes_first(d_act, N).cpu().numpy(), vs.lanes_first(d_init, N).cpu().numpy()
-    got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
-    assert np.isfinite(got).all()
-    return got.astype(np.float64)
 
 
 def check_policy_keeps_the_box(c, acts, length):
@@ -294,14 +223,14 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     c = case(key)
     ref = c["ref"]
     f1, f2, length, acts, open_init = oracle_reference(key)
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
     check_policy_keeps_the_box(c, acts, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
     # ---- the test can see the feedback (oracle alone): closed- and open-loop d_init differ by more than 10 x the tolerance on at
     # least half of the full-length lanes
     init_cols = slice(T * ref.A, None)
-    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance(f1, smooth)[:, init_cols]
+    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance_per_lane(f1, smooth)[:, init_cols]
     full = length == T
     seen = float(gap.any(axis=1)[full].mean())
     assert seen >= 0.5, (key, seen)
@@ -310,7 +239,7 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     got = scaled(vs, c, *e.rollout_vjp_policy(T, **cotangents(vs, key, e)))
     assert e.error_count() == 0
     e.close()
-    bad, worst = within(got, f1, smooth)
+    bad, worst = within_per_lane(got, f1, smooth)
     print(f"{key}: not smooth {(~smooth).mean():.4f}, feedback seen on {seen:.2f} of the full lanes, bad share {bad:.2e}, "
           f"worst error / tolerance {worst:.3f}")
     assert bad <= 2e-3, (key, bad, worst)
@@ -335,9 +264,6 @@ def test_a_constant_policy_reduces_to_the_open_loop_sweep(vs, key):
 
 
 # ------------------------------------------------------------------------------------------------- 4. exact structure
-STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG")
-
-
 @pytest.mark.parametrize("key", ["qq-su", "qcp-su"])
 def test_exact_structure(vs, key):
     L = vs._lib
@@ -379,13 +305,13 @@ def test_exploration_noise_is_an_additive_constant(vs):
     offs = (act - (features(c["terms"], x) @ c["W"].astype(np.float64).T).reshape(T, N, ref.A)).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
     f1, f2, length, _, _ = reference(c, np.ascontiguousarray(offs))
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert (~smooth).mean() <= 0.01
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_policy(T, **cotangents(vs, key, e)))
     assert e.error_count() == 0
     e.close()
-    bad, worst = within(got, f1, smooth)
+    bad, worst = within_per_lane(got, f1, smooth)
     print(f"{key} + noise: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
     assert bad <= 2e-3, (bad, worst)
 
@@ -514,7 +440,7 @@ def test_autograd(vs, name):
     tc = torch_case(name)
     gw, gs, length = oracle_loss_gradients(name)
     for pair in (gw, gs):
-        assert (~smooth_of(*pair)).mean() <= 0.01
+        assert (~smooth_per_lane(*pair)).mean() <= 0.01
     env = getattr(vs, ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
     roll = vs.DifferentiablePolicyRollout(env, policy)
@@ -538,7 +464,7 @@ def test_autograd(vs, name):
     got_w = (g1[0].detach().cpu().numpy().astype(np.float64) * wscale).reshape(1, -1)
     got_s = g1[1].cpu().numpy().astype(np.float64) * np.array(INIT_SCALE[name])
     for what, got, (f1, f2) in (("weights", got_w, gw), ("init_states", got_s, gs)):
-        bad, worst = within(got, f1, smooth_of(f1, f2))
+        bad, worst = within_per_lane(got, f1, smooth_per_lane(f1, f2))
         print(f"{name} {what}: bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
         assert bad <= 2e-3, (name, what, bad, worst)
     # ---- two steps of plain gradient descent on the weights (in units of |W|) lower the oracle's loss

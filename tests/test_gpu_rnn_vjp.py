@@ -2,7 +2,7 @@
 vs_rollout_vjp_rnn / k_rollout_vjp_rnn: the reverse-mode sweep over CLOSED-LOOP recorded rollouts with a recurrent policy (Elman tanh /
 relu, GRU, LSTM of one or two layers) in the loop, VecSimEnv.rollout_vjp_rnn and DifferentiableRecurrentRollout.
 
-Shapes, scales and the tolerance rule are those of test_gpu_fnn_vjp.py / test_gpu_policy_vjp.py (whose helpers are imported): 150 lanes
+Shapes, scales and the tolerance rule are those of test_gpu_fnn_vjp.py / test_gpu_policy_vjp.py, all three from derivative_cases.py: 150 lanes
 (64 + 64 + 22), T = 24, max_steps = 50, +-5 % per-lane parameters, lanes 0 .. 9 end early, random cotangents on all FIVE inputs (g_rew,
 g_obs, g_act, g_state_last, g_hid_last); per lane 3e-3 |g| + 3e-4 max |g| against central differences of the fp64 closed loop at relative
 steps 1e-6 and 1e-5 (oracle.cpu_ref for the step, the NumPy cells of test_rnn_vjp_host.py for the policy).  The tolerance is taken
@@ -37,10 +37,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_policy_vjp as lin  # noqa: E402
 import test_rnn_vjp_host as cells  # noqa: E402  (the fp64 cells)
-from test_gpu_fnn_vjp import STATE_BUFFERS, TANH_OUT_AMP, TANH_OUT_AT, worst_of  # noqa: E402
-from test_gpu_policy_vjp import ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, T, dev, lengths_of, smooth_of, tolerance  # noqa: E402
+from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, TANH_OUT_AMP, TANH_OUT_AT,  # noqa: E402
+                              case_cotangents, check_net_keeps_the_box, dev, draw_params_and_init, frozen, lengths_of, record_mode2,
+                              smooth_per_lane, tolerance_per_lane, worst_of)
 
 # case -> (family, cell, layers, units, output nonlinearity, obs_idx, seed, gain of the output layer, whh)
 CASES = {
@@ -159,9 +159,7 @@ def case(key):
     name, cell, n_layers, H, output_nonlin, obs_idx, seed, gain, whh = {**CASES, **ELMAN_AS_FNN}[key]
     ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
     rng = np.random.default_rng(300 + seed)
-    nominal = ref.nominal_params(1).astype(np.float32)[0]
-    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
-    init = lin.edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
+    params, init = draw_params_and_init(ref, name, rng)
     h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
     net = make_rnn(ref, name, cell, n_layers, H, output_nonlin, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T,
                    gain, whh)
@@ -175,14 +173,10 @@ def case(key):
         while len(flat) < N_PAIRS:
             flat.add(int(rng.integers(T * Hs)))
         pairs = [(f // Hs, f % Hs) for f in sorted(flat)]
-    c = dict(name=name, ref=ref, params=params, init=init, h0=h0, net=net, Hs=Hs, pairs=tuple(pairs),
-             g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
-             g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32),
-             g_hid=rng.normal(size=(N, Hs)).astype(np.float32))
-    for v in c.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return c
+    return frozen(dict(name=name, ref=ref, params=params, init=init, h0=h0, net=net, Hs=Hs, pairs=tuple(pairs),
+                       g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
+                       g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32),
+                       g_hid=rng.normal(size=(N, Hs)).astype(np.float32)))
 
 
 def phi(c, state0, offs, length, reps=1, **kw):
@@ -265,7 +259,7 @@ def blocks_of(c):
 
 
 def block_tolerance(c, want, smooth):
-    return np.concatenate([tolerance(want[:, b], smooth[:, b]) for b in blocks_of(c)], axis=1)
+    return np.concatenate([tolerance_per_lane(want[:, b], smooth[:, b]) for b in blocks_of(c)], axis=1)
 
 
 def worst_in_blocks(c, got, want, smooth):
@@ -284,29 +278,20 @@ def recorded(vs, key, splits=(T,), noise_seed=0, net=None, spec=None, cap=T, noi
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(cap)
-    e.set_params(c["params"])
-    if spec is None:
-        set_rnn(e, c["net"] if net is None else net, noise_std)
-    else:  # what rnn_kernel_spec made of a torch policy
-        e.set_policy_rnn(**spec)
-        e.set_policy_hidden_record(c["Hs"])
-    e.reset(init_state=c["init"])
-    t0 = 0
-    for k in splits:
-        e.set_traj_offset(t0)
-        e.step_policy(k, record=True, noise_seed=noise_seed)
-        t0 += k
-    e.set_traj_offset(0)
-    return e
+
+    def policy(e):
+        if spec is None:
+            set_rnn(e, c["net"] if net is None else net, noise_std)
+        else:  # what rnn_kernel_spec made of a torch policy
+            e.set_policy_rnn(**spec)
+            e.set_policy_hidden_record(c["Hs"])
+
+    return record_mode2(e, cap, c["params"], policy, c["init"], splits, noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True, with_hid=True):
     c = case(key)
-    out = dict(g_rew=vs.lanes_last(dev(c["g_rew"]), e.ld), g_obs=vs.lanes_last(dev(c["g_obs"]), e.ld),
-               g_state_last=vs.lanes_last(dev(c["g_last"]), e.ld))
+    out = case_cotangents(vs, c, e)
     if with_act:
         out["g_act"] = vs.lanes_last(dev(c["g_act"]), e.ld)
     if with_hid:
@@ -321,14 +306,6 @@ def scaled(vs, c, d_act, d_init, d_hid, d_hid0):
     got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name]), d_hid0, picked], axis=1)
     assert np.isfinite(got).all()
     return got.astype(np.float64)
-
-
-def check_policy_keeps_the_box(c, acts, length):
-    name = c["name"]
-    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
-    a = np.abs(acts)
-    lo, hi = (0.51, 0.83) if c["net"]["output_nonlin"] == "tanh" else (0.30 * ACT_IN[name], 0.60 * ACT_IN[name])
-    assert (np.where(inside, a, lo) >= lo).all() and (np.where(inside, a, lo) <= hi).all(), name
 
 
 def check_no_unit_near_a_kink(c, pres, length):
@@ -355,9 +332,9 @@ def oracle_conditions(key):
     """everything the reference alone must meet (asserted before the GPU is asked) -> (c, f1, smooth, length, shares)"""
     c = case(key)
     f1, f2, length, acts, open_init, cut_init, pres = oracle_reference(key)
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert smooth.all(), (key, float((~smooth).mean()))  # every entry, none excluded
-    check_policy_keeps_the_box(c, acts, length)
+    check_net_keeps_the_box(c, acts, length)
     check_no_unit_near_a_kink(c, pres, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
     seen = shares(c, f1, smooth, open_init, cut_init, length)
@@ -411,7 +388,7 @@ def test_exploration_noise_is_an_additive_constant(vs):
     offs = (act - mean).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
     f1, f2, length = reference(c, np.ascontiguousarray(offs))[:3]
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert smooth.all()
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_rnn(T, **cotangents(vs, key, e)))
@@ -791,7 +768,7 @@ def test_autograd(vs, name):
     tc = torch_case(name)
     gw, gs, length = oracle_loss_gradients(name)
     for pair in (gw, gs):
-        assert smooth_of(*pair).all()
+        assert smooth_per_lane(*pair).all()
     cell, n_layers, H = AUTOGRAD[name][:3]
     env = getattr(vs, ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = cells.torch_policy(env.spec, cell, n_layers, H)
@@ -821,7 +798,7 @@ def test_autograd(vs, name):
     got_w = (flat_grad(g1[:-1]) * scale)[which].reshape(1, -1)
     got_s = g1[-1].cpu().numpy().astype(np.float64) * np.array(INIT_SCALE[name])
     for what, got, (f1, f2) in (("parameters", got_w, gw), ("init_states", got_s, gs)):
-        worst = worst_of(got, f1, smooth_of(f1, f2))
+        worst = worst_of(got, f1, smooth_per_lane(f1, f2))
         print(f"{name} {what}: worst error / tolerance {worst:.4f}")
         assert worst <= 1.0, (name, what, worst)
     # ---- two steps of plain gradient descent on the parameters (in units of |theta|) lower the oracle's loss; the step size moves no

@@ -16,21 +16,12 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import cpu_ref
-
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-FAMILIES = ["omo", "bob", "qq-su", "qcp-su", "pend", "qbb"]
-KW = {"omo": dict(dt=0.02), "bob": dict(dt=0.01), "qq-su": dict(dt=0.004), "qcp-su": dict(dt=0.002), "pend": dict(dt=0.01),
-      "qbb": dict(dt=0.01)}
-# action sizes strictly inside every lane's action box (and outside the dead zones): |a| in [0.3, 0.6] of these
-ACT_IN = {"omo": 10.0, "bob": 10.0, "qq-su": 4.0, "qcp-su": 5.0, "pend": 3.0, "qbb": 2.5}
-# full initial states well inside the state space: uniform in +- these
-INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
-              "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
-N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
+from derivative_cases import (ACT_IN, FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, case_cotangents, dev,  # noqa: E402
+                              frozen, lengths_of, oracle_rollout, playback_case, record_mode2, smooth_per_lane, within_per_lane)
 
 
 @pytest.fixture(scope="module")
@@ -42,59 +33,11 @@ def vs():
     return simurlacra_amd
 
 
-def edge_states(name, init):
-    """lanes 0 .. N_EDGE - 1 start at the edge of the state space, moving out: they end early"""
-    init = init.copy()
-    e = slice(0, N_EDGE)
-    if name == "qbb":
-        init[e, 2], init[e, 6] = 0.13, 0.45
-    elif name == "qq-su":
-        init[e, 0], init[e, 2] = 2.0, 5.0
-    elif name == "bob":
-        init[e, 0], init[e, 2] = 0.98, 3.0
-    elif name == "omo":
-        init[e, 0], init[e, 1] = 0.98, 5.0
-    elif name == "qcp-su":
-        init[e, 0], init[e, 2] = 0.25, 0.6
-    else:  # pend
-        init[e, 0], init[e, 1] = 12.5, 5.0
-    return init
-
-
 @functools.lru_cache(maxsize=None)
 def case(name):
     """the inputs of a family, all float32 and left unchanged by the tests: params [N, P], init [N, S], acts [N, T, A] and the
     cotangents g_rew [N, T], g_obs [N, T + 1, O], g_last [N, S + H]"""
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(23)
-    nominal = ref.nominal_params(1).astype(np.float32)[0]
-    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
-    init = edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
-    acts = (ACT_IN[name] * rng.uniform(0.3, 0.6, (N, T, ref.A)) * rng.choice([-1.0, 1.0], (N, T, ref.A))).astype(np.float32)
-    c = dict(ref=ref, params=params, init=init, acts=acts, g_rew=rng.normal(size=(N, T)).astype(np.float32),
-             g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
-    for v in c.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return c
-
-
-def oracle_rollout(ref, params, state0, hidden0, acts):
-    """the fp64 oracle along acts [N, T, A] (it does not freeze at done) -> states [T + 1, N, S], hiddens [T + 1, N, H],
-    obs [T + 1, N, O], rew [T, N], done [T, N]"""
-    st, hid = state0.copy(), hidden0.copy()
-    states, hiddens, obs, rew, done = [st], [hid], [ref.observe(st)], [], []
-    with np.errstate(all="ignore"):
-        for t in range(acts.shape[1]):
-            out = ref.step(st, hid, acts[:, t], params, np.full(st.shape[0], t))
-            st, hid = out["state"], out["hidden"]
-            states.append(st), hiddens.append(hid), obs.append(out["obs"]), rew.append(out["rew"]), done.append(out["done"])
-    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done)
-
-
-def lengths_of(done):
-    """[N]: 1 + the first step whose done flag is set, T if none is (done [T, N])"""
-    return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
+    return frozen(playback_case(name)[0])
 
 
 def phi(c, state0, hidden0, acts, length):
@@ -117,7 +60,7 @@ def oracle_reference(name):
     ref = c["ref"]
     s0, a0 = c["init"].astype(np.float64), c["acts"].astype(np.float64)
     h0 = ref.reset(c["params"].astype(np.float64), s0, True)["hidden"]
-    length = lengths_of(oracle_rollout(ref, c["params"].astype(np.float64), s0, h0, a0)[4])
+    length = lengths_of(oracle_rollout(ref, c["params"].astype(np.float64), s0, h0, a0).done)
     out = []
     for h in (1e-6, 1e-5):
         g = np.zeros((N, T * ref.A + ref.S))
@@ -134,47 +77,15 @@ def oracle_reference(name):
     return out[0], out[1], length
 
 
-def smooth_of(g1, g2):
-    mag = np.maximum(np.abs(g1), np.abs(g2))
-    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max(axis=1, keepdims=True))
-
-
-def within(got, want, smooth):
-    """the project's tolerance per lane on the smooth entries -> (share of bad entries, worst error / tolerance)"""
-    top = np.where(smooth, np.abs(want), 0.0).max(axis=1, keepdims=True)
-    tol = 3e-3 * np.abs(want) + 3e-4 * np.where(smooth.any(axis=1, keepdims=True), top, 1.0)
-    err = np.abs(got - want)
-    bad = smooth & (err > tol)
-    return float(bad.mean()), float((err[smooth] / tol[smooth]).max())
-
-
-def dev(x):
-    return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
-
-
 def recorded(vs, name, splits=(T,), acts=None, n=N):
     """a handle whose rows 0 .. T - 1 hold the playback rollouts of the case, recorded in mode 2 by step_policy in the given launches"""
     c = case(name)
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(T)
-    e.set_params(c["params"][:n])
-    e.set_policy_playback(c["acts"][:n] if acts is None else acts)
-    e.reset(init_state=c["init"][:n])
-    t0 = 0
-    for k in splits:
-        e.set_traj_offset(t0)
-        e.step_policy(k, record=True)
-        t0 += k
-    e.set_traj_offset(0)
-    return e
+    return record_mode2(e, T, c["params"][:n], lambda e: e.set_policy_playback(c["acts"][:n] if acts is None else acts), c["init"][:n], splits)
 
 
 def cotangents(vs, name, e, t_steps=T):
-    c = case(name)
-    return dict(g_rew=vs.lanes_last(dev(c["g_rew"][:e.n_envs, :t_steps]), e.ld),
-                g_obs=vs.lanes_last(dev(c["g_obs"][:e.n_envs, :t_steps + 1]), e.ld), g_state_last=vs.lanes_last(dev(c["g_last"][:e.n_envs]), e.ld))
+    return case_cotangents(vs, case(name), e, t_steps)
 
 
 def host(vs, d_act, d_init, n=N):
@@ -190,7 +101,7 @@ def test_against_the_fp64_oracle(vs, name):
     c = case(name)
     ref = c["ref"]
     f1, f2, length = oracle_reference(name)
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_per_lane(f1, f2)
     assert (~smooth).mean() <= 0.01, (name, float((~smooth).mean()))  # from the oracle alone
     e = recorded(vs, name)
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
@@ -200,7 +111,7 @@ def test_against_the_fp64_oracle(vs, name):
     e.close()
     got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
     assert np.isfinite(got).all()
-    bad, worst = within(got.astype(np.float64), f1, smooth)
+    bad, worst = within_per_lane(got.astype(np.float64), f1, smooth)
     print(f"{name}: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
     assert bad <= 2e-3, (name, bad, worst)
 
@@ -253,9 +164,6 @@ def test_against_chained_one_step_jacobians(vs, name):
 
 
 # ------------------------------------------------------------------------------------------------- 3. exact structure
-STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG")
-
-
 @pytest.mark.parametrize("name", ["qq-su", "qcp-su"])
 def test_exact_structure(vs, name):
     L = vs._lib

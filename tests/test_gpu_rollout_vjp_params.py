@@ -4,7 +4,8 @@ parameters next to it, VecSimEnv.rollout_vjp_params and DifferentiableRollout wi
 
 Shapes are those of test_gpu_trajectory_grad.py and test_gpu_rollout_vjp.py: 150 lanes (three waves, the last one partial), T = 24
 steps, max_steps = 50, one recording per lane with actions strictly inside the box and outside the dead zones, lanes 0 .. 9 start at
-the edge of the state space and end early, +-5 % per-lane parameters, the WRT index sets and the dts of test_gpu_trajectory_grad.py.
+the edge of the state space and end early, +-5 % per-lane parameters, the WRT index sets and the dts of test_gpu_trajectory_grad.py:
+all three files take them from derivative_cases.py, and the first two share the draws of their case() (playback_case).
 
 Derivatives are compared per unit RELATIVE change of a parameter (d / d log theta = theta d / d theta), which puts the columns of one
 family in one unit, with the project's tolerance (3e-3 |g| + 3e-4 max |g|, at most a 2e-3 share of bad entries; against the oracle on
@@ -22,24 +23,12 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import cpu_ref
-
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-FAMILIES = ["omo", "bob", "qq-su", "qcp-su", "pend", "qbb"]
-KW = {"omo": dict(dt=0.02), "bob": dict(dt=0.01), "qq-su": dict(dt=0.004), "qcp-su": dict(dt=0.002), "pend": dict(dt=0.01),
-      "qbb": dict(dt=0.01)}
-# action sizes strictly inside every lane's action box (and outside the dead zones): |a| in [0.3, 0.6] of these
-ACT_IN = {"omo": 10.0, "bob": 10.0, "qq-su": 4.0, "qcp-su": 5.0, "pend": 3.0, "qbb": 2.5}
-# the parameters differentiated (indices into vs_param_name): masses, lengths, motor constants, dampings -- none is 0 at nominal
-WRT = {"omo": [0, 1, 2], "bob": [0, 1, 3, 6], "qq-su": [1, 2, 6, 8], "qcp-su": [1, 8, 12, 13], "pend": [0, 1, 2, 3],
-       "qbb": [1, 4, 9, 10]}
-# full initial states well inside the state space: uniform in +- these
-INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
-              "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
-N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
+from derivative_cases import (FAMILIES, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, WRT, case_cotangents, dev, frozen,  # noqa: E402
+                              lengths_of, oracle_rollout, playback_case, record_mode2, smooth_global, within_global)
 
 
 @pytest.fixture(scope="module")
@@ -51,62 +40,16 @@ def vs():
     return simurlacra_amd
 
 
-def edge_states(name, init):
-    """lanes 0 .. N_EDGE - 1 start at the edge of the state space, moving out: they end early"""
-    init = init.copy()
-    e = slice(0, N_EDGE)
-    if name == "qbb":
-        init[e, 2], init[e, 6] = 0.13, 0.45
-    elif name == "qq-su":
-        init[e, 0], init[e, 2] = 2.0, 5.0
-    elif name == "bob":
-        init[e, 0], init[e, 2] = 0.98, 3.0
-    elif name == "omo":
-        init[e, 0], init[e, 1] = 0.98, 5.0
-    elif name == "qcp-su":
-        init[e, 0], init[e, 2] = 0.25, 0.6
-    else:  # pend
-        init[e, 0], init[e, 1] = 12.5, 5.0
-    return init
-
-
 @functools.lru_cache(maxsize=None)
 def case(name):
     """the inputs of a family, all float32 and left unchanged by the tests: params [N, P] (+-5 % per lane and parameter), init [N, S],
     acts [N, T, A], the cotangents g_rew [N, T], g_obs [N, T + 1, O], g_last [N, S + H], and for the forward-mode comparison the
     residuals resid [N, T + 1, O] (target = recorded observation - resid) and the weights [O]"""
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(23)
-    nominal = ref.nominal_params(1).astype(np.float32)[0]
-    params = (nominal[None, :] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (N, nominal.size)))).astype(np.float32)
-    init = edge_states(name, (rng.uniform(-1.0, 1.0, (N, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32))
-    acts = (ACT_IN[name] * rng.uniform(0.3, 0.6, (N, T, ref.A)) * rng.choice([-1.0, 1.0], (N, T, ref.A))).astype(np.float32)
-    c = dict(ref=ref, params=params, init=init, acts=acts, g_rew=rng.normal(size=(N, T)).astype(np.float32),
-             g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32),
-             resid=(rng.uniform(0.05, 0.15, (N, T + 1, ref.O)) * rng.choice([-1.0, 1.0], (N, T + 1, ref.O))).astype(np.float32),
-             weights=np.linspace(0.5, 2.0, ref.O).astype(np.float32))
-    for v in c.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return c
-
-
-def oracle_rollout(ref, params, state0, hidden0, acts):
-    """the fp64 oracle along acts [N, T, A] (it does not freeze at done) -> states [T + 1, N, S], hiddens [T + 1, N, H],
-    obs [T + 1, N, O], done [T, N]"""
-    st, hid = state0.copy(), hidden0.copy()
-    states, hiddens, obs, done = [st], [hid], [ref.observe(st)], []
-    with np.errstate(all="ignore"):
-        for t in range(acts.shape[1]):
-            out = ref.step(st, hid, acts[:, t], params, np.full(st.shape[0], t))
-            st, hid = out["state"], out["hidden"]
-            states.append(st), hiddens.append(hid), obs.append(out["obs"]), done.append(out["done"])
-    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(done)
-
-
-def lengths_of(done):
-    """[N]: 1 + the first step whose done flag is set, T if none is (done [T, N])"""
-    return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
+    c, rng = playback_case(name)
+    O = c["ref"].O
+    c["resid"] = (rng.uniform(0.05, 0.15, (N, T + 1, O)) * rng.choice([-1.0, 1.0], (N, T + 1, O))).astype(np.float32)
+    c["weights"] = np.linspace(0.5, 2.0, O).astype(np.float32)
+    return frozen(c)
 
 
 def phi(c, params, params0, state0, hidden0, acts, length):
@@ -114,7 +57,7 @@ def phi(c, params, params0, state0, hidden0, acts, length):
     rollout under `params`; the reward function keeps the constants of params0 (the convention: see the module docstring; a final
     reward is a constant of the branch taken and drops out of the differences)"""
     ref, n, Tn = c["ref"], state0.shape[0], acts.shape[1]
-    states, hiddens, obs, _ = oracle_rollout(ref, params, state0, hidden0, acts)
+    states, hiddens, obs, _, _ = oracle_rollout(ref, params, state0, hidden0, acts)
     with np.errstate(all="ignore"):
         rew = np.stack([ref.step_rew(states[t], acts[:, t], params0) for t in range(Tn)])
     k = np.arange(Tn + 1)[:, None]
@@ -134,7 +77,7 @@ def oracle_reference(name, t_steps=T):
     P0 = c["params"].astype(np.float64)
     s0, a0 = c["init"].astype(np.float64), c["acts"].astype(np.float64)[:, :t_steps]
     h0 = ref.reset(P0, s0, True)["hidden"]
-    length = lengths_of(oracle_rollout(ref, P0, s0, h0, a0)[3])
+    length = lengths_of(oracle_rollout(ref, P0, s0, h0, a0).done)
     out = []
     for h in (1e-6, 1e-5):
         g = np.zeros((N, len(WRT[name])))
@@ -147,48 +90,17 @@ def oracle_reference(name, t_steps=T):
     return out[0], out[1], length
 
 
-def smooth_of(g1, g2):
-    mag = np.maximum(np.abs(g1), np.abs(g2))
-    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max())
-
-
-def within(got, want, smooth=None):
-    """the project's tolerance on (smooth) entries -> (share of bad entries, worst error / tolerance)"""
-    smooth = np.ones(want.shape, dtype=bool) if smooth is None else smooth
-    tol = 3e-3 * np.abs(want) + 3e-4 * (np.abs(want[smooth]).max() if smooth.any() else 1.0)
-    err = np.abs(got - want)
-    bad = smooth & (err > tol)
-    return float(bad.mean()), float((err[smooth] / tol[smooth]).max()) if smooth.any() else 0.0
-
-
-def dev(x):
-    return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
-
-
 def recorded(vs, name, splits=(T,), n=N, t_steps=T):
     """a handle whose rows 0 .. t_steps - 1 hold the playback rollouts of the case, recorded in mode 2 by step_policy in the given
     launches"""
     c = case(name)
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-    e.set_auto_reset(False)
-    e.set_record_mode(2)
-    e.set_traj_capacity(t_steps)
-    e.set_params(c["params"][:n])
-    e.set_policy_playback(c["acts"][:n, :max(t_steps, 2)])
-    e.reset(init_state=c["init"][:n])
-    t0 = 0
-    for k in splits:
-        e.set_traj_offset(t0)
-        e.step_policy(k, record=True)
-        t0 += k
-    e.set_traj_offset(0)
-    return e
+    acts = c["acts"][:n, :max(t_steps, 2)]
+    return record_mode2(e, t_steps, c["params"][:n], lambda e: e.set_policy_playback(acts), c["init"][:n], splits)
 
 
 def cotangents(vs, name, e, t_steps=T):
-    c = case(name)
-    return dict(g_rew=vs.lanes_last(dev(c["g_rew"][:e.n_envs, :t_steps]), e.ld),
-                g_obs=vs.lanes_last(dev(c["g_obs"][:e.n_envs, :t_steps + 1]), e.ld), g_last=vs.lanes_last(dev(c["g_last"][:e.n_envs]), e.ld))
+    return case_cotangents(vs, case(name), e, t_steps, last="g_last")
 
 
 def per_log_theta(vs, name, d_params, n=N, wrt=None):
@@ -231,7 +143,7 @@ def test_against_the_forward_mode_sensitivities(vs, name):
     want = f.rollout_grad().cpu().numpy().astype(np.float64) * c["params"][:, WRT[name]].astype(np.float64)
     f.close()
     assert np.isfinite(got).all() and want.any(axis=1).all()
-    bad, worst = within(got, want)
+    bad, worst = within_global(got, want)
     print(f"{name}: against forward mode: bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
     assert bad < 2e-3, (name, bad, worst)
 
@@ -239,7 +151,7 @@ def test_against_the_forward_mode_sensitivities(vs, name):
 # ----------------------------------------------------------------------------------------- 2. against the fp64 oracle
 def against_oracle(vs, name, n=N, t_steps=T):
     f1, f2, length = oracle_reference(name, t_steps)
-    smooth = smooth_of(f1, f2)
+    smooth = smooth_global(f1, f2)
     assert smooth.mean() > 0.9, (name, float(smooth.mean()))  # from the oracle alone
     e = recorded(vs, name, splits=(t_steps,), n=n, t_steps=t_steps)
     assert np.array_equal(e.rollout_lengths(n, t_steps)[0].cpu().numpy(), length[:n])
@@ -248,7 +160,7 @@ def against_oracle(vs, name, n=N, t_steps=T):
     assert e.error_count() == 0 and not dp[:, n:].any()
     e.close()
     assert np.isfinite(got).all()
-    bad, worst = within(got, f1[:n], smooth[:n])
+    bad, worst = within_global(got, f1[:n], smooth[:n])
     print(f"{name} n = {n} T = {t_steps}: smooth {smooth.mean():.3f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
     assert bad < 2e-3, (name, n, t_steps, bad, worst)
     return length
@@ -269,8 +181,7 @@ def test_one_step_one_lane_and_a_second_wave_of_one_lane(vs, name, n, t_steps):
 
 
 # ------------------------------------------------------------------------------------------------- 3. exact structure
-STATE_BUFFERS = ("VS_STATE", "VS_HIDDEN", "VS_OBS", "VS_STEPCOUNT", "VS_DONE", "VS_REW", "VS_RETURNS", "VS_FAILED", "VS_ERRFLAG",
-                 "VS_EPSTAT_COUNT", "VS_EPSTAT_RETSUM", "VS_EPSTAT_LENSUM", "VS_PARAMS", "VS_CONSTS")
+ALL_BUFFERS = STATE_BUFFERS + ("VS_EPSTAT_COUNT", "VS_EPSTAT_RETSUM", "VS_EPSTAT_LENSUM", "VS_PARAMS", "VS_CONSTS")
 
 
 @pytest.mark.parametrize("name", ["qq-su", "qcp-su", "qbb"])
@@ -287,7 +198,7 @@ def test_exact_structure(vs, name):
     e.step_policy(T)
 
     def snapshot():
-        bufs = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
+        bufs = [e.get(getattr(L, b)).copy() for b in ALL_BUFFERS]
         tt = e.traj_tensors(T)
         bufs += [tt["rec"].clone().cpu().numpy(), tt["done"].clone().cpu().numpy(), e.rollout_loss().clone().cpu().numpy(), e.rollout_grad().clone().cpu().numpy(),
                  e.rollout_gn().clone().cpu().numpy(), e.get(L.VS_ROLLOUT_SENS).copy()]
