@@ -1,11 +1,12 @@
 """
 What the GPU tests of the derivative kernels share (test_gpu_rollout_vjp*, test_gpu_trajectory_grad, test_gpu_policy_vjp, test_gpu_fnn_vjp,
-test_gpu_rnn_vjp, test_gpu_fnn_param_grad): the families' tables and shapes, the edge lanes, the fp64 open-loop rollout, the mode-2
-recording launch loop, the playback cotangents and the project's tolerance.  Not a test module: import it by bare name.
+test_gpu_rnn_vjp, test_gpu_fnn_param_grad, test_gpu_param_derivatives_all): the families' tables and shapes, the edge lanes, the fp64
+open-loop rollout, the all-parameter oracle, the mode-2 recording launch loop, the playback cotangents and the project's tolerance.
+Not a test module: import it by bare name.
 
 The project's tolerance (test_step_jacobians_against_finite_differences) is 3e-3 |g| + 3e-4 max |g_smooth|, an entry smooth where the
 central differences of the fp64 oracle at relative steps 1e-6 and 1e-5 agree to 1e-4.  `max |g_smooth|` needs entries of ONE unit, and
-the derivative tests have two kinds of arrays, hence two rules -- both intended, neither a special case of the other:
+the derivative tests have three kinds of arrays, hence three rules -- all intended, none a special case of another:
 
   * per lane (smooth_per_lane, tolerance_per_lane, within_per_lane, worst_of): gradients with respect to action and state columns,
     [N, T A + S (+ hidden entries)], each column scaled by ACT_IN / INIT_SCALE.  The lanes differ by orders of magnitude (an edge lane
@@ -13,9 +14,17 @@ the derivative tests have two kinds of arrays, hence two rules -- both intended,
     test_gpu_rollout_vjp, test_gpu_policy_vjp, test_gpu_fnn_vjp, test_gpu_rnn_vjp (the last per block of columns).
   * global (smooth_global, within_global): derivatives per unit relative change of a domain parameter, d / d log theta, [N, G] and
     [N, G, G].  That unit is one per FAMILY -- the +-5 % lanes are of one size -- so there is one maximum over the whole array; without a
-    mask every entry counts, and with nothing smooth the result is (0.0, 0.0).  Users: test_gpu_rollout_vjp_params,
-    test_gpu_trajectory_grad.
+    mask every entry counts, and with nothing smooth the result is (0.0, 0.0).  Right for a handful of columns of similar size (the
+    WRT sets).  Users: test_gpu_rollout_vjp_params, test_gpu_trajectory_grad.
+  * per column (smooth_per_column, within_per_column): derivatives with respect to EVERY domain parameter of a family, [N, P], each
+    column per PARAM_UNIT of its parameter (|theta|, or 0.1 where theta = 0: the angle offsets and volt thresholds that are 0 at
+    nominal).  The columns of one family differ by three orders of magnitude (a damping against a length), so a floor of 3e-4 of the
+    family's largest column lets a small column be wrong by tens of per cent; the maximum is taken over a column's own smooth entries
+    instead, the lanes of a column being of one size.  The coefficients are the same.  Columns the oracle holds (almost) at zero have
+    no unit of their own: null_columns() finds them, NULL_COLUMNS says why each is one, and their callers check them apart.  Right
+    whenever the columns are not hand-picked.  Users: test_gpu_param_derivatives_all, test_param_derivative_columns_host.
 """
+import functools
 from typing import NamedTuple
 
 import numpy as np
@@ -91,6 +100,25 @@ def playback_case(name):
     return c, rng
 
 
+@functools.lru_cache(maxsize=None)
+def params_case(name):
+    """the inputs of a family's domain-parameter derivative tests, all float32 and left unchanged by the tests: playback_case(name),
+    and for the forward-mode comparison the residuals resid [N, T + 1, O] (target = recorded observation - resid) and the weights [O]"""
+    c, rng = playback_case(name)
+    O = c["ref"].O
+    c["resid"] = (rng.uniform(0.05, 0.15, (N, T + 1, O)) * rng.choice([-1.0, 1.0], (N, T + 1, O))).astype(np.float32)
+    c["weights"] = np.linspace(0.5, 2.0, O).astype(np.float32)
+    return frozen(c)
+
+
+def PARAM_UNIT(name, params):
+    """[N, P] float64: the unit a family's domain-parameter derivatives are compared in and its finite differences step by, per lane
+    and parameter: |theta|, or 0.1 where theta = 0 (0.1 rad for the angle offsets ang_offset, offset_th_x / _y, 0.1 V for the volt
+    thresholds of qq / qcp; `name` is the family, for the caller's record: the rule is the same for all six)"""
+    th = np.abs(np.asarray(params, dtype=np.float64))
+    return np.where(th != 0.0, th, 0.1)
+
+
 # ------------------------------------------------------------------------------------------------------- the fp64 oracle
 class Rollout(NamedTuple):
     states: np.ndarray   # [T + 1, N, S]
@@ -115,6 +143,76 @@ def oracle_rollout(ref, params, state0, hidden0, acts):
 def lengths_of(done):
     """[N]: 1 + the first step whose done flag is set, T if none is (done [T, N])"""
     return np.where(done.any(axis=0), done.argmax(axis=0) + 1, done.shape[0])
+
+
+def phi_and_obs(c, params, params0, state0, hidden0, acts, length):
+    """([n]: sum g_rew r + sum g_obs . obs + g_last . (s_L, h_L) of every lane over its first length[n] steps (fp64 oracle) along the
+    rollout under `params`, and the observations [T + 1, n, O] of that rollout).  The reward function keeps the constants of params0
+    (the project's convention, vecsim_envs.h: the reward FUNCTION, the bounds of the spaces, the initial state and the initial hidden
+    state are constants with respect to the parameters; a final reward is a constant of the branch taken and drops out of the
+    differences)"""
+    ref, n, Tn = c["ref"], state0.shape[0], acts.shape[1]
+    states, hiddens, obs, _, _ = oracle_rollout(ref, params, state0, hidden0, acts)
+    with np.errstate(all="ignore"):
+        rew = np.stack([ref.step_rew(states[t], acts[:, t], params0) for t in range(Tn)])
+    k = np.arange(Tn + 1)[:, None]
+    out = (np.where(k[:Tn] < length[None, :], c["g_rew"][:n, :Tn].T.astype(np.float64) * rew, 0.0)).sum(axis=0)
+    out += np.where((k <= length[None, :])[:, :, None], c["g_obs"][:n, :Tn + 1].transpose(1, 0, 2).astype(np.float64) * obs, 0.0).sum(axis=(0, 2))
+    last = np.concatenate([states[length, np.arange(n)], hiddens[length, np.arange(n)]], axis=1)
+    return out + (c["g_last"][:n].astype(np.float64) * last).sum(axis=1), obs
+
+
+def phi(c, params, params0, state0, hidden0, acts, length):
+    return phi_and_obs(c, params, params0, state0, hidden0, acts, length)[0]
+
+
+class ParamOracle(NamedTuple):
+    f1: np.ndarray      # [N, P]: d Phi / d theta_j per PARAM_UNIT, central differences at h = 1e-6
+    f2: np.ndarray      # [N, P]: the same at h = 1e-5
+    gn1: np.ndarray     # [N, P]: sum over rows 1 .. length and q of w_q (d obs_q / d theta_j)^2 per PARAM_UNIT^2, at h = 1e-6
+    gn2: np.ndarray     # [N, P]: the same at h = 1e-5
+    disc1: np.ndarray   # [N, P]: sum over the same rows of 2 w_q resid_q d obs_q / d theta_j per PARAM_UNIT, at h = 1e-6: the gradient of
+    disc2: np.ndarray   # the weighted squared discrepancy against target = obs - resid; [N, P]: the same at h = 1e-5
+    length: np.ndarray  # [N]: the oracle's lane lengths
+    unit: np.ndarray    # [N, P]: PARAM_UNIT of the case's parameters
+
+
+@functools.lru_cache(maxsize=None)
+def all_param_oracle(name):
+    """Central differences of Phi (phi_and_obs, the cotangents of params_case(name)) with respect to EVERY domain parameter of every
+    lane, the step h PARAM_UNIT ADDED to the parameter (a relative step cannot move a zero), h = 1e-6 and 1e-5, per PARAM_UNIT; and
+    from the same perturbed rollouts the gradient and the diagonal of the Gauss-Newton matrix of the weighted squared discrepancy
+    against the target obs - resid under the case's weights.  The initial
+    hidden state comes from the oracle's reset under the unperturbed parameters and is held; a lane's length is held at its
+    unperturbed value (the branch taken); the actions lie strictly inside every lane's box, so a moved bound changes nothing."""
+    c = params_case(name)
+    ref = c["ref"]
+    P0 = c["params"].astype(np.float64)
+    s0, a0 = c["init"].astype(np.float64), c["acts"].astype(np.float64)
+    h0 = ref.reset(P0, s0, True)["hidden"]
+    length = lengths_of(oracle_rollout(ref, P0, s0, h0, a0).done)
+    unit = PARAM_UNIT(name, P0)
+    summed = ((np.arange(T + 1)[:, None] >= 1) & (np.arange(T + 1)[:, None] <= length[None, :]))[:, :, None]  # [T + 1, N, 1]
+    w = c["weights"].astype(np.float64)[None, None, :]
+    resid = c["resid"].astype(np.float64).transpose(1, 0, 2)  # [T + 1, N, O]
+    out = []
+    for h in (1e-6, 1e-5):
+        g, gn, disc = np.zeros(P0.shape), np.zeros(P0.shape), np.zeros(P0.shape)
+        for pj in range(P0.shape[1]):
+            lo, hi = P0.copy(), P0.copy()
+            hi[:, pj] += h * unit[:, pj]
+            lo[:, pj] -= h * unit[:, pj]
+            (f_hi, o_hi), (f_lo, o_lo) = phi_and_obs(c, hi, P0, s0, h0, a0, length), phi_and_obs(c, lo, P0, s0, h0, a0, length)
+            g[:, pj] = (f_hi - f_lo) / (2.0 * h)
+            J = np.where(summed, (o_hi - o_lo) / (2.0 * h), 0.0)
+            gn[:, pj] = (w * J * J).sum(axis=(0, 2))
+            disc[:, pj] = (2.0 * w * resid * J).sum(axis=(0, 2))
+        out.append((g, gn, disc))
+    (g1, gn1, disc1), (g2, gn2, disc2) = out
+    o = ParamOracle(g1, g2, gn1, gn2, disc1, disc2, length, unit)
+    for a in o:
+        a.setflags(write=False)
+    return o
 
 
 def action_window(name, output_nonlin):
@@ -209,3 +307,52 @@ def within_global(got, want, smooth=None):
     err = np.abs(got - want)
     bad = smooth & (err > tol)
     return float(bad.mean()), float((err[smooth] / tol[smooth]).max()) if smooth.any() else 0.0
+
+
+# -------------------------------------------------------------------------------------- the tolerance, one unit per column
+# The columns of an all-parameter array that the oracle holds at (almost) zero, and why.  "exact": the parameter reaches only code
+# that runs on float values -- a dead-zone comparison, the bounds of the action or state box -- so no tangent ever leaves
+# calc_consts<Dual>: the device column is 0.0 in every lane.  "cancels": the parameter drops out analytically and fp32 tangents
+# leave rounding noise: the device column stays below CANCEL_FLOOR x the maximum of the family's smallest non-null column.
+NULL_COLUMNS = {
+    "omo": {},
+    "bob": {2: ("cancels", "ball_radius: zeta_ball = m + J_ball / r^2 with J_ball = 2/5 m r^2, r^2 cancels (C_INV_ZETA_BALL is its only use)")},
+    "qq-su": {9: ("exact", "voltage_thold_neg: C_TH_NEG is read by dead_zone's comparison alone"),
+              10: ("exact", "voltage_thold_pos: C_TH_POS is read by dead_zone's comparison alone")},
+    "qcp-su": {2: ("exact", "rail_length: C_XMAX and C_XDMAX, the state box, and nothing in f_dyn"),
+               15: ("exact", "voltage_thold_neg: C_TH_NEG is read by f_dyn's dead-zone comparison alone"),
+               16: ("exact", "voltage_thold_pos: C_TH_POS is read by f_dyn's dead-zone comparison alone")},
+    "pend": {4: ("exact", "torque_thold: C_AMAX, the action box, and nothing in dynamics")},
+    "qbb": {14: ("exact", "voltage_thold_x_pos: C_TXP is read by dead_zone's comparison alone"),
+            15: ("exact", "voltage_thold_x_neg: C_TXN is read by dead_zone's comparison alone"),
+            16: ("exact", "voltage_thold_y_pos: C_TYP is read by dead_zone's comparison alone"),
+            17: ("exact", "voltage_thold_y_neg: C_TYN is read by dead_zone's comparison alone")},
+}
+NULL_BELOW, CANCEL_FLOOR = 1e-8, 3e-4
+
+
+def null_columns(f1, f2):
+    """[P] bool: the columns whose largest entry is below NULL_BELOW of the array's largest at both step sizes"""
+    top1, top2 = np.abs(f1).max(axis=0), np.abs(f2).max(axis=0)
+    return (top1 < NULL_BELOW * top1.max()) & (top2 < NULL_BELOW * top2.max())
+
+
+def smooth_per_column(g1, g2):
+    mag = np.maximum(np.abs(g1), np.abs(g2))
+    return np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max(axis=0, keepdims=True))
+
+
+def tolerance_per_column(want, smooth):
+    """[N, P]: 3e-3 |g| + 3e-4 x the largest smooth entry of the column (a column without one: an error, not a floor)"""
+    if not smooth.any(axis=0).all():
+        raise ValueError(f"no smooth entry in columns {np.flatnonzero(~smooth.any(axis=0)).tolist()}")
+    return 3e-3 * np.abs(want) + 3e-4 * np.where(smooth, np.abs(want), 0.0).max(axis=0, keepdims=True)
+
+
+def within_per_column(got, want, smooth):
+    """the project's tolerance per column on the smooth entries of [N, P] arrays -> (share of bad entries over the whole array, [P]:
+    worst error / tolerance of every column)"""
+    tol = tolerance_per_column(want, smooth)
+    err = np.abs(got - want)
+    bad = smooth & (err > tol)
+    return float(bad.mean()), np.where(smooth, err / tol, 0.0).max(axis=0)

@@ -27,8 +27,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (FAMILIES, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, WRT, case_cotangents, dev, frozen,  # noqa: E402
-                              lengths_of, oracle_rollout, playback_case, record_mode2, smooth_global, within_global)
+from derivative_cases import (FAMILIES, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, WRT, case_cotangents, dev,  # noqa: E402
+                              lengths_of, oracle_rollout, params_case, phi, record_mode2, smooth_global, within_global)
 
 
 @pytest.fixture(scope="module")
@@ -40,31 +40,7 @@ def vs():
     return simurlacra_amd
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """the inputs of a family, all float32 and left unchanged by the tests: params [N, P] (+-5 % per lane and parameter), init [N, S],
-    acts [N, T, A], the cotangents g_rew [N, T], g_obs [N, T + 1, O], g_last [N, S + H], and for the forward-mode comparison the
-    residuals resid [N, T + 1, O] (target = recorded observation - resid) and the weights [O]"""
-    c, rng = playback_case(name)
-    O = c["ref"].O
-    c["resid"] = (rng.uniform(0.05, 0.15, (N, T + 1, O)) * rng.choice([-1.0, 1.0], (N, T + 1, O))).astype(np.float32)
-    c["weights"] = np.linspace(0.5, 2.0, O).astype(np.float32)
-    return frozen(c)
-
-
-def phi(c, params, params0, state0, hidden0, acts, length):
-    """[n]: sum g_rew r + sum g_obs . obs + g_last . (s_L, h_L) of every lane over its first length[n] steps (fp64 oracle) along the
-    rollout under `params`; the reward function keeps the constants of params0 (the convention: see the module docstring; a final
-    reward is a constant of the branch taken and drops out of the differences)"""
-    ref, n, Tn = c["ref"], state0.shape[0], acts.shape[1]
-    states, hiddens, obs, _, _ = oracle_rollout(ref, params, state0, hidden0, acts)
-    with np.errstate(all="ignore"):
-        rew = np.stack([ref.step_rew(states[t], acts[:, t], params0) for t in range(Tn)])
-    k = np.arange(Tn + 1)[:, None]
-    out = (np.where(k[:Tn] < length[None, :], c["g_rew"][:n, :Tn].T.astype(np.float64) * rew, 0.0)).sum(axis=0)
-    out += np.where((k <= length[None, :])[:, :, None], c["g_obs"][:n, :Tn + 1].transpose(1, 0, 2).astype(np.float64) * obs, 0.0).sum(axis=(0, 2))
-    last = np.concatenate([states[length, np.arange(n)], hiddens[length, np.arange(n)]], axis=1)
-    return out + (c["g_last"][:n].astype(np.float64) * last).sum(axis=1)
+case = params_case  # (shared with test_gpu_param_derivatives_all: the same draws)
 
 
 @functools.lru_cache(maxsize=None)
