@@ -558,6 +558,26 @@ int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
  * the policy's Hs (VS_ERR_STATE). */
 int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0);
+/* The parameter gradient that vs_rollout_vjp_rnn leaves to the caller, as one device pass over the same records:
+ *     d_params[q] = sum over the rows t < L of every lane i < n_envs of (d F / d theta_q)(x_t, p_t)^T (abar_t, d_hid[t])
+ * for the handle's current recurrent policy (all four cells, one or two layers), i.e. per row and layer
+ *     dW_ih += delta x^T, dW_hh += delta h^T, db_ih += delta, db_hh += delta;   dW_out += delta_out h'_top^T, db_out += delta_out
+ * with the gates recomputed at the recorded (x_t, p_t) with the rollout kernel's expressions and the deltas formed as in
+ * vs_rollout_vjp_rnn (GRU: W_hn and b_hn take delta_n r, W_in and b_in delta_n; LSTM: the cell adjoint is d_hid's c part; two layers:
+ * the adjoint of layer 0's h' is its d_hid part plus layer 1's W_ih^T delta).  x_t is the RECORDED observation of row t through obs_idx,
+ * p_t row t of VS_POLICY_HIDDEN_REC, L the lane's length as vs_rollout_vjp takes it.
+ *   abar      [t_steps][A][ld]    device: d_act as vs_rollout_vjp_rnn returned it (ld = vs_ld(h))
+ *   d_hid     [t_steps][Hs][ld]   device: d_hid as vs_rollout_vjp_rnn returned it.  Of both, and of the hidden-state record, rows
+ *                                 t >= L, lanes >= n_envs and anything behind row t_steps are never read into the arithmetic: they
+ *                                 may hold anything, NaN included
+ *   d_params  [n_params]          device, out: the gradient in the order of the parameter vector vs_set_policy_rnn took;
+ *                                 accumulate != 0: added to what is there, one fp32 add per entry
+ * Runs on the handle's stream and writes nothing of the handle.  The sum is deterministic: no atomics, every partial sum is added in
+ * a fixed order that depends on (ld, t_steps, device) only, so two calls on the same inputs return the same bits.  A workspace for
+ * the partial sums belongs to the policy on the handle: allocated at the first call, freed when the policy is replaced or removed.
+ * Refused with nothing written: everything vs_rollout_vjp_rnn refuses, with the same codes; NULL abar, d_hid or d_params, n_params
+ * other than the policy's parameter count, more than 2^31 - 1 tiles of 64 lanes x one step (VS_ERR_ARG). */
+int vs_rnn_param_grad(vs_handle h, int t_steps, const float* abar, const float* d_hid, float* d_params, int64_t n_params, int accumulate);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

@@ -548,8 +548,9 @@ static int drop_fnn(vs_handle h) {
 }
 
 static int drop_rnn(vs_handle h) {
-    if (int rc = dfree(h, h->rnn.w, h->rnn.hid)) return rc;
+    if (int rc = dfree(h, h->rnn.w, h->rnn.hid, h->rnn_pg_part, h->rnn_pg_map)) return rc;  // (the workspace of vs_rnn_param_grad too)
     h->rnn = Rnn{};
+    h->rnn_pg_wgs = 0;
     return VS_OK;
 }
 
@@ -633,7 +634,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 316; }
+int vs_version(void) { return 317; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1791,6 +1792,66 @@ int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float
     return VS_OK;
 }
 
+// what vs_rollout_vjp_rnn and vs_rnn_param_grad need of the policy slot
+static const char* rnn_sweep_policy(vs_handle h) {
+    if (!h->rnn.w) return "no recurrent policy on the handle (vs_set_policy_rnn)";
+    if (h->pop.w) return "not available with a policy population on the handle";
+    if (!h->d_hrec || h->hrec_width != h->rnn.hs)
+        return "needs the hidden-state record plane at the policy's hidden size (vs_set_policy_hidden_record)";
+    return nullptr;
+}
+
+// workgroups of k_rnn_param_grad: a function of (ld, t_steps, device) only -- a workgroup per tile while there are fewer tiles than
+// compute units (the LDS rows of a wide cell leave room for one workgroup on each), else one per compute unit, each a run of tiles
+static int rnn_param_grad_wgs(const vs_env* h, int t_steps) {
+    return (int)std::min<int64_t>((int64_t)(h->d.ld / 64) * t_steps, (int64_t)h->n_cu);
+}
+
+// (k_fnn_param_reduce, launched where vs_fnn_param_grad is: the kernels keep their order in the code object)
+static void launch_param_reduce(vs_handle h, const float* part, int n_wg, int psize, const int* map, float* d_params, int accumulate);
+
+int vs_rnn_param_grad(vs_handle h, int t_steps, const float* abar, const float* d_hid, float* d_params, int64_t n_params,
+                      int accumulate) {
+    const char* who = "vs_rnn_param_grad";
+    if (int rc = vjp_checks(h, who, t_steps, abar, d_params, rnn_sweep_policy, "NULL handle, abar or d_params")) return rc;
+    if (!d_hid) return fail(h, VS_ERR_ARG, who, "NULL d_hid");
+    if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, who, "n_params is not the parameter count of the policy on the handle");
+    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    Rnn P = h->rnn;
+    P.hrec = h->d_hrec;
+    const EnvInfo& ei = ENV_INFO[h->type];
+    const int psize = (int)h->pol_map.size(), n_wg = rnn_param_grad_wgs(h, t_steps), G = rnn_gates(P.cell);
+    if (psize != P.off_o + ei.A * P.hp + 4 || P.hp > RNN_MAXW || P.n_layers > RNN_MAXL)
+        return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_rnn's");
+    HIPCHK(h, hipSetDevice(h->device));
+    // ---- the workspace belongs to the policy on the handle: first use, or a grid larger than every one before
+    if (!h->rnn_pg_map) {
+        int* map = nullptr;
+        HIPCHK(h, hipMalloc((void**)&map, (size_t)psize * sizeof(int)));
+        hipError_t e = hipMemcpy(map, h->pol_map.data(), (size_t)psize * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
+        h->rnn_pg_map = map;
+    }
+    if (n_wg > h->rnn_pg_wgs) {
+        if (h->rnn_pg_part) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
+        if (int rc = dfree(h, h->rnn_pg_part)) return rc;
+        h->rnn_pg_wgs = 0;
+        HIPCHK(h, hipMalloc((void**)&h->rnn_pg_part, (size_t)n_wg * psize * sizeof(float)));
+        h->rnn_pg_wgs = n_wg;
+    }
+    const FnnRows rows{h->d.traj_rec, h->d.traj_done, record_width(h->type, 2), ei.O, ei.A, h->d.n, h->d.ld};
+    const size_t lds = rnng_lds_floats(G, P.n_layers, P.hp, ei.A) * sizeof(float);
+    auto kern = G == 1 ? k_rnn_param_grad<1> : G == 3 ? k_rnn_param_grad<3> : k_rnn_param_grad<4>;
+    // beyond the 64 KiB a kernel gets by default the limit is raised; refused, there is no launch
+    if (lds > 64 * 1024)
+        HIPCHK(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * RNNG_WAVES), lds, h->stream, rows, abar, d_hid, P, t_steps, psize,
+                       h->rnn_pg_part);
+    launch_param_reduce(h, h->rnn_pg_part, n_wg, psize, h->rnn_pg_map, d_params, accumulate);
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
 // workgroups of k_fnn_param_grad: a function of (ld, t_steps, device) only, so that the bits of a result do not depend on earlier
 // calls -- a wave per tile while there are fewer tiles than wave slots, else two workgroups per compute unit, each wave a run of tiles
 static int fnn_param_grad_wgs(const vs_env* h, int t_steps) {
@@ -1834,16 +1895,14 @@ int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
     return VS_OK;
 }
 
+static void launch_param_reduce(vs_handle h, const float* part, int n_wg, int psize, const int* map, float* d_params, int accumulate) {
+    hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream, part, n_wg, psize,
+                       map, d_params, accumulate != 0 ? 1 : 0);
+}
+
 int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0) {
-    const auto policy = [](vs_handle h) -> const char* {
-        if (!h->rnn.w) return "no recurrent policy on the handle (vs_set_policy_rnn)";
-        if (h->pop.w) return "not available with a policy population on the handle";
-        if (!h->d_hrec || h->hrec_width != h->rnn.hs)
-            return "needs the hidden-state record plane at the policy's hidden size (vs_set_policy_hidden_record)";
-        return nullptr;
-    };
-    if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, policy)) return rc;
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, rnn_sweep_policy)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
     DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_rnn(h, v, g_act, g_hid_last, d_hid, d_hid0, t_steps));

@@ -19,6 +19,7 @@
 //   k_rollout_vjp_fnn  vs_rollout_vjp_fnn     ... with the handle's feed-forward network of one or two hidden layers in the loop
 //   k_rollout_vjp_rnn  vs_rollout_vjp_rnn     ... with the handle's recurrent policy in the loop (a second adjoint for its hidden state)
 //   k_fnn_param_grad / k_fnn_param_reduce  vs_fnn_param_grad   the network's parameter gradients from the records and the sweep's d_act
+//   k_rnn_param_grad (+ k_fnn_param_reduce)  vs_rnn_param_grad  the recurrent policy's, from the records, the sweep's d_act and d_hid
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -3575,6 +3576,332 @@ __global__ __launch_bounds__(64) void k_rollout_vjp_rnn(Task T, Dev d, Vjp V, co
                 d_hid0[(size_t)p * ld + i] = q < Ln ? adj[(q * hp + j) * 64] : cadj[((q - Ln) * hp + j) * 64];
 }
 
+// ----------------------------------------------------------------------------- parameter gradients of a recurrent policy
+// vs_rnn_param_grad: what the sweep above leaves to the caller -- d Phi / d theta = sum over the rows (t < L_i, i < n) of
+//     dW_ih += delta x^T   dW_hh += delta h^T   db_ih, db_hh += delta   (per layer)        dW_out += delta_out h'_top^T   db_out += delta_out
+// with abar = the sweep's d_act and d_hid = the sweep's d_hid (the total cotangent of p_{t+1}, step t's output layer not included),
+// the gates recomputed by rnn_unit_act at the recorded (x_t, p_t) and the deltas formed with k_rollout_vjp_rnn's expressions.  No
+// chain in time: every (t, env) row is independent, so the launch fills the chip.  The input row is the RECORDED observation
+// through obs_idx, as in k_fnn_param_grad, so the kernel needs nothing of the family: one instantiation per gate count.
+//   * A workgroup of RNNG_WAVES = 8 waves owns a contiguous run of tiles (64 lanes x one step, lane-group major; L once per lane
+//     group).  A tile no lane reaches is skipped before its loads.  Per tile, two kinds of phases between workgroup barriers:
+//       - lane = env, the units of a layer dealt round-robin to the waves, weights as scalar operands (the sweep's shape): load
+//         x_t, h_t, abar (only where t < L and i < n: everything else is zero by select, never read); forward, layer by layer, to
+//         h'_top (dW_out needs it) and y_out; then, top layer first, per unit: recompute, deltas, one LDS row [64 envs] per gate.
+//         The GRU keeps a fourth row delta_n r (what W_hn, b_hn take); the LSTM's cell adjoint is d_hid's c part.  With two
+//         layers the adjoint of layer 0's h' is its d_hid part plus layer 1's W_ih^T delta, gathered from layer 1's delta rows in the
+//         sweep's order (unit, then gate) by the wave that owns the unit.
+//       - lane = unit, wave = a set of columns: the contraction over the tile's 64 envs, Delta [G hp x 64] . Y^T [64 x (in + hp + 2)]
+//         with Y = (x | h | 1 | 1): the two rows of ones (zero for a lane that is not live) make the biases columns of the same
+//         product, and column kk of unit u is slot kk G + g of the unit's packed block, i.e. the partial vector has the layout of
+//         Rnn::w.  Four envs per LDS read: the delta rows have a stride of 68 floats, so that the 64 units' b128 reads spread over
+//         the banks; the Y rows are one address for the wave (a broadcast).  Plain fp32 FMAs: the contraction costs what the delta
+//         phase costs, which scalar weights keep off the matrix pipe in any case.  Accumulators stay in registers across the run
+//         of tiles: 17 + 10 columns x G.
+//   * One delta buffer: layer 1's contraction and the gather come before layer 0's deltas overwrite it.  Two LSTM layers of 64:
+//     267 rows of 64 and 322 rows of 68 floats = 152.3 KiB.
+//   * Deterministic, no atomics: a thread owns its slots, the workgroup stores row blockIdx.x of the workspace [n_wg][psize], and
+//     k_fnn_param_reduce adds the rows in its fixed order, through the setter's index map (padding: -1, never written).
+constexpr int RNNG_WAVES = 8;
+constexpr int RNNG_RS = 68;                                                                 // floats per delta row
+constexpr int RNNG_NC0 = (RNN_XP + RNN_MAXW + 2 + RNNG_WAVES - 1) / RNNG_WAVES;              // columns per wave, layer 0
+constexpr int RNNG_NC1 = (2 * RNN_MAXW + 2 + RNNG_WAVES - 1) / RNNG_WAVES;                   // ... layer 1
+__host__ __device__ constexpr int rnng_delta_rows(int gates) { return gates == 1 ? 1 : 4; }  // per unit (GRU: r, z, n, n r)
+// floats of LDS per workgroup: rows of 64 (x | h | layer 0's h' and adjoint (two layers) | abar | ones), rows of 68 (h'_top | deltas | delta_out)
+__host__ __device__ constexpr size_t rnng_lds_floats(int gates, int n_layers, int hp, int A) {
+    return (size_t)(RNN_XP + n_layers * hp + (n_layers > 1 ? 2 * hp : 0) + A + 1) * 64 +
+           (size_t)(hp + rnng_delta_rows(gates) * hp + A) * RNNG_RS;
+}
+// acc[c][g] += sum over the tile's envs of delta_g[lane][e] Y[kk][e], kk = wave + c RNNG_WAVES: lane = unit (< H, the caller's
+// guard), the column and its row of Y are wave-uniform.  yin: the layer's `inp` input rows, yh its hp state rows, then the ones.
+template <int G, int NC>
+__device__ __forceinline__ void rnng_contract(float (&acc)[NC][G], const float* drow, const float* yin, int inp, const float* yh,
+                                              int hp, const float* ones, int wave, int lane) {
+    constexpr int DG = rnng_delta_rows(G);
+    const int nk = inp + hp + 2;
+#pragma unroll 1
+    for (int e = 0; e < 64; e += 4) {
+        float4 dl[DG];
+#pragma unroll
+        for (int g = 0; g < DG; ++g) dl[g] = *reinterpret_cast<const float4*>(drow + (size_t)(g * hp + lane) * RNNG_RS + e);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int kk = wave + c * RNNG_WAVES;
+            if (kk >= nk) continue;  // (wave-uniform)
+            const bool hid = kk >= inp && kk != inp + hp;  // W_hh, b_hh: the GRU's n row is delta_n r there
+            const float* yr = kk < inp ? yin + kk * 64 : kk < inp + hp ? yh + (kk - inp) * 64 : ones;
+            const float4 y = *reinterpret_cast<const float4*>(yr + e);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float4 dv = (G == 3 && g == 2 && hid) ? dl[DG - 1] : dl[g];
+                float a = acc[c][g];
+                a = fmaf(dv.x, y.x, a);
+                a = fmaf(dv.y, y.y, a);
+                a = fmaf(dv.z, y.z, a);
+                a = fmaf(dv.w, y.w, a);
+                acc[c][g] = a;
+            }
+        }
+    }
+}
+template <int G>
+__global__ __launch_bounds__(64 * RNNG_WAVES) void k_rnn_param_grad(FnnRows R, const float* abar, const float* d_hid, Rnn P, int t_steps,
+                                                                    int psize, float* part) {
+    static_assert(G == 1 || G == 3 || G == 4, "RNN, GRU or LSTM");
+    extern __shared__ __attribute__((aligned(16))) float l_rpg[];
+    typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
+    constexpr int DG = rnng_delta_rows(G), RS = RNNG_RS;
+    const cfp W = (cfp)P.w;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int A = R.A, Ln = P.n_layers, H = P.hidden, hp = P.hp, hs = P.hs;
+    float* const xrow = l_rpg;                                   // x_t [RNN_XP][64]
+    float* const hrow = xrow + RNN_XP * 64;                      // h_t of every layer [Ln hp][64]
+    float* const frow = hrow + Ln * hp * 64;                     // layer 0's h' (two layers) [hp][64]
+    float* const arow = frow + (Ln > 1 ? hp : 0) * 64;           // adjoint of layer 0's h' (two layers) [hp][64]
+    float* const abrow = arow + (Ln > 1 ? hp : 0) * 64;          // abar [A][64]
+    float* const ones = abrow + A * 64;                          // 1 where the lane is live [64]
+    float* const htop = ones + 64;                               // h' of the top layer [hp][RS]
+    float* const drow = htop + hp * RS;                          // deltas [DG hp][RS]
+    float* const dorow = drow + DG * hp * RS;                    // delta_out [A][RS]
+    for (int p = (int)threadIdx.x; p < (int)rnng_lds_floats(G, Ln, hp, A); p += 64 * RNNG_WAVES) l_rpg[p] = 0.f;  // (the padding rows stay 0)
+
+    float acc0[RNNG_NC0][G], acc1[RNNG_NC1][G], aWo[MAXA], abo[MAXA];
+#pragma unroll
+    for (int c = 0; c < RNNG_NC0; ++c)
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc0[c][g] = 0.f;
+#pragma unroll
+    for (int c = 0; c < RNNG_NC1; ++c)
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc1[c][g] = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) aWo[j] = abo[j] = 0.f;
+
+    // ---- the workgroup's run of tiles: tile = lane group * t_steps + step
+    const size_t ld = (size_t)R.ld;
+    const int tiles = (R.ld / 64) * t_steps;
+    const int chunk = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
+    const long long first = (long long)blockIdx.x * chunk;
+    const int tile0 = first < tiles ? (int)first : tiles;
+    const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
+    const int NQ = R.F / 4, H2 = (R.F % 4) >= 2 ? 1 : 0;
+    const bool need_y = P.out_nonlin != FNN_ID;
+    int g_of_L = -1, L = 0;
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int gr = tile / t_steps, t = tile - gr * t_steps;  // uniform over the workgroup
+        const int i = gr * 64 + lane;
+        if (gr != g_of_L) {
+            // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (k_rollout_vjp_rnn's)
+            g_of_L = gr;
+            L = 0;
+            if (i < R.n) {
+                L = t_steps;
+                for (int w = 0; w * 32 < t_steps; ++w) {
+                    uint32_t m = R.done[(size_t)w * ld + i];
+                    const int rem = t_steps - w * 32;
+                    if (rem < 32) m &= (1u << rem) - 1u;
+                    if (m) {
+                        L = w * 32 + __ffs((int)m);
+                        break;
+                    }
+                }
+            }
+        }
+        const bool live = t < L;
+        if (__ballot(live) == 0ull) continue;  // no lane of the tile reaches step t (the same in every wave): nothing is loaded
+        __syncthreads();                       // the contraction of the tile before has read its rows
+        const float* const hr = P.hrec + (size_t)t * (size_t)hs * ld + i;  // p_t
+        const float* const er = d_hid + (size_t)t * (size_t)hs * ld + i;   // the cotangent of p_{t+1}
+        // ---- loads, lane = env: x_t (wave 0), abar and the ones (wave 1), the h rows (every wave its share)
+        if (wave == 0) {
+            float ob[MAXO];
+#pragma unroll
+            for (int c = 0; c < MAXO; ++c) {  // column c of the record planes (Planes<F>, F at run time)
+                ob[c] = 0.f;
+                if (live && c < R.O) {
+                    const size_t at = c < 4 * NQ ? (size_t)(c / 4) * 4 * ld + 4 * (size_t)i + (c & 3)
+                                      : (H2 && c < 4 * NQ + 2) ? (size_t)NQ * 4 * ld + 2 * (size_t)i + (c - 4 * NQ)
+                                                               : ((size_t)NQ * 4 + H2 * 2) * ld + i;
+                    ob[c] = R.rec[(size_t)t * R.F * ld + at];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < RNN_XP; ++k) {  // what the policy saw of obs_t, as in k_rollout_rnn
+                float v = 0.f;
+                if (P.ident) {
+                    v = ob[k];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < MAXO; ++j) v = (k < P.n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                }
+                xrow[k * 64 + lane] = v;
+            }
+        } else if (wave == 1) {
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j)
+                if (j < A) abrow[j * 64 + lane] = live ? abar[((size_t)t * A + j) * ld + i] : 0.f;
+            ones[lane] = live ? 1.0f : 0.f;
+        }
+        for (int r = wave; r < Ln * H; r += RNNG_WAVES) {
+            const int l = r / H, j = r - l * H;
+            hrow[(l * hp + j) * 64 + lane] = live ? hr[(size_t)r * ld] : 0.f;
+        }
+        __syncthreads();
+        float xv[RNN_XP];
+#pragma unroll
+        for (int k = 0; k < RNN_XP; ++k) xv[k] = xrow[k * 64 + lane];
+        // ---- forward, layer by layer: layer 0's h' for layer 1, h'_top for dW_out and y_out
+        for (int l = 0; l < Ln; ++l) {
+            const float* hst = hrow + (size_t)(l * hp) * 64 + lane;
+#pragma unroll 1
+            for (int u = wave; u < H; u += RNNG_WAVES) {
+                const RnnAct<G> a = rnn_unit_act<G>(P.cell, W + P.off[l] + u * P.blk[l], l == 0, xv, frow + lane, hst, hp);
+                float hv;
+                if constexpr (G == 1) {
+                    hv = a.g[0];
+                } else if constexpr (G == 3) {
+                    hv = (1.0f - a.g[1]) * a.g[2] + a.g[1] * hst[u * 64];
+                } else {
+                    const float cu = live ? hr[(size_t)((Ln + l) * H + u) * ld] : 0.f;
+                    hv = a.g[3] * tanh_fast(a.g[1] * cu + a.g[0] * a.g[2]);
+                }
+                if (l < Ln - 1) frow[u * 64 + lane] = hv;
+                else htop[u * RS + lane] = hv;
+            }
+            __syncthreads();
+        }
+        // ---- delta_out (every wave for its own use, wave 0 leaves it for the contraction)
+        float dout[MAXA];
+#pragma unroll
+        for (int j = 0; j < MAXA; ++j) dout[j] = j < A ? abrow[j * 64 + lane] : 0.f;
+        if (need_y) {
+            float yo[MAXA];
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) yo[j] = 0.f;
+            for (int u = 0; u < H; ++u) {
+                const float hv = htop[u * RS + lane];
+#pragma unroll
+                for (int j = 0; j < MAXA; ++j)
+                    if (j < A) yo[j] = fmaf(W[P.off_o + j * hp + u], hv, yo[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j)
+                if (j < A) dout[j] *= fnn_nonlin_grad(P.out_nonlin, fnn_nonlin(P.out_nonlin, yo[j] + W[P.off_o + A * hp + j]));
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j)
+                if (j < A) dorow[j * RS + lane] = dout[j];
+        }
+        // ---- the deltas of layer l, the wave's units: recompute, k_rollout_vjp_rnn's expressions, one row per gate
+        auto deltas = [&](int l) __attribute__((always_inline)) {
+            const float* hst = hrow + (size_t)(l * hp) * 64 + lane;
+#pragma unroll 1
+            for (int u = wave; u < H; u += RNNG_WAVES) {
+                const RnnAct<G> a = rnn_unit_act<G>(P.cell, W + P.off[l] + u * P.blk[l], l == 0, xv, frow + lane, hst, hp);
+                float dh;
+                if (l == Ln - 1) {
+                    dh = live ? er[(size_t)(l * H + u) * ld] : 0.f;
+#pragma unroll
+                    for (int j = 0; j < MAXA; ++j)
+                        if (j < A) dh = fmaf(W[P.off_o + j * hp + u], dout[j], dh);
+                } else {
+                    dh = arow[u * 64 + lane];
+                }
+                float* const dr = drow + (size_t)u * RS + lane;
+                if constexpr (G == 1) {
+                    const float y = a.g[0];
+                    dr[0] = dh * (P.cell == RNN_CELL_RELU ? (y > 0.f ? 1.0f : 0.f) : fmaf(-y, y, 1.0f));
+                } else if constexpr (G == 3) {
+                    const float r = a.g[0], z = a.g[1], n = a.g[2], hu = hst[u * 64];
+                    const float dn = dh * (1.0f - z) * fmaf(-n, n, 1.0f);
+                    dr[0] = dn * a.hn * (r * (1.0f - r));
+                    dr[(size_t)hp * RS] = dh * (hu - n) * (z * (1.0f - z));
+                    dr[(size_t)2 * hp * RS] = dn;
+                    dr[(size_t)3 * hp * RS] = dn * r;
+                } else {
+                    const float ig = a.g[0], fg = a.g[1], gg = a.g[2], og = a.g[3];
+                    const float cu = live ? hr[(size_t)((Ln + l) * H + u) * ld] : 0.f;
+                    const float ca = live ? er[(size_t)((Ln + l) * H + u) * ld] : 0.f;
+                    const float tc = tanh_fast(fg * cu + ig * gg);
+                    const float dc = fmaf(dh * og, fmaf(-tc, tc, 1.0f), ca);
+                    dr[0] = dc * gg * (ig * (1.0f - ig));
+                    dr[(size_t)hp * RS] = dc * cu * (fg * (1.0f - fg));
+                    dr[(size_t)2 * hp * RS] = dc * ig * fmaf(-gg, gg, 1.0f);
+                    dr[(size_t)3 * hp * RS] = dh * tc * (og * (1.0f - og));
+                }
+            }
+        };
+        deltas(Ln - 1);
+        __syncthreads();
+        if (Ln > 1) {
+            // ---- the adjoint of layer 0's h': its d_hid part, then layer 1's W_ih^T delta, unit by unit and gate by gate
+#pragma unroll 1
+            for (int k = wave; k < H; k += RNNG_WAVES) {
+                float v = live ? er[(size_t)k * ld] : 0.f;
+                for (int u = 0; u < H; ++u) {
+                    const cfp wk = W + P.off[1] + u * P.blk[1] + k * G;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) v = fmaf(wk[g], drow[(size_t)(g * hp + u) * RS + lane], v);
+                }
+                arow[k * 64 + lane] = v;  // (read back by this wave only)
+            }
+            if (lane < H) rnng_contract<G, RNNG_NC1>(acc1, drow, frow, hp, hrow + (size_t)hp * 64, hp, ones, wave, lane);
+        } else {
+            if (lane < H) rnng_contract<G, RNNG_NC0>(acc0, drow, xrow, RNN_XP, hrow, hp, ones, wave, lane);
+        }
+        if (wave == 0 && lane < H) {  // dW_out, db_out (the same sum in every lane)
+#pragma unroll 1
+            for (int e = 0; e < 64; e += 4) {
+                const float4 y = *reinterpret_cast<const float4*>(htop + (size_t)lane * RS + e);
+#pragma unroll
+                for (int j = 0; j < MAXA; ++j) {
+                    if (j >= A) continue;
+                    const float4 dv = *reinterpret_cast<const float4*>(dorow + (size_t)j * RS + e);
+                    aWo[j] = fmaf(dv.w, y.w, fmaf(dv.z, y.z, fmaf(dv.y, y.y, fmaf(dv.x, y.x, aWo[j]))));
+                    abo[j] = (((abo[j] + dv.x) + dv.y) + dv.z) + dv.w;
+                }
+            }
+        }
+        if (Ln > 1) {
+            __syncthreads();  // layer 1's delta rows are read
+            deltas(0);
+            __syncthreads();
+            if (lane < H) rnng_contract<G, RNNG_NC0>(acc0, drow, xrow, RNN_XP, hrow, hp, ones, wave, lane);
+        }
+    }
+
+    // ---- the workgroup's row of the workspace: every slot has one owner
+    float* const prow = part + (size_t)blockIdx.x * psize;
+    if (lane < H) {
+#pragma unroll
+        for (int c = 0; c < RNNG_NC0; ++c) {
+            const int kk = wave + c * RNNG_WAVES;
+            if (kk >= RNN_XP + hp + 2) continue;
+#pragma unroll
+            for (int g = 0; g < G; ++g) prow[P.off[0] + lane * P.blk[0] + kk * G + g] = acc0[c][g];
+        }
+        if (Ln > 1) {
+#pragma unroll
+            for (int c = 0; c < RNNG_NC1; ++c) {
+                const int kk = wave + c * RNNG_WAVES;
+                if (kk >= 2 * hp + 2) continue;
+#pragma unroll
+                for (int g = 0; g < G; ++g) prow[P.off[1] + lane * P.blk[1] + kk * G + g] = acc1[c][g];
+            }
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int j = 0; j < MAXA; ++j) {
+                if (j >= A) continue;
+                prow[P.off_o + j * hp + lane] = aWo[j];
+                if (lane == 0) prow[P.off_o + A * hp + j] = abo[j];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------ wave-specialised rollout kernel
 // At the size of the headline metric (65 536 envs) k_rollout has exactly one wave per SIMD, and a lone wave issues a VALU
 // instruction only every ~7 cycles while the SIMD takes one every 4 from two or more waves (the same
@@ -4559,6 +4886,9 @@ struct vs_env {
     int* fnn_pg_map = nullptr;    // ... pol_map on the device; both go with the network (drop_fnn)
     int fnn_pg_wgs = 0;
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
+    float* rnn_pg_part = nullptr; // vs_rnn_param_grad: as fnn_pg_*, for the recurrent policy (drop_rnn)
+    int* rnn_pg_map = nullptr;
+    int rnn_pg_wgs = 0;
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)
     vs::Sens sens{};              // vs_set_rollout_sens: the sensitivity buffers and the chosen parameters (sens.n == 0: off)

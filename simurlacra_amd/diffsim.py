@@ -462,14 +462,22 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
     policy's hidden state included.  Every rollout starts from init_hidden(), a constant.
     Forward: set_policy_rnn from the module's current weights (that zeroes the hidden state), set_policy_hidden_record(Hs),
     reset(init_state), one recording step_policy(T).  Backward: one rollout_vjp_rnn per batch for the adjoints of the actions and of
-    the hidden states and d init_states, then ONE batched single-step pass of the policy over the recorded [N T] observations and
-    hidden states -- not sequential in time, 2^20 rows at a time -- for the parameter gradients."""
+    the hidden states and d init_states, and the parameter gradients by param_pass:
+      "torch"   (the default) ONE batched single-step pass of the policy over the recorded [N T] observations and hidden states --
+                not sequential in time, 2^20 rows at a time;
+      "kernel"  one rnn_param_grad per batch (vs_rnn_param_grad), straight on the sweep's d_act and d_hid and the handle's records:
+                the first batch writes the flat gradient, later batches add to it; no [N, T, .] copy of d_hid, of the hidden-state
+                record or of the observations is made.  Deterministic: backward() twice returns the same bits.
+    A policy with a parameter that is not float32 takes the torch pass whatever is asked (self.param_pass says which one runs); any
+    other value raises ValueErr."""
 
     _PASS_ROWS = 1 << 20  # rows of the batched parameter pass at a time (the device RNN library's tensors are indexed with 32 bits)
 
-    def __init__(self, env, policy, batch_lanes: int = 65536):
+    def __init__(self, env, policy, batch_lanes: int = 65536, param_pass: str = "torch"):
         from .policies import NormalActNoiseExplStrat, _RNNPolicyBase, rnn_kernel_spec
 
+        if param_pass not in ("kernel", "torch"):
+            raise ValueErr(msg=f"param_pass is 'kernel' or 'torch', got {param_pass!r}")
         inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
         if not isinstance(inner, _RNNPolicyBase):
             raise TypeErr(msg="DifferentiableRecurrentRollout takes an RNNPolicy, GRUPolicy or LSTMPolicy, optionally inside a "
@@ -483,6 +491,23 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
         self.policy, self._mean = policy, inner
         self._arch = {k: spec[k] for k in ("cell", "n_layers", "hidden_size", "output_nonlin")}
         self._hs = inner.hidden_size
+        fp32 = all(p.dtype == torch.float32 for p in inner.parameters())
+        self.param_pass = param_pass if fp32 else "torch"
+        if self.param_pass == "kernel":  # the device pass runs per batch (_keep_flat); _keep and _param_grads are the torch pass
+            self._needs_rows = False
+            self._keep, self._param_grads = self._keep_flat, self._flat_param_grads
+
+    def _keep_flat(self, v, T, n, more, da, kept):
+        """the running flat gradient: the first batch writes it, every later batch adds to what the batch before returned"""
+        flat = kept[-1] if kept else None
+        return v.rnn_param_grad(T, da, more[0], out=flat, accumulate=flat is not None)
+
+    def _flat_param_grads(self, seen, abar, kept):
+        flat, grads, at = kept[-1], [], 0
+        for p in self._mean.parameters():  # parameters_to_vector's order
+            grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
+            at += p.numel()
+        return tuple(grads)
 
     def _noise_std(self):
         from .policies import rnn_kernel_spec

@@ -646,6 +646,7 @@ class VecSimEnv:
         self._check(self._lib.vs_set_policy_rnn(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_rnn")
         self._rnn_hs = d.n_layers * d.hidden * (2 if d.cell == L.VS_RNN_LSTM else 1)
+        self._rnn_n_params = int(flat.size)  # (what rnn_param_grad returns; it holds while _rnn_hs is not 0)
 
     _LIN_KINDS = {"identity": L.VS_FEAT_IDENTITY, "sign": L.VS_FEAT_SIGN, "abs": L.VS_FEAT_ABS, "squared": L.VS_FEAT_SQUARED,
                   "cubic": L.VS_FEAT_CUBIC, "sig": L.VS_FEAT_SIG, "bell": L.VS_FEAT_BELL, "sin": L.VS_FEAT_SIN, "cos": L.VS_FEAT_COS,
@@ -983,6 +984,39 @@ class VecSimEnv:
         self._check(self._lib.vs_rollout_vjp_rnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr()),
                                                  C.c_void_p(d_hid.data_ptr()), C.c_void_p(d_hid0.data_ptr())), "vs_rollout_vjp_rnn")
         return d_act, d_init, d_hid, d_hid0
+
+    def rnn_param_grad(self, t_steps, abar, d_hid, out=None, accumulate=False):
+        """The parameter gradient that goes with rollout_vjp_rnn, in one device pass over the same records (vs_rnn_param_grad):
+        sum over the rows t < L of the lanes < n_envs of (d F / d theta)(x_t, p_t)^T (abar[t], d_hid[t]), x_t the recorded
+        observation as the policy saw it, p_t row t of the hidden-state record.  abar [t_steps, A, ld] and d_hid [t_steps, Hs, ld]
+        are rollout_vjp_rnn's d_act and d_hid as returned (lanes last); what they hold behind a lane's end and at lanes >= n_envs
+        is never read.  Returns the flat float32 gradient in parameters_to_vector's order on the handle's device: a new tensor,
+        or `out` [n_params], to which accumulate=True adds instead of overwriting.  Deterministic: two calls on the same inputs
+        return the same bits."""
+        import torch
+
+        T, A, Hs = int(t_steps), self.dims["A"], self._rnn_hs
+        if not Hs:
+            raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
+        n_params = self._rnn_n_params
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        for name, x, shape in (("abar", abar, (T, A, self.ld)), ("d_hid", d_hid, (T, Hs, self.ld))):
+            if not hasattr(x, "data_ptr") or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+                raise TypeErr(msg=f"{name} must be a contiguous float32 tensor on the GPU")
+            if tuple(x.shape) != shape:
+                raise ShapeErr(msg=f"{name} must be {shape}, got {tuple(x.shape)}")
+        if out is None:
+            if accumulate:
+                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
+            out = torch.empty(n_params, dtype=torch.float32, device=abar.device)
+        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
+        elif tuple(out.shape) != (n_params,):
+            raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
+        self._check(self._lib.vs_rnn_param_grad(self._h, T, C.c_void_p(abar.data_ptr()), C.c_void_p(d_hid.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), n_params, int(bool(accumulate))), "vs_rnn_param_grad")
+        return out
 
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")

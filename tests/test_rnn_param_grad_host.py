@@ -1,0 +1,175 @@
+"""
+vs_rnn_param_grad / DifferentiableRecurrentRollout(param_pass=...), the parts that need no GPU: the C-ABI declaration, export and
+binding, the NULL refusals, the fp64 restatement of rnn_param_grad_fp64 against torch.autograd.grad of the .double() modules, and what
+its error bound lets through and what it catches.
+
+Rows here are synthetic (normal inputs, hidden states, cotangents; every fourth row is outside): the modules' default initialisation,
+uniform in +-1 / sqrt(H), keeps every gate unsaturated, which the test checks (|z| <= 8).
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import simurlacra_amd as vs
+from simurlacra_amd import _lib as L
+
+torch = pytest.importorskip("torch")
+
+import rnn_param_grad_fp64 as ref64  # noqa: E402
+import test_rnn_vjp_host as cells  # noqa: E402  (unpack_rnn, torch_policy)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the table of test_gpu_rnn_param_grad: (env class, dt, cell, layers, units, output nonlinearity)
+TABLE = {
+    "omo-tanh-3": ("OneMassOscillatorSim", 0.02, "tanh", 1, 3, None),
+    "pend-relu-8": ("PendulumSim", 0.01, "relu", 1, 8, None),
+    "pend-gru-8": ("PendulumSim", 0.01, "gru", 1, 8, None),
+    "qq-su-gru-2x64": ("QQubeSwingUpSim", 0.004, "gru", 2, 64, None),
+    "qcp-su-lstm-64": ("QCartPoleSwingUpSim", 0.002, "lstm", 1, 64, None),
+    "qbb-lstm-2x33-tanh-out": ("QBallBalancerSim", 0.01, "lstm", 2, 33, "tanh"),
+    "bob-gru-63": ("BallOnBeamSim", 0.01, "gru", 1, 63, None),
+}
+ROWS = 240
+
+
+def rows_case(key):
+    """(torch fp64 policy, unpacked fp64 net, x, p, abar, d_hid, inside, output nonlinearity's name)"""
+    env_cls, dt, cell, nl, H, out = TABLE[key]
+    env = getattr(vs, env_cls)(dt=dt, max_steps=30)
+    O, A = env.obs_space.flat_dim, env.act_space.flat_dim
+    torch.manual_seed(11)
+    policy = cells.torch_policy(env.spec, cell, nl, H, {None: None, "tanh": torch.tanh}[out])
+    with torch.no_grad():  # float32 values, so that the float32 pass below runs on the very same parameters
+        flat = policy.param_values.detach().float()
+    policy = policy.double()
+    policy.param_values = flat.double()
+    net = cells.unpack_rnn(flat.numpy(), cell, nl, H, O, A)
+    rng = np.random.default_rng(17)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+    x, p = f32(rng.normal(size=(ROWS, O))), f32(0.5 * rng.normal(size=(ROWS, policy.hidden_size)))
+    abar, d_hid = f32(rng.normal(size=(ROWS, A))), f32(rng.normal(size=(ROWS, policy.hidden_size)))
+    inside = np.arange(ROWS) % 4 != 3
+    return policy, net, x, p, abar, d_hid, inside, out
+
+
+def torch_grad(policy, x, p, abar, d_hid, inside, dtype):
+    policy = policy.to(dtype)
+    t = lambda a: torch.as_tensor(a[inside]).to(dtype)  # noqa: E731
+    act, p_new = policy(t(x), t(p))
+    g = torch.autograd.grad((act, p_new), list(policy.parameters()), grad_outputs=(t(abar), t(d_hid)))
+    return torch.cat([v.reshape(-1) for v in g]).numpy().astype(np.float64)
+
+
+# --------------------------------------------------------------------------------------------------------- the C-ABI
+def test_header_declares_the_exact_signature():
+    header = open(os.path.join(ROOT, "include", "vecsim.h")).read()
+    sig = (r"int\s+vs_rnn_param_grad\(vs_handle h, int t_steps, const float\* abar, const float\* d_hid,\s*float\* d_params, "
+           r"int64_t n_params, int accumulate\);")
+    assert re.search(sig, header)
+
+
+def test_symbol_is_exported_and_bound():
+    lib = C.CDLL(L.LIB_PATH)
+    assert hasattr(lib, "vs_rnn_param_grad")
+    assert "vs_rnn_param_grad" in L.exported_symbols()
+    fn = L.load().vs_rnn_param_grad
+    assert fn.restype is C.c_int and len(fn.argtypes) == 7 and fn.argtypes[5] is C.c_int64
+    assert L.load().vs_version() >= 317
+    assert callable(vs.VecSimEnv.rnn_param_grad)
+
+
+def test_null_handle_and_null_pointers_are_refused_before_a_device_is_touched():
+    out = (C.c_float * 4)()
+    fn = L.load().vs_rnn_param_grad
+    assert fn(None, 1, out, out, out, 4, 0) == L.VS_ERR_ARG
+    assert fn(None, 1, None, out, out, 4, 0) == L.VS_ERR_ARG
+    assert fn(None, 1, out, None, out, 4, 0) == L.VS_ERR_ARG
+    assert fn(None, 1, out, out, None, 4, 0) == L.VS_ERR_ARG
+    assert all(v == 0.0 for v in out)
+
+
+# ------------------------------------------------------------------------------------------------- the fp64 restatement
+@pytest.mark.parametrize("key", list(TABLE))
+def test_restatement_matches_the_double_modules(key):
+    policy, net, x, p, abar, d_hid, inside, out = rows_case(key)
+    got, mag, bound, _ = ref64.param_grad_fp64(net, x, p, abar, d_hid, inside, out)
+    want = torch_grad(policy, x, p, abar, d_hid, inside, torch.float64)
+    assert got.shape == want.shape == mag.shape == bound.shape
+    assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
+    assert (mag >= np.abs(got) - 1e-12).all()
+
+
+@pytest.mark.parametrize("key", list(TABLE))
+def test_bound_admits_the_fp32_pass_and_stays_small(key):
+    policy, net, x, p, abar, d_hid, inside, out = rows_case(key)
+    want, mag, bound, info = ref64.param_grad_fp64(net, x, p, abar, d_hid, inside, out)
+    assert info["zmax"] <= 8.0                                   # gates unsaturated: the bound's assumption
+    assert (bound <= 1e-3 * mag + 1e-4).all()            # the bound cannot hide an error of a thousandth of a parameter's terms
+    fp32 = torch_grad(policy, x, p, abar, d_hid, inside, torch.float32)
+    worst = ref64.worst_ratio(np.abs(fp32 - want), 2.0 * bound)
+    print(f"{key}: torch fp32 pass against fp64, worst error / (2 bound) {worst:.3f}; bound / sum |term| at most "
+          f"{float((bound / np.where(mag > 0, mag, 1.0)).max()):.1e}")
+    assert worst <= 1.0, (key, worst)
+
+
+def segments(net, n_in, A):
+    """{(layer, name): slice of the flat vector}"""
+    G, H, at, out = ref64.GATES[net["cell"]], net["hidden"], 0, {}
+    for l in range(net["n_layers"]):
+        for name, size in (("w_ih", G * H * (n_in if l == 0 else H)), ("w_hh", G * H * H), ("b_ih", G * H), ("b_hh", G * H)):
+            out[(l, name)] = slice(at, at + size)
+            at += size
+    out[("out", "w")] = slice(at, at + A * H)
+    return out
+
+
+MISTAKES = [("swapped gate order", "qcp-su-lstm-64"), ("b_hn folded into b_in", "pend-gru-8"), ("r-scaling dropped", "bob-gru-63"),
+            ("a dropped unit", "omo-tanh-3"), ("the c part of d_hid ignored", "qbb-lstm-2x33-tanh-out"),
+            ("a transposed W_hh block", "qq-su-gru-2x64")]
+
+
+@pytest.mark.parametrize("what,key", MISTAKES)
+def test_bound_catches_the_mistake(what, key):
+    policy, net, x, p, abar, d_hid, inside, out = rows_case(key)
+    want, mag, bound, _ = ref64.param_grad_fp64(net, x, p, abar, d_hid, inside, out)
+    G, H = ref64.GATES[net["cell"]], net["hidden"]
+    seg = segments(net, x.shape[1], abar.shape[1])
+    bad = want.copy()
+    if what == "swapped gate order":     # the first two gates of weight_ih change places
+        s = seg[(0, "w_ih")]
+        blk = bad[s].reshape(G, H, -1).copy()
+        blk[[0, 1]] = blk[[1, 0]]
+        bad[s] = blk.reshape(-1)
+    elif what == "b_hn folded into b_in":  # db_hn = db_in (delta_n, not delta_n r)
+        bad[seg[(0, "b_hh")]].reshape(G, H)[2] = bad[seg[(0, "b_ih")]].reshape(G, H)[2]
+    elif what == "a transposed W_hh block":
+        v = bad[seg[(1, "w_hh")]].reshape(G, H, H)
+        v[0] = v[0].T.copy()
+    else:
+        name = {"r-scaling dropped": "no_r_scale", "a dropped unit": "drop_unit", "the c part of d_hid ignored": "ignore_c"}[what]
+        bad = ref64.param_grad_fp64(net, x, p, abar, d_hid, inside, out, mistake=name)[0]
+    live = mag > 1e-9 * mag.max()        # parameters that are not null
+    caught = live & (np.abs(bad - want) > 2.0 * bound)
+    assert caught.any(), what
+
+
+# ------------------------------------------------------------------------------------------------------- param_pass
+def test_param_pass_validation_and_fallback():
+    env = vs.PendulumSim(dt=0.01, max_steps=30)
+    policy = vs.GRUPolicy(env.spec, hidden_size=8, num_recurrent_layers=1)
+    with pytest.raises(vs.ValueErr, match="param_pass"):
+        vs.DifferentiableRecurrentRollout(env, policy, param_pass="triton")
+    import inspect
+
+    sig = inspect.signature(vs.DifferentiableRecurrentRollout.__init__)
+    assert sig.parameters["param_pass"].default == "torch" and sig.parameters["batch_lanes"].default == 65536
+    roll = vs.DifferentiableRecurrentRollout(env, policy, param_pass="kernel")  # (the constructor makes no handle)
+    assert roll.param_pass == "kernel"
+    roll.close()
+    assert vs.DifferentiableRecurrentRollout(env, policy).param_pass == "torch"
+    roll = vs.DifferentiableRecurrentRollout(env, policy.double(), param_pass="kernel")
+    assert roll.param_pass == "torch"
+    roll.close()
