@@ -4,8 +4,9 @@ test_gpu_rnn_vjp, test_gpu_fnn_param_grad, test_gpu_param_derivatives_all): the 
 open-loop rollout, the all-parameter oracle, the mode-2 recording launch loop, the playback cotangents and the project's tolerance.
 Not a test module: import it by bare name.
 
-The project's tolerance (test_step_jacobians_against_finite_differences) is 3e-3 |g| + 3e-4 max |g_smooth|, an entry smooth where the
-central differences of the fp64 oracle at relative steps 1e-6 and 1e-5 agree to 1e-4.  `max |g_smooth|` needs entries of ONE unit, and
+The project's tolerance is 3e-3 |g| + 3e-4 max |g_smooth|, an entry smooth where the central differences of the fp64 oracle at
+relative steps 1e-6 and 1e-5 agree to 1e-4 (it began in test_step_jacobians_against_finite_differences with one maximum over a whole
+Jacobian; that test now applies it per Jacobian position: step_jacobian_cases.py).  `max |g_smooth|` needs entries of ONE unit, and
 the derivative tests have three kinds of arrays, hence three rules -- all intended, none a special case of another:
 
   * per lane (smooth_per_lane, tolerance_per_lane, within_per_lane, worst_of): gradients with respect to action and state columns,

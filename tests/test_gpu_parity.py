@@ -13,11 +13,13 @@ achieve on the reference's golden step cases (scratch/r2_errors.py on MI355X; ev
   done / failed masks : bit-exact wherever the fp64 next state is further than 1e-5 (relative) from a bound,
                         and ALWAYS bit-exact w.r.t. the kernel's own fp32 next state.
 """
+import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import step_jacobian_cases as sj
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -731,71 +733,129 @@ def test_full_size_mixed_config5_rank_shard(vs):
     assert a_m[2].get(L.VS_EPSTAT_COUNT).sum() > per // 2  # ball-on-beam episodes are short under a random policy
 
 
-@pytest.mark.parametrize("name", ENVS)
-def test_step_jacobians_against_finite_differences(vs, name):
+def setup_jac_lanes(env, L, c):
+    """the lanes of a step_jacobian_cases.Case on a handle; in the "uniform" layout without set_params: the handle keeps the uniform
+    constants of its constructor, and k_step_jac<E, true> runs"""
+    if c.set_params:
+        env.set_params(c.params)
+    env.reset(init_state=c.state)  # full-state shape -> copied verbatim
+    if c.hidden.shape[1]:
+        env.put(L.VS_HIDDEN, c.hidden)
+    env.put(L.VS_STEPCOUNT, c.curr.astype(np.int32))
+    assert np.array_equal(env.get(L.VS_PARAMS), c.params)  # (the oracle's parameters are the device's, in every layout)
+
+
+def jac_at_full_pitch(env, L):
+    """the three Jacobian buffers of the last vs_step_jac as the device holds them, padding lanes included: [rows (S + A), ld] each"""
+    S, A, O = (env.dims[k] for k in "SAO")
+    out = {}
+    for key, which, rows in (("state", L.VS_JAC_STATE, S), ("rew", L.VS_JAC_REW, 1), ("obs", L.VS_JAC_OBS, O)):
+        buf = np.empty((rows * (S + A), env.ld), dtype=np.float32)
+        env._check(env._lib.vs_copy_to_host(env._h, which, buf.ctypes.data_as(C.c_void_p)), "vs_copy_to_host")
+        out[key] = buf
+    return out
+
+
+VALUE_BUFFERS = ("VS_STATE", "VS_OBS", "VS_REW", "VS_DONE", "VS_HIDDEN", "VS_STEPCOUNT")
+
+
+@pytest.mark.parametrize("name,layout", [pytest.param(name, layout, id=name if layout == "nominal" else f"{name}-{layout}")
+                                         for layout in sj.LAYOUTS for name in ENVS])
+def test_step_jacobians_against_finite_differences(vs, name, layout):
     """vs_step_jac (forward-mode differentiation of the step code in the kernel) against central finite differences of the
-    fp64 oracle, on the entries where two step sizes of the finite difference agree (i.e. away from the kinks of clip,
-    dead zone, fold and done); the step VALUES must equal vs_step bit for bit"""
+    fp64 oracle, position by position under the rule of step_jacobian_cases.py, in its three parameter layouts: not one bad entry,
+    every entry of every live position being smooth on these draws, and exact zeros where the oracle has them; the step VALUES must
+    equal vs_step bit for bit"""
     L = vs._lib
-    n = 768
-    rng = np.random.default_rng(11)
-    ref = cpu_ref.make_ref(name, **KW[name])
-    P = ref.nominal_params(n).astype(np.float32).astype(np.float64)
-    slo, shi, alo, ahi = ref.bounds(P)
-    state = f32(0.5 * (slo + shi) + rng.uniform(-0.6, 0.6, slo.shape) * 0.5 * (shi - slo)).astype(np.float64)
-    hidden = f32(rng.uniform(-1, 1, (n, ref.H)) * (20 if name.startswith("qcp") else 0.1)).astype(np.float64)
-    act = f32(rng.uniform(0.35, 0.9, alo.shape) * ahi * rng.choice([-1, 1], alo.shape)).astype(np.float64)
-    act[: n // 8] *= 1.5  # some clipped actions: zero action gradient
-    act = f32(act).astype(np.float64)
-    curr = rng.integers(0, 50, n)
-    a = vs.VecSimEnv(name, n, **KW[name])
-    b = vs.VecSimEnv(name, n, **KW[name])
+    assert sj.ENVS == ENVS
+    c, o, rs = sj.case(name, layout), sj.oracle(name, layout), sj.rules(name, layout)
+    ref, n = c.ref, c.n
+    a = vs.VecSimEnv(name, n, **sj.KW[name])
+    b = vs.VecSimEnv(name, n, **sj.KW[name])
     for e in (a, b):
-        setup_lanes(e, L, P, state, hidden, curr)
-    J = a.step_jac(dev(act))
-    b.step(dev(act))
-    for which in (L.VS_STATE, L.VS_OBS, L.VS_REW, L.VS_DONE, L.VS_HIDDEN, L.VS_STEPCOUNT):
-        assert np.array_equal(a.get(which), b.get(which))
+        setup_jac_lanes(e, L, c)
+    act = dev(np.array(c.act))  # (a copy: the case arrays are read-only)
+    J = a.step_jac(act)
+    b.step(act)
+    for which in VALUE_BUFFERS:
+        assert np.array_equal(a.get(getattr(L, which)), b.get(getattr(L, which))), which
     S, A, O = ref.S, ref.A, ref.O
     assert J["state"].shape == (n, S, S + A) and J["rew"].shape == (n, S + A) and J["obs"].shape == (n, O, S + A)
-    x0 = np.concatenate([state, act], axis=1)
-    scale = np.concatenate([np.maximum(np.abs(shi), 1e-3), np.maximum(np.abs(ahi), 1e-3)], axis=1)
-
-    def fd(eps_rel):
-        js = np.zeros((n, S, S + A)); jr = np.zeros((n, S + A)); jo = np.zeros((n, O, S + A))
-        for k in range(S + A):
-            h_ = eps_rel * scale[:, k]
-            outs = []
-            for sgn in (+1, -1):
-                x = x0.copy()
-                x[:, k] += sgn * h_
-                outs.append(ref.step(x[:, :S], hidden, x[:, S:], P, curr))
-            js[:, :, k] = (outs[0]["state"] - outs[1]["state"]) / (2 * h_[:, None])
-            jr[:, k] = (outs[0]["rew"] - outs[1]["rew"]) / (2 * h_)
-            jo[:, :, k] = (outs[0]["obs"] - outs[1]["obs"]) / (2 * h_[:, None])
-        return js, jr, jo
-
-    f1, f2 = fd(1e-6), fd(1e-5)
-    checked = 0
-    for got, g1, g2, tag in zip((J["state"], J["rew"], J["obs"]), f1, f2, ("state", "rew", "obs")):
-        mag = np.maximum(np.abs(g1), np.abs(g2))
-        smooth = np.abs(g1 - g2) <= 1e-4 * mag + 1e-7 * (1 + mag.max())
-        err = np.abs(got - g1)
-        tol = 3e-3 * np.abs(g1) + 3e-4 * (np.abs(g1[smooth]).max() if smooth.any() else 1.0)
-        bad = smooth & (err > tol)
-        assert bad.mean() < 2e-3, (tag, int(bad.sum()), float(err[bad].max()) if bad.any() else 0.0)
-        assert smooth.mean() > 0.9, (tag, float(smooth.mean()))
-        checked += int(smooth.sum())
-    # structure: clipped actions have zero action-gradient of the next state
-    clipped = (np.abs(act) > ahi).all(axis=1)
+    checked, failures = 0, []
+    for tag, r in zip(sj.ARRAYS, rs):
+        got = J[tag].reshape(n, -1).astype(np.float64)
+        assert np.isfinite(got).all(), tag
+        bad, worst = sj.within(got, r)
+        beyond = sj.ulps_beyond(got, r)
+        print(f"[{name} {layout}] d {tag}: {bad} bad, worst ratio {worst.max():.3g} at position "
+              f"{sj.position(worst.argmax(), S + A)}, {beyond.max():.3g} ulp of the row maximum beyond the relative terms")
+        if bad:
+            failures.append(f"{bad} bad; " + sj.report(name, layout, tag, worst, S + A))
+        assert r.smooth[:, r.live].all() and r.smooth.mean() > 0.9, (tag, float(r.smooth.mean()))
+        assert not got[:, r.exact].any(), (tag, "an exact-zero position is not 0.0")
+        checked += int(sj.checked(r).sum())
+    assert not failures, "\n".join(failures)
+    # structure: clipped actions have zero action-gradient of the next state (of the 1.5 x lanes, n // 8, those whose draw lies above
+    # 2 / 3 of the bound in every action dimension clip: more than 10 of 96, at least 3 of 18)
     if name != "bob-d":
-        assert clipped.sum() > 10 and np.abs(J["state"][clipped][:, :, S:]).max() == 0.0
+        assert o.clipped.sum() > (10 if layout == "nominal" else 2) and np.abs(J["state"][o.clipped][:, :, S:]).max() == 0.0
     assert checked > 0.9 * n * (S + 1 + O) * (S + A)
+    # the padding lanes n .. ld - 1 of the three buffers hold numbers (768 lanes fill their blocks, 150 do not)
+    full = jac_at_full_pitch(a, L)
+    assert a.ld >= n and (a.ld > n) == (layout != "nominal")
+    for tag in sj.ARRAYS:
+        assert full[tag].shape[1] == a.ld and np.isfinite(full[tag]).all(), tag
+        assert np.array_equal(full[tag][:, :n].T, J[tag].reshape(n, -1)), tag
+    # the lanes at curr = max_steps - 1 take the time-limit branch of done, under the same rule as the others (checked above:
+    # every entry of theirs is smooth)
+    assert np.array_equal(a.get(L.VS_DONE).astype(bool), o.done)
+    if layout != "nominal":
+        limit = slice(n - sj.N_LIMIT, n)
+        assert o.done[limit].all() and not a.get(L.VS_FAILED)[limit].any() and o.done.sum() == sj.N_LIMIT
+        assert (a.get(L.VS_STEPCOUNT)[limit] == sj.KW[name]["max_steps"]).all()
+        assert all(sj.checked(r)[limit].all() for r in rs)
+    if name == "omo":
+        # a lane that has already yielded its final reward has the d r of one that has not: a third handle pays the malus first
+        # (a step from outside the box), then steps from the case's lanes
+        y = vs.VecSimEnv(name, n, **sj.KW[name])
+        setup_jac_lanes(y, L, c)
+        y.put(L.VS_STATE, (1.5 * ref.bounds(c.params.astype(np.float64))[1]).astype(np.float32))
+        y.step(act)
+        assert y.get(L.VS_FAILED).all() and (y.get(L.VS_REW) < -900).all()
+        y.put(L.VS_STATE, c.state)
+        y.put(L.VS_STEPCOUNT, c.curr.astype(np.int32))
+        Jy = y.step_jac(act)
+        for tag in sj.ARRAYS:
+            assert np.array_equal(Jy[tag], J[tag]), tag
+        assert np.array_equal(y.get(L.VS_REW), a.get(L.VS_REW))  # (no lane of the case fails: none has a malus to pay)
+        y.close()
     with pytest.raises(RuntimeError):
         a.set_auto_reset(True)
-        a.step_jac(dev(act))
+        a.step_jac(act)
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize("name", ENVS)
+def test_step_jacobians_uniform_constants_equal_per_lane_nominal(vs, name):
+    """k_step_jac<E, true> (a handle that keeps its uniform constants) against k_step_jac<E, false> (the nominal parameters set per
+    lane): the three Jacobians and the step values agree bit for bit, on the first 64 lanes of the "uniform" case"""
+    L = vs._lib
+    c = sj.case(name, "uniform")
+    n = 64
+    cut = c._replace(n=n, params=c.params[:n], state=c.state[:n], hidden=c.hidden[:n], act=c.act[:n], curr=c.curr[:n])
+    uni = vs.VecSimEnv(name, n, **sj.KW[name])
+    per = vs.VecSimEnv(name, n, **sj.KW[name])
+    setup_jac_lanes(uni, L, cut)
+    setup_jac_lanes(per, L, cut._replace(set_params=True))
+    act = dev(np.array(cut.act))  # (a copy: the case arrays are read-only)
+    Ju, Jp = uni.step_jac(act), per.step_jac(act)
+    for tag in sj.ARRAYS:
+        assert np.isfinite(Ju[tag]).all() and np.abs(Ju[tag]).max() > 0.0 and np.array_equal(Ju[tag], Jp[tag]), tag
+    for which in VALUE_BUFFERS:
+        assert np.array_equal(uni.get(getattr(L, which)), per.get(getattr(L, which))), which
+    uni.close()
+    per.close()
 
 
 def test_maximum_size_batch_4m_lanes(vs):
