@@ -39,7 +39,7 @@ def kernels(obj_path):
             out[cur] = []
         elif cur and line.startswith("\t"):
             ins = line.split("//")[0].strip()
-            if ins:
+            if ins and ins != "...":  # (the disassembler's mark for zero padding behind the last kernel of a section: no instruction)
                 out[cur].append(ins)
     names = list(out)
     dm = codeobj._demangle(names)

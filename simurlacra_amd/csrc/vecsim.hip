@@ -541,16 +541,14 @@ static int drop_pop(vs_handle h) {
 }
 
 static int drop_fnn(vs_handle h) {
-    if (int rc = dfree(h, h->fnn.w, h->fnn_pg_part, h->fnn_pg_map)) return rc;  // (the workspace of vs_fnn_param_grad is the network's)
+    if (int rc = dfree(h, h->fnn.w)) return rc;
     h->fnn = Fnn{};
-    h->fnn_pg_wgs = 0;
     return VS_OK;
 }
 
 static int drop_rnn(vs_handle h) {
-    if (int rc = dfree(h, h->rnn.w, h->rnn.hid, h->rnn_pg_part, h->rnn_pg_map)) return rc;  // (the workspace of vs_rnn_param_grad too)
+    if (int rc = dfree(h, h->rnn.w, h->rnn.hid)) return rc;
     h->rnn = Rnn{};
-    h->rnn_pg_wgs = 0;
     return VS_OK;
 }
 
@@ -579,16 +577,46 @@ static int drop_play(vs_handle h) {  // the playback policy and the target that 
 }
 
 // one in-kernel policy at a time: whichever kind is set goes, with what belongs to it -- the running hidden state, the playback
-// target and its sensitivities, the population (it was set for this policy) and the packer's index map
+// target and its sensitivities, the population (it was set for this policy), the packer's index map and the workspace of the
+// parameter-gradient pass (its index map and the width of its partial vectors are this policy's)
 static int drop_policy(vs_handle h) {
     if (int rc = drop_fnn(h)) return rc;
     if (int rc = drop_rnn(h)) return rc;
     if (int rc = drop_lin(h)) return rc;
     if (int rc = drop_play(h)) return rc;
     if (int rc = drop_pop(h)) return rc;
+    if (int rc = dfree(h, h->pg.part, h->pg.map)) return rc;
+    h->pg.wgs = 0;
     h->pol_map.clear();
     h->pol_n_params = 0;
     return VS_OK;
+}
+
+// The workspace for a grid of n_wg workgroups and partial vectors of psize floats.  It belongs to the policy on the handle
+// (drop_policy frees it, so psize and the map are this policy's): the index map goes up on first use, the partial buffer grows when a
+// grid is larger than every one before and never shrinks.
+static int param_grad_workspace(vs_handle h, const char* who, int psize, int n_wg) {
+    if (!h->pg.map) {
+        int* map = nullptr;
+        HIPCHK(h, hipMalloc((void**)&map, (size_t)psize * sizeof(int)));
+        hipError_t e = hipMemcpy(map, h->pol_map.data(), (size_t)psize * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
+        h->pg.map = map;
+    }
+    if (n_wg > h->pg.wgs) {
+        if (h->pg.part) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
+        if (int rc = dfree(h, h->pg.part)) return rc;
+        h->pg.wgs = 0;
+        HIPCHK(h, hipMalloc((void**)&h->pg.part, (size_t)n_wg * psize * sizeof(float)));
+        h->pg.wgs = n_wg;
+    }
+    return VS_OK;
+}
+
+// the reduction of the n_wg partial vectors into d_params, in parameters_to_vector's order
+static void launch_param_reduce(vs_handle h, int n_wg, int psize, float* d_params, int accumulate) {
+    hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream,
+                       (const float*)h->pg.part, n_wg, psize, (const int*)h->pg.map, d_params, accumulate != 0 ? 1 : 0);
 }
 
 // the observation rows a policy sees, descriptor D -> kernel arguments P (n_obs == 0: all of them, in order; ident: exactly that)
@@ -1723,14 +1751,21 @@ static int vjp_checks(vs_handle h, const char* who, int t_steps, const float* d_
     return VS_OK;
 }
 
+// What the sweep entry points do once nothing is refused: the launch is the family's Launch<E>:: call, which may name `v`, the
+// arguments every sweep takes (the entry point's own g_rew, g_obs, g_state_last, d_act and d_init).
+#define VJP_LAUNCH(...)                                         \
+    do {                                                        \
+        HIPCHK(h, hipSetDevice(h->device));                     \
+        const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init}; \
+        DISPATCH_ENV(h->type, __VA_ARGS__);                     \
+        HIPCHK(h, hipGetLastError());                           \
+        return VS_OK;                                           \
+    } while (0)
+
 int vs_rollout_vjp(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last, float* d_act,
                    float* d_init) {
     if (int rc = vjp_checks(h, "vs_rollout_vjp", t_steps, d_act, d_init, nullptr)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
-    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp(h, v, t_steps));
-    HIPCHK(h, hipGetLastError());
-    return VS_OK;
+    VJP_LAUNCH(Launch<E>::rollout_vjp(h, v, t_steps));
 }
 
 int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_state_last,
@@ -1752,11 +1787,7 @@ int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const fl
             if (param_idx[l] == param_idx[j]) return fail(h, VS_ERR_ARG, who, "a parameter index is repeated");
         q.idx[j] = param_idx[j];
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
-    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_dp(h, v, q, t_steps));
-    HIPCHK(h, hipGetLastError());
-    return VS_OK;
+    VJP_LAUNCH(Launch<E>::rollout_vjp_dp(h, v, q, t_steps));
 }
 
 int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
@@ -1767,11 +1798,7 @@ int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const fl
         return nullptr;
     };
     if (int rc = vjp_checks(h, "vs_rollout_vjp_policy", t_steps, d_act, d_init, policy)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
-    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_lin(h, v, g_act, t_steps));
-    HIPCHK(h, hipGetLastError());
-    return VS_OK;
+    VJP_LAUNCH(Launch<E>::rollout_vjp_lin(h, v, g_act, t_steps));
 }
 
 // what vs_rollout_vjp_fnn and vs_fnn_param_grad need of the policy slot
@@ -1785,11 +1812,7 @@ static const char* fnn_sweep_policy(vs_handle h) {
 int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                        const float* g_state_last, float* d_act, float* d_init) {
     if (int rc = vjp_checks(h, "vs_rollout_vjp_fnn", t_steps, d_act, d_init, fnn_sweep_policy)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
-    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_fnn(h, v, g_act, t_steps));
-    HIPCHK(h, hipGetLastError());
-    return VS_OK;
+    VJP_LAUNCH(Launch<E>::rollout_vjp_fnn(h, v, g_act, t_steps));
 }
 
 // what vs_rollout_vjp_rnn and vs_rnn_param_grad need of the policy slot
@@ -1801,53 +1824,52 @@ static const char* rnn_sweep_policy(vs_handle h) {
     return nullptr;
 }
 
+int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0) {
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, rnn_sweep_policy)) return rc;
+    VJP_LAUNCH(Launch<E>::rollout_vjp_rnn(h, v, g_act, g_hid_last, d_hid, d_hid0, t_steps));
+}
+#undef VJP_LAUNCH
+
+// ---- vs_fnn_param_grad / vs_rnn_param_grad: one pass over the records a sweep read, a partial vector per workgroup, then one reduction
+// What the two refuse alike after vjp_checks, before the first device call (`what`: "network" or "policy"), and the records they read.
+static int param_grad_checks(vs_handle h, const char* who, const char* what, int t_steps, int64_t n_params, FnnRows& rows) {
+    if (n_params != h->pol_n_params)
+        return fail(h, VS_ERR_ARG, who, (std::string("n_params is not the parameter count of the ") + what + " on the handle").c_str());
+    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    const EnvInfo& ei = ENV_INFO[h->type];
+    rows = FnnRows{h->d.traj_rec, h->d.traj_done, record_width(h->type, 2), ei.O, ei.A, h->d.n, h->d.ld};
+    return VS_OK;
+}
+
 // workgroups of k_rnn_param_grad: a function of (ld, t_steps, device) only -- a workgroup per tile while there are fewer tiles than
 // compute units (the LDS rows of a wide cell leave room for one workgroup on each), else one per compute unit, each a run of tiles
 static int rnn_param_grad_wgs(const vs_env* h, int t_steps) {
     return (int)std::min<int64_t>((int64_t)(h->d.ld / 64) * t_steps, (int64_t)h->n_cu);
 }
 
-// (k_fnn_param_reduce, launched where vs_fnn_param_grad is: the kernels keep their order in the code object)
-static void launch_param_reduce(vs_handle h, const float* part, int n_wg, int psize, const int* map, float* d_params, int accumulate);
-
 int vs_rnn_param_grad(vs_handle h, int t_steps, const float* abar, const float* d_hid, float* d_params, int64_t n_params,
                       int accumulate) {
     const char* who = "vs_rnn_param_grad";
     if (int rc = vjp_checks(h, who, t_steps, abar, d_params, rnn_sweep_policy, "NULL handle, abar or d_params")) return rc;
     if (!d_hid) return fail(h, VS_ERR_ARG, who, "NULL d_hid");
-    if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, who, "n_params is not the parameter count of the policy on the handle");
-    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    FnnRows rows;
+    if (int rc = param_grad_checks(h, who, "policy", t_steps, n_params, rows)) return rc;
     Rnn P = h->rnn;
     P.hrec = h->d_hrec;
-    const EnvInfo& ei = ENV_INFO[h->type];
     const int psize = (int)h->pol_map.size(), n_wg = rnn_param_grad_wgs(h, t_steps), G = rnn_gates(P.cell);
-    if (psize != P.off_o + ei.A * P.hp + 4 || P.hp > RNN_MAXW || P.n_layers > RNN_MAXL)
+    if (psize != P.off_o + rows.A * P.hp + 4 || P.hp > RNN_MAXW || P.n_layers > RNN_MAXL)
         return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_rnn's");
     HIPCHK(h, hipSetDevice(h->device));
-    // ---- the workspace belongs to the policy on the handle: first use, or a grid larger than every one before
-    if (!h->rnn_pg_map) {
-        int* map = nullptr;
-        HIPCHK(h, hipMalloc((void**)&map, (size_t)psize * sizeof(int)));
-        hipError_t e = hipMemcpy(map, h->pol_map.data(), (size_t)psize * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
-        h->rnn_pg_map = map;
-    }
-    if (n_wg > h->rnn_pg_wgs) {
-        if (h->rnn_pg_part) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
-        if (int rc = dfree(h, h->rnn_pg_part)) return rc;
-        h->rnn_pg_wgs = 0;
-        HIPCHK(h, hipMalloc((void**)&h->rnn_pg_part, (size_t)n_wg * psize * sizeof(float)));
-        h->rnn_pg_wgs = n_wg;
-    }
-    const FnnRows rows{h->d.traj_rec, h->d.traj_done, record_width(h->type, 2), ei.O, ei.A, h->d.n, h->d.ld};
-    const size_t lds = rnng_lds_floats(G, P.n_layers, P.hp, ei.A) * sizeof(float);
+    if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
+    const size_t lds = rnng_lds_floats(G, P.n_layers, P.hp, rows.A) * sizeof(float);
     auto kern = G == 1 ? k_rnn_param_grad<1> : G == 3 ? k_rnn_param_grad<3> : k_rnn_param_grad<4>;
     // beyond the 64 KiB a kernel gets by default the limit is raised; refused, there is no launch
     if (lds > 64 * 1024)
         HIPCHK(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * RNNG_WAVES), lds, h->stream, rows, abar, d_hid, P, t_steps, psize,
-                       h->rnn_pg_part);
-    launch_param_reduce(h, h->rnn_pg_part, n_wg, psize, h->rnn_pg_map, d_params, accumulate);
+                       h->pg.part);
+    launch_param_reduce(h, n_wg, psize, d_params, accumulate);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }
@@ -1862,50 +1884,16 @@ static int fnn_param_grad_wgs(const vs_env* h, int t_steps) {
 int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate) {
     const char* who = "vs_fnn_param_grad";
     if (int rc = vjp_checks(h, who, t_steps, abar, d_params, fnn_sweep_policy, "NULL handle, abar or d_params")) return rc;
-    if (n_params != h->pol_n_params) return fail(h, VS_ERR_ARG, who, "n_params is not the parameter count of the network on the handle");
-    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    FnnRows rows;
+    if (int rc = param_grad_checks(h, who, "network", t_steps, n_params, rows)) return rc;
     const Fnn& f = h->fnn;
     const int psize = (int)h->pol_map.size(), n_wg = fnn_param_grad_wgs(h, t_steps);
     if (psize != f.off_b[f.n_hidden] + 8 || psize > FNNG_PMAX) return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_fnn's");
     HIPCHK(h, hipSetDevice(h->device));
-    // ---- the workspace belongs to the network on the handle: first use, or a grid larger than every one before
-    if (!h->fnn_pg_map) {
-        int* map = nullptr;
-        HIPCHK(h, hipMalloc((void**)&map, (size_t)psize * sizeof(int)));
-        hipError_t e = hipMemcpy(map, h->pol_map.data(), (size_t)psize * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
-        h->fnn_pg_map = map;
-    }
-    if (n_wg > h->fnn_pg_wgs) {
-        if (h->fnn_pg_part) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
-        if (int rc = dfree(h, h->fnn_pg_part)) return rc;
-        h->fnn_pg_wgs = 0;
-        HIPCHK(h, hipMalloc((void**)&h->fnn_pg_part, (size_t)n_wg * psize * sizeof(float)));
-        h->fnn_pg_wgs = n_wg;
-    }
-    const EnvInfo& ei = ENV_INFO[h->type];
-    const FnnRows rows{h->d.traj_rec, h->d.traj_done, record_width(h->type, 2), ei.O, ei.A, h->d.n, h->d.ld};
-    if (f.n_hidden == 1)
-        hipLaunchKernelGGL((k_fnn_param_grad<1>), dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->fnn_pg_part);
-    else
-        hipLaunchKernelGGL((k_fnn_param_grad<2>), dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->fnn_pg_part);
-    hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream,
-                       (const float*)h->fnn_pg_part, n_wg, psize, (const int*)h->fnn_pg_map, d_params, accumulate != 0 ? 1 : 0);
-    HIPCHK(h, hipGetLastError());
-    return VS_OK;
-}
-
-static void launch_param_reduce(vs_handle h, const float* part, int n_wg, int psize, const int* map, float* d_params, int accumulate) {
-    hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream, part, n_wg, psize,
-                       map, d_params, accumulate != 0 ? 1 : 0);
-}
-
-int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
-                       const float* g_state_last, const float* g_hid_last, float* d_act, float* d_init, float* d_hid, float* d_hid0) {
-    if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, rnn_sweep_policy)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const Vjp v{g_rew, g_obs, g_state_last, d_act, d_init};
-    DISPATCH_ENV(h->type, Launch<E>::rollout_vjp_rnn(h, v, g_act, g_hid_last, d_hid, d_hid0, t_steps));
+    if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
+    auto kern = f.n_hidden == 1 ? k_fnn_param_grad<1> : k_fnn_param_grad<2>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->pg.part);
+    launch_param_reduce(h, n_wg, psize, d_params, accumulate);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

@@ -4882,13 +4882,12 @@ struct vs_env {
     float* d_pbuf = nullptr;      // DomainRandWrapperBuffer parameter sets
     float* d_ring = nullptr;      // ActDelayWrapper ring (Pipe::ring)
     vs::Fnn fnn{};                // vs_set_policy_fnn: the network vs_step_policy evaluates (fnn.w == nullptr: none)
-    float* fnn_pg_part = nullptr; // vs_fnn_param_grad: the workgroups' partial vectors [fnn_pg_wgs][packed size], allocated on first use,
-    int* fnn_pg_map = nullptr;    // ... pol_map on the device; both go with the network (drop_fnn)
-    int fnn_pg_wgs = 0;
     vs::Rnn rnn{};                // vs_set_policy_rnn: the recurrent policy vs_step_policy evaluates (rnn.w == nullptr: none)
-    float* rnn_pg_part = nullptr; // vs_rnn_param_grad: as fnn_pg_*, for the recurrent policy (drop_rnn)
-    int* rnn_pg_map = nullptr;
-    int rnn_pg_wgs = 0;
+    struct ParamGradWs {          // vs_fnn_param_grad / vs_rnn_param_grad: the workspace of the policy in the slot, freed with it (drop_policy)
+        float* part = nullptr;    // the workgroups' partial vectors [wgs][packed size], allocated on first use and grown, never shrunk
+        int* map = nullptr;       // pol_map on the device, uploaded on first use
+        int wgs = 0;
+    } pg;
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)
     vs::Sens sens{};              // vs_set_rollout_sens: the sensitivity buffers and the chosen parameters (sens.n == 0: off)

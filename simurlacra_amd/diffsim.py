@@ -227,10 +227,23 @@ class _ClosedLoopRollout(_RecordedBatches):
     self.policy (what the caller gave), self._mean (the module whose parameters get gradients: the policy without its exploration
     noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now.
     A policy with more than the action adjoint to pull back (a hidden state) also says what it keeps of a batch's sweep (_keep)
-    and how the parameter gradients come from it (_param_grads).  A subclass whose _keep already does the parameter pass on the
-    device sets _needs_rows to False: the [N, T, .] copies of abar and of the observations are then not made."""
+    and how the parameter gradients come from it (_param_grads): that is the torch pass.  A subclass with a parameter pass on the
+    device takes param_pass ("kernel" or "torch") through _check_param_pass and _set_param_pass and says which handle method the
+    device pass is (_device_pass).  Under "kernel" it runs per batch on a running flat gradient -- the first batch writes it,
+    later batches add to it -- and _needs_rows is False: the [N, T, .] copies of abar and of the observations are not made."""
 
     _needs_rows = True  # _param_grads reads abar [N, T, A] and the recorded observations [N, T, O]
+
+    @staticmethod
+    def _check_param_pass(param_pass):
+        if param_pass not in ("kernel", "torch"):
+            raise ValueErr(msg=f"param_pass is 'kernel' or 'torch', got {param_pass!r}")
+
+    def _set_param_pass(self, param_pass):
+        """self.param_pass: what was asked, or "torch" when a parameter of self._mean is not float32"""
+        fp32 = all(p.dtype == torch.float32 for p in self._mean.parameters())
+        self.param_pass = param_pass if fp32 else "torch"
+        self._needs_rows = self.param_pass == "torch"
 
     def _check_dims(self, obs_dim, act_dim):
         A, _, O = self._dims()
@@ -247,10 +260,14 @@ class _ClosedLoopRollout(_RecordedBatches):
         """(d_act, d_init, anything else the sweep returns) of one batch"""
         raise NotImplementedError
 
-    def _keep(self, v, T, n, more, da, kept):
-        """what _param_grads needs of a batch beyond abar and the observations; `more`: the sweep's further returns, da: its
-        action adjoints [T, A, ld] as returned (lanes last), kept: what the batches before this one returned here"""
+    def _keep(self, v, T, n, more):
+        """what _param_grads needs of a batch beyond abar and the observations; `more`: the sweep's further returns"""
         return None
+
+    def _device_pass(self, v, T, da, more, out, accumulate):
+        """the handle's parameter-gradient pass of one batch; da: the sweep's action adjoints [T, A, ld] as returned (lanes last),
+        `more`: its further returns; returns the flat gradient (`out`, or a new tensor when out is None)"""
+        raise NotImplementedError
 
     def _param_grads(self, seen, abar, kept):
         """gradients of self._mean's parameters: one batched pass over the [N T] recorded observations"""
@@ -320,11 +337,12 @@ class _ClosedLoopRollout(_RecordedBatches):
         """(gradients of the policy's parameters, d init_states)"""
         A, S, O = self._dims()
         N, T, dev = init_states.shape[0], setup[3], init_states.device
+        kernel = getattr(self, "param_pass", "torch") == "kernel"  # (the linear class has no param_pass: its pass is in torch)
         rows = self._needs_rows
         abar = torch.empty(N, T, A, dtype=torch.float32, device=dev) if rows else None
         seen = torch.empty(N, T, O, dtype=torch.float32, device=dev) if rows else None
         d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
-        kept = []
+        flat, kept = None, []
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, setup, n0, n1, init_states, weights)
@@ -335,8 +353,17 @@ class _ClosedLoopRollout(_RecordedBatches):
                 if rows:
                     abar[n0:n1] = lanes_first(da, n)               # (0 behind a rollout's end: the kernel writes it so)
                     seen[n0:n1] = v.traj_tensors(T, n)["obs"].transpose(0, 1)
-                kept.append(self._keep(v, T, n, more, da, kept))
-        return self._param_grads(seen, abar, kept), d_init
+                if kernel:
+                    flat = self._device_pass(v, T, da, more, out=flat, accumulate=flat is not None)
+                else:
+                    kept.append(self._keep(v, T, n, more))
+        if not kernel:
+            return self._param_grads(seen, abar, kept), d_init
+        grads, at = [], 0
+        for p in self._mean.parameters():  # parameters_to_vector's order
+            grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
+            at += p.numel()
+        return tuple(grads), d_init
 
 
 class DifferentiablePolicyRollout(_ClosedLoopRollout):
@@ -402,8 +429,7 @@ class DifferentiableNetRollout(_ClosedLoopRollout):
     def __init__(self, env, policy, batch_lanes: int = 65536, param_pass: str = "kernel"):
         from .policies import FNN, FNNPolicy, NormalActNoiseExplStrat, fnn_kernel_spec
 
-        if param_pass not in ("kernel", "torch"):
-            raise ValueErr(msg=f"param_pass is 'kernel' or 'torch', got {param_pass!r}")
+        self._check_param_pass(param_pass)
         inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
         if not isinstance(inner, (FNN, FNNPolicy)):
             raise TypeErr(msg="DifferentiableNetRollout takes an FNN or FNNPolicy, optionally inside a NormalActNoiseExplStrat, got "
@@ -419,25 +445,13 @@ class DifferentiableNetRollout(_ClosedLoopRollout):
         self._check_dims(net.hidden_layers[0].in_features - (1 if spec["feat"] else 0), net.output_layer.out_features)
         self.policy, self._mean = policy, inner
         self._arch = {k: spec[k] for k in ("hidden_sizes", "hidden_nonlin", "output_nonlin", "feat")}
-        fp32 = all(p.dtype == torch.float32 for p in inner.parameters())
-        self.param_pass = param_pass if fp32 else "torch"
-        self._needs_rows = self.param_pass == "torch"
+        self._set_param_pass(param_pass)
 
-    def _keep(self, v, T, n, more, da, kept):
-        """the running flat gradient: the first batch writes it, every later batch adds to what the batch before returned"""
-        if self.param_pass != "kernel":
-            return None
-        flat = kept[-1] if kept else None
-        return v.fnn_param_grad(T, da, out=flat, accumulate=flat is not None)
+    def _device_pass(self, v, T, da, more, out, accumulate):
+        return v.fnn_param_grad(T, da, out=out, accumulate=accumulate)
 
-    def _param_grads(self, seen, abar, kept):
-        if self.param_pass != "kernel":  # (the rows in the parameters' dtype: a no-op for a float32 network, whose pass is unchanged)
-            return super()._param_grads(seen.to(next(self._mean.parameters()).dtype), abar, kept)
-        flat, grads, at = kept[-1], [], 0
-        for p in self._mean.parameters():  # parameters_to_vector's order
-            grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
-            at += p.numel()
-        return tuple(grads)
+    def _param_grads(self, seen, abar, kept):  # (the rows in the parameters' dtype: a no-op for a float32 network)
+        return super()._param_grads(seen.to(next(self._mean.parameters()).dtype), abar, kept)
 
     def _noise_std(self):
         from .policies import fnn_kernel_spec
@@ -476,8 +490,7 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
     def __init__(self, env, policy, batch_lanes: int = 65536, param_pass: str = "torch"):
         from .policies import NormalActNoiseExplStrat, _RNNPolicyBase, rnn_kernel_spec
 
-        if param_pass not in ("kernel", "torch"):
-            raise ValueErr(msg=f"param_pass is 'kernel' or 'torch', got {param_pass!r}")
+        self._check_param_pass(param_pass)
         inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
         if not isinstance(inner, _RNNPolicyBase):
             raise TypeErr(msg="DifferentiableRecurrentRollout takes an RNNPolicy, GRUPolicy or LSTMPolicy, optionally inside a "
@@ -491,23 +504,10 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
         self.policy, self._mean = policy, inner
         self._arch = {k: spec[k] for k in ("cell", "n_layers", "hidden_size", "output_nonlin")}
         self._hs = inner.hidden_size
-        fp32 = all(p.dtype == torch.float32 for p in inner.parameters())
-        self.param_pass = param_pass if fp32 else "torch"
-        if self.param_pass == "kernel":  # the device pass runs per batch (_keep_flat); _keep and _param_grads are the torch pass
-            self._needs_rows = False
-            self._keep, self._param_grads = self._keep_flat, self._flat_param_grads
+        self._set_param_pass(param_pass)
 
-    def _keep_flat(self, v, T, n, more, da, kept):
-        """the running flat gradient: the first batch writes it, every later batch adds to what the batch before returned"""
-        flat = kept[-1] if kept else None
-        return v.rnn_param_grad(T, da, more[0], out=flat, accumulate=flat is not None)
-
-    def _flat_param_grads(self, seen, abar, kept):
-        flat, grads, at = kept[-1], [], 0
-        for p in self._mean.parameters():  # parameters_to_vector's order
-            grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
-            at += p.numel()
-        return tuple(grads)
+    def _device_pass(self, v, T, da, more, out, accumulate):
+        return v.rnn_param_grad(T, da, more[0], out=out, accumulate=accumulate)
 
     def _noise_std(self):
         from .policies import rnn_kernel_spec
@@ -522,7 +522,7 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
     def _sweep(self, v, T, g_rew, g_obs, g_act):
         return v.rollout_vjp_rnn(T, g_rew=g_rew, g_obs=g_obs, g_act=g_act)
 
-    def _keep(self, v, T, n, more, da, kept):
+    def _keep(self, v, T, n, more):
         """(cotangents of p_{t+1} [n, T, Hs], recorded p_t [n, T, Hs])"""
         return lanes_first(more[0], n), lanes_first(v.hidden_record_tensor()[:T], n)
 

@@ -903,32 +903,59 @@ class VecSimEnv:
                                                     C.c_void_p(d_params.data_ptr())), "vs_rollout_vjp_params")
         return d_act, d_init, d_params
 
+    def _closed_loop_vjp(self, entry, t_steps, g_rew, g_obs, g_act, g_state_last, more=(), outs=()):
+        """the closed-loop sweep `entry` (a vs_rollout_vjp_* of the library): rollout_vjp's cotangents and g_act [T, A, ld], then
+        `more` of them [(name, tensor or None, shape)]; returns (d_act, d_init) and one new tensor [*shape, ld] per shape in outs"""
+        import torch
+
+        T = int(t_steps)
+        S, A, O, H = (self.dims[k] for k in "SAOH")
+        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
+                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld)),
+                                                    *more))
+        res = (d_act, d_init) + tuple(torch.empty(*shape, self.ld, dtype=torch.float32, device=d_act.device) for shape in outs)
+        self._check(getattr(self._lib, entry)(self._h, T, *ptrs, *(C.c_void_p(x.data_ptr()) for x in res)), entry)
+        return res
+
+    def _param_grad(self, entry, t_steps, inputs, n_params, out, accumulate):
+        """the parameter-gradient pass `entry` (vs_fnn_param_grad / vs_rnn_param_grad) on its inputs [(name, tensor, width)], each
+        a contiguous float32 device tensor [t_steps, width, ld]; returns the flat gradient [n_params]: `out`, or a new tensor"""
+        import torch
+
+        T = int(t_steps)
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        for name, x, width in inputs:
+            if not hasattr(x, "data_ptr") or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+                raise TypeErr(msg=f"{name} must be a contiguous float32 tensor on the GPU")
+            if tuple(x.shape) != (T, width, self.ld):
+                raise ShapeErr(msg=f"{name} must be {(T, width, self.ld)}, got {tuple(x.shape)}")
+        if out is None:
+            if accumulate:
+                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
+            out = torch.empty(n_params, dtype=torch.float32, device=inputs[0][1].device)
+        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
+        elif tuple(out.shape) != (n_params,):
+            raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
+        self._check(getattr(self._lib, entry)(self._h, T, *(C.c_void_p(x.data_ptr()) for _, x, _ in inputs),
+                                              C.c_void_p(out.data_ptr()), n_params, int(bool(accumulate))), entry)
+        return out
+
     def rollout_vjp_policy(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
         """The sweep of rollout_vjp for closed-loop records (vs_rollout_vjp_policy): rows 0 .. t_steps - 1 were recorded by
         step_policy with the linear policy of set_policy_linear that is still on the handle, a_t = W phi(obs_t) + n_t with the
         exploration noise n_t a constant.  One more cotangent, g_act [T, A, ld], on the raw policy action.  Returns
         (d_act [T, A, ld], d_init [S + H, ld]): d_act[t] is the TOTAL adjoint of a_t (= d Phi / d n_t; the parameter gradient is
         sum_t d_act[t] phi(obs_t)^T), d_init includes the feedback through the policy."""
-        T = int(t_steps)
-        S, A, O, H = (self.dims[k] for k in "SAOH")
-        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
-                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld))))
-        self._check(self._lib.vs_rollout_vjp_policy(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
-                    "vs_rollout_vjp_policy")
-        return d_act, d_init
+        return self._closed_loop_vjp("vs_rollout_vjp_policy", t_steps, g_rew, g_obs, g_act, g_state_last)
 
     def rollout_vjp_fnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
         """rollout_vjp_policy for records made with the feed-forward network of set_policy_fnn that is still on the handle (one or
         two hidden layers; vs_rollout_vjp_fnn): a_t = net(x_t) + n_t with the exploration noise n_t a constant.  Same cotangents,
         same returns: d_act[t] is the TOTAL adjoint of the raw action a_t -- the network's parameter gradient is one batched
         backward pass over the recorded observations with it as grad_outputs --, d_init includes the feedback through the network."""
-        T = int(t_steps)
-        S, A, O, H = (self.dims[k] for k in "SAOH")
-        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
-                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld))))
-        self._check(self._lib.vs_rollout_vjp_fnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr())),
-                    "vs_rollout_vjp_fnn")
-        return d_act, d_init
+        return self._closed_loop_vjp("vs_rollout_vjp_fnn", t_steps, g_rew, g_obs, g_act, g_state_last)
 
     def fnn_param_grad(self, t_steps, abar, out=None, accumulate=False):
         """The parameter gradient that goes with rollout_vjp_fnn, in one device pass over the same records (vs_fnn_param_grad):
@@ -937,29 +964,10 @@ class VecSimEnv:
         end and at lanes >= n_envs is never read.  Returns the flat float32 gradient in parameters_to_vector's order on the
         handle's device: a new tensor, or `out` [n_params], to which accumulate=True adds instead of overwriting.  Deterministic:
         two calls on the same inputs return the same bits."""
-        import torch
-
-        T, A = int(t_steps), self.dims["A"]
         n_params = getattr(self, "_fnn_n_params", 0)
         if not n_params:
             raise ValueErr(msg="no feed-forward network set (set_policy_fnn)")
-        if T < 1:
-            raise ValueErr(given=T, ge_constraint="1")
-        if not hasattr(abar, "data_ptr") or not abar.is_cuda or abar.dtype != torch.float32 or not abar.is_contiguous():
-            raise TypeErr(msg="abar must be a contiguous float32 tensor on the GPU")
-        if tuple(abar.shape) != (T, A, self.ld):
-            raise ShapeErr(msg=f"abar must be {(T, A, self.ld)}, got {tuple(abar.shape)}")
-        if out is None:
-            if accumulate:
-                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
-            out = torch.empty(n_params, dtype=torch.float32, device=abar.device)
-        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
-            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
-        elif tuple(out.shape) != (n_params,):
-            raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
-        self._check(self._lib.vs_fnn_param_grad(self._h, T, C.c_void_p(abar.data_ptr()), C.c_void_p(out.data_ptr()), n_params,
-                                                int(bool(accumulate))), "vs_fnn_param_grad")
-        return out
+        return self._param_grad("vs_fnn_param_grad", t_steps, (("abar", abar, self.dims["A"]),), n_params, out, accumulate)
 
     def rollout_vjp_rnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None, g_hid_last=None):
         """rollout_vjp_policy for records made with the recurrent policy of set_policy_rnn that is still on the handle, with the
@@ -969,21 +977,11 @@ class VecSimEnv:
         action a_t and d_hid[t] the total cotangent of p_{t+1} (step t's own output layer not included) -- the parameter gradient
         is one batched single-step backward pass of the policy over the recorded (obs_t, p_t) with the two as grad_outputs --,
         d_hid0 is the cotangent of the initial hidden state, d_init includes the feedback through the policy."""
-        import torch
-
-        T = int(t_steps)
-        S, A, O, H = (self.dims[k] for k in "SAOH")
-        Hs = self._rnn_hs
+        T, Hs = int(t_steps), self._rnn_hs
         if not Hs:
             raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
-        T, ptrs, d_act, d_init = self._vjp_args(T, (("g_rew", g_rew, (T, self.ld)), ("g_obs", g_obs, (T + 1, O, self.ld)),
-                                                    ("g_act", g_act, (T, A, self.ld)), ("g_state_last", g_state_last, (S + H, self.ld)),
-                                                    ("g_hid_last", g_hid_last, (Hs, self.ld))))
-        d_hid = torch.empty(T, Hs, self.ld, dtype=torch.float32, device=d_act.device)
-        d_hid0 = torch.empty(Hs, self.ld, dtype=torch.float32, device=d_act.device)
-        self._check(self._lib.vs_rollout_vjp_rnn(self._h, T, *ptrs, C.c_void_p(d_act.data_ptr()), C.c_void_p(d_init.data_ptr()),
-                                                 C.c_void_p(d_hid.data_ptr()), C.c_void_p(d_hid0.data_ptr())), "vs_rollout_vjp_rnn")
-        return d_act, d_init, d_hid, d_hid0
+        return self._closed_loop_vjp("vs_rollout_vjp_rnn", T, g_rew, g_obs, g_act, g_state_last,
+                                     more=(("g_hid_last", g_hid_last, (Hs, self.ld)),), outs=((T, Hs), (Hs,)))
 
     def rnn_param_grad(self, t_steps, abar, d_hid, out=None, accumulate=False):
         """The parameter gradient that goes with rollout_vjp_rnn, in one device pass over the same records (vs_rnn_param_grad):
@@ -993,30 +991,11 @@ class VecSimEnv:
         is never read.  Returns the flat float32 gradient in parameters_to_vector's order on the handle's device: a new tensor,
         or `out` [n_params], to which accumulate=True adds instead of overwriting.  Deterministic: two calls on the same inputs
         return the same bits."""
-        import torch
-
-        T, A, Hs = int(t_steps), self.dims["A"], self._rnn_hs
+        Hs = self._rnn_hs
         if not Hs:
             raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
-        n_params = self._rnn_n_params
-        if T < 1:
-            raise ValueErr(given=T, ge_constraint="1")
-        for name, x, shape in (("abar", abar, (T, A, self.ld)), ("d_hid", d_hid, (T, Hs, self.ld))):
-            if not hasattr(x, "data_ptr") or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-                raise TypeErr(msg=f"{name} must be a contiguous float32 tensor on the GPU")
-            if tuple(x.shape) != shape:
-                raise ShapeErr(msg=f"{name} must be {shape}, got {tuple(x.shape)}")
-        if out is None:
-            if accumulate:
-                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
-            out = torch.empty(n_params, dtype=torch.float32, device=abar.device)
-        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
-            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
-        elif tuple(out.shape) != (n_params,):
-            raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
-        self._check(self._lib.vs_rnn_param_grad(self._h, T, C.c_void_p(abar.data_ptr()), C.c_void_p(d_hid.data_ptr()),
-                                                C.c_void_p(out.data_ptr()), n_params, int(bool(accumulate))), "vs_rnn_param_grad")
-        return out
+        return self._param_grad("vs_rnn_param_grad", t_steps, (("abar", abar, self.dims["A"]), ("d_hid", d_hid, Hs)),
+                                self._rnn_n_params, out, accumulate)
 
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")

@@ -30,6 +30,7 @@ torch = pytest.importorskip("torch")
 
 import rnn_param_grad_fp64 as ref64  # noqa: E402
 import test_fnn_param_grad_host as fnn_host  # noqa: E402  (the FNN pass's fp64 reference and bound)
+import test_gpu_fnn_vjp as fv  # noqa: E402  (the [8] tanh network of the pendulum)
 import test_gpu_rnn_vjp as rv  # noqa: E402  (make_rnn, flat_params, set_rnn, the autograd cases)
 from derivative_cases import ACT_IN, KW, MAX_STEPS, STATE_BUFFERS, dev, draw_params_and_init, frozen, record_mode2  # noqa: E402
 
@@ -371,3 +372,63 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     print(f"{name}: loss {losses[0]:.6f} -> {losses[1]:.6f} -> {losses[2]:.6f}")
     assert losses[2] < losses[1] < losses[0], losses
     roll.close()
+
+
+# ------------------------------------------------------------------------------------------------------- 6. one workspace
+def test_one_workspace_serves_both_policy_kinds_in_turn(vs):
+    """The workspace of the parameter-gradient pass (index map, partial vectors) belongs to the handle's policy slot, whichever kind is
+    in it.  ONE pendulum handle of 65 lanes (two lane groups, the second 1/64 full) runs, in this order,
+      1. the [8] tanh network: record T = 3, sweep, fnn_param_grad           (3 ld / 64 tiles)
+      2. the GRU of pend-gru-8 with its hidden record: record T = 40, rnn_param_grad
+                                                                              (40 ld / 64 tiles: the buffer regrows, another packed size and map; 40 rows
+                                                                              cross the 32-row done word; rows 3 .. 39 of step 1 were stale)
+      3. the network again: record T = 40, fnn_param_grad                    (again another packed size and map)
+      4. the same network, not set again: record T = 3, sweep, fnn_param_grad (a smaller grid in the larger buffer)
+    and each result equals BIT FOR BIT that of the same call on a fresh handle: the grid is a function of (ld, t_steps, device) and the
+    kernels are deterministic (test_two_calls_and_accumulate_are_exact), so a stale map, a buffer of another width or a regrow under
+    a running launch would show, and nothing else can differ."""
+    n, long = 65, 40
+    fc, gc = fv.case("pend-8"), case("pend-gru-8")
+    params, init, A = fc["params"][:n], fc["init"][:n], fc["ref"].A
+
+    def record(e, t, set_policy):
+        return record_mode2(e, long, params, set_policy, init, (t,))
+
+    def dense(e, t, width, seed):
+        return torch.randn(t, width, e.ld, device="cuda", generator=torch.Generator("cuda").manual_seed(seed))
+
+    def fnn_short(e, set_policy=lambda e: fv.set_net(e, fc["net"])):
+        record(e, 3, set_policy)
+        ll = lambda x: vs.lanes_last(dev(x), e.ld)  # noqa: E731
+        da, _ = e.rollout_vjp_fnn(3, g_rew=ll(fc["g_rew"][:n, :3]), g_obs=ll(fc["g_obs"][:n, :4]), g_act=ll(fc["g_act"][:n, :3]),
+                                  g_state_last=ll(fc["g_last"][:n]))
+        return e.fnn_param_grad(3, da)
+
+    def gru_long(e):
+        record(e, long, lambda e: rv.set_rnn(e, gc["net"]))
+        return e.rnn_param_grad(long, dense(e, long, A, 6), dense(e, long, gc["Hs"], 7))
+
+    def fnn_long(e):
+        record(e, long, lambda e: fv.set_net(e, fc["net"]))
+        return e.fnn_param_grad(long, dense(e, long, A, 5))
+
+    def handle():
+        return vs.VecSimEnv("pend", n, max_steps=MAX_STEPS, **KW["pend"])
+
+    e = handle()
+    got = [fnn_short(e).clone(), gru_long(e).clone(), fnn_long(e).clone()]
+    length = e.rollout_lengths(n, long)[0].cpu().numpy()
+    got.append(fnn_short(e, lambda e: None).clone())
+    assert e.error_count() == 0
+    e.close()
+    for k, step in ((0, fnn_short), (1, gru_long), (2, fnn_long)):
+        f = handle()
+        want = step(f)
+        assert bool(torch.isfinite(want).all()) and bool(want.any()) and f.error_count() == 0, k
+        assert torch.equal(got[k], want), k
+        if k == 0:
+            assert torch.equal(got[3], want), 3
+        f.close()
+    assert got[0].shape == got[2].shape and got[1].shape != got[0].shape and not torch.equal(got[0], got[2])
+    print(f"lengths of the network's {long}-row record: {np.bincount(length, minlength=long + 1).tolist()}")
+    assert (length < long).any() and (length > 32).any()  # lanes that end early, lanes that live into the second done word
