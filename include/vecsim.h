@@ -493,7 +493,8 @@ int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const fl
  * before the first device call, outputs untouched" are vs_rollout_vjp's, with one more cotangent:
  *   g_act   [t_steps][A][ld]   cotangent of the raw policy action a_t; NULL: 0
  *   d_act   [t_steps][A][ld]   out: the TOTAL adjoint abar_t of a_t = d Phi / d n_t -- what the policy's parameter gradient needs:
- *                              d Phi / d W = sum_t abar_t phi(obs_t)^T over the recorded observations (left to the caller: one GEMM)
+ *                              d Phi / d W = sum_t abar_t phi(obs_t)^T over the recorded observations (left to the caller: one GEMM,
+ *                              or vs_lin_param_grad below, one device pass over the handle's own records)
  *   d_init  [S + H][ld]        out: d Phi / d (s_0, h_0), feedback through the policy included
  * For t = L - 1 .. 0 the step is differentiated as in vs_rollout_vjp with the observation cotangent g_obs[t + 1] + gpol, gpol [O] being
  * the policy's pull-back of step t + 1 (0 at t = L - 1; observe(s_{t+1}) is the observation the policy saw);  abar_t = (the step's
@@ -539,6 +540,24 @@ int vs_rollout_vjp_fnn(vs_handle h, int t_steps, const float* g_rew, const float
  * Refused with nothing written: everything vs_rollout_vjp_fnn refuses, with the same codes; NULL abar or d_params, n_params other
  * than the network's parameter count (VS_ERR_ARG). */
 int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate);
+/* The weight gradient that vs_rollout_vjp_policy leaves to the caller, as one device pass over the same records:
+ *     d Phi / d W[j][q] = sum over the rows t < L of every lane i < n_envs of abar_t[j] phi_q(x_t)
+ * for the handle's current linear policy (vs_set_policy_linear), phi_q the q-th feature of its stack evaluated with the rollout
+ * kernel's expressions (sincos_fast, v_exp_f32, the bare v_rcp_f32, the device library's atan2f).  x_t is built from the RECORDED
+ * observation of row t (obs_idx): the row the policy saw.  L is the lane's length as vs_rollout_vjp takes it from the done bits of
+ * rows 0 .. t_steps - 1.
+ *   abar      [t_steps][A][ld]   device: d_act as vs_rollout_vjp_policy returned it (ld = vs_ld(h)).  Rows t >= L, lanes >= n_envs
+ *                                and anything behind row t_steps are never read into the arithmetic: they may hold anything, NaN
+ *                                included
+ *   d_params  [A * F]            device, out: the gradient in the order of the parameter vector vs_set_policy_linear took (net.weight
+ *                                [A][F] row-major, F features in stack order); accumulate != 0: added to what is there, one fp32 add
+ *                                per entry
+ * Runs on the handle's stream and writes nothing of the handle.  The sum is deterministic: no atomics, every partial sum is added in
+ * a fixed order that depends on (ld, t_steps, device) only, so two calls on the same inputs return the same bits.  A workspace for
+ * the partial sums belongs to the policy on the handle: allocated at the first call, freed when the policy is replaced or removed.
+ * Refused with nothing written: everything vs_rollout_vjp_policy refuses, with the same codes; NULL abar or d_params, n_params
+ * other than the policy's parameter count, more than 2^31 - 1 tiles of 64 lanes x one step (VS_ERR_ARG). */
+int vs_lin_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate);
 /* ... and for rollouts recorded with the handle's current RECURRENT policy (vs_set_policy_rnn: RNN tanh / relu, GRU or LSTM of one or
  * two layers) in the loop: (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0), p the packed hidden state [Hs] (h of layer 0, 1, .. then, LSTM, c
  * of layer 0, 1, ..), x_t the observation rows the policy sees (obs_idx), n_t constant.  The differentiated function is

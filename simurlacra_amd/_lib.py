@@ -110,6 +110,7 @@ _SIGNATURES = {
     "vs_rollout_vjp_fnn": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vs_fnn_param_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int]),
     "vs_rnn_param_grad": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int]),
+    "vs_lin_param_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int]),
     "vs_rollout_vjp_rnn": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
     "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),

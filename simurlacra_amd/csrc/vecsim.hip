@@ -662,7 +662,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 317; }
+int vs_version(void) { return 318; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1790,14 +1790,16 @@ int vs_rollout_vjp_params(vs_handle h, int t_steps, const float* g_rew, const fl
     VJP_LAUNCH(Launch<E>::rollout_vjp_dp(h, v, q, t_steps));
 }
 
+// what vs_rollout_vjp_policy and vs_lin_param_grad need of the policy slot
+static const char* lin_sweep_policy(vs_handle h) {
+    if (!h->lin.w) return "no linear policy on the handle (vs_set_policy_linear)";
+    if (h->pop.w) return "not available with a policy population on the handle";
+    return nullptr;
+}
+
 int vs_rollout_vjp_policy(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
                           const float* g_state_last, float* d_act, float* d_init) {
-    const auto policy = [](vs_handle h) -> const char* {
-        if (!h->lin.w) return "no linear policy on the handle (vs_set_policy_linear)";
-        if (h->pop.w) return "not available with a policy population on the handle";
-        return nullptr;
-    };
-    if (int rc = vjp_checks(h, "vs_rollout_vjp_policy", t_steps, d_act, d_init, policy)) return rc;
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_policy", t_steps, d_act, d_init, lin_sweep_policy)) return rc;
     VJP_LAUNCH(Launch<E>::rollout_vjp_lin(h, v, g_act, t_steps));
 }
 
@@ -1831,8 +1833,8 @@ int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float
 }
 #undef VJP_LAUNCH
 
-// ---- vs_fnn_param_grad / vs_rnn_param_grad: one pass over the records a sweep read, a partial vector per workgroup, then one reduction
-// What the two refuse alike after vjp_checks, before the first device call (`what`: "network" or "policy"), and the records they read.
+// ---- vs_fnn_param_grad / vs_rnn_param_grad / vs_lin_param_grad: one pass over the records a sweep read, a partial vector per workgroup, then one reduction
+// What they refuse alike after vjp_checks, before the first device call (`what`: "network" or "policy"), and the records they read.
 static int param_grad_checks(vs_handle h, const char* who, const char* what, int t_steps, int64_t n_params, FnnRows& rows) {
     if (n_params != h->pol_n_params)
         return fail(h, VS_ERR_ARG, who, (std::string("n_params is not the parameter count of the ") + what + " on the handle").c_str());
@@ -1893,6 +1895,28 @@ int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
     if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
     auto kern = f.n_hidden == 1 ? k_fnn_param_grad<1> : k_fnn_param_grad<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->pg.part);
+    launch_param_reduce(h, n_wg, psize, d_params, accumulate);
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+// workgroups of k_lin_param_grad, one wave each: a function of (ld, t_steps, device) only -- a wave per tile while there are fewer
+// tiles than wave slots (the LDS rows of a wave leave room for four on a compute unit), else four per compute unit, each a run of tiles
+static int lin_param_grad_wgs(const vs_env* h, int t_steps) {
+    return (int)std::min<int64_t>((int64_t)(h->d.ld / 64) * t_steps, 4 * (int64_t)h->n_cu);
+}
+
+int vs_lin_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int64_t n_params, int accumulate) {
+    const char* who = "vs_lin_param_grad";
+    if (int rc = vjp_checks(h, who, t_steps, abar, d_params, lin_sweep_policy, "NULL handle, abar or d_params")) return rc;
+    FnnRows rows;
+    if (int rc = param_grad_checks(h, who, "policy", t_steps, n_params, rows)) return rc;
+    const int psize = (int)h->pol_map.size(), n_wg = lin_param_grad_wgs(h, t_steps);
+    if (psize != rows.A * LIN_SLOTS || rows.A > MAXA) return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_linear's");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
+    auto kern = rows.A == 1 ? k_lin_param_grad<1> : k_lin_param_grad<2>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64), 0, h->stream, rows, abar, h->lin, t_steps, h->pg.part);
     launch_param_reduce(h, n_wg, psize, d_params, accumulate);
     HIPCHK(h, hipGetLastError());
     return VS_OK;

@@ -20,6 +20,7 @@
 //   k_rollout_vjp_rnn  vs_rollout_vjp_rnn     ... with the handle's recurrent policy in the loop (a second adjoint for its hidden state)
 //   k_fnn_param_grad / k_fnn_param_reduce  vs_fnn_param_grad   the network's parameter gradients from the records and the sweep's d_act
 //   k_rnn_param_grad (+ k_fnn_param_reduce)  vs_rnn_param_grad  the recurrent policy's, from the records, the sweep's d_act and d_hid
+//   k_lin_param_grad (+ k_fnn_param_reduce)  vs_lin_param_grad  the linear policy's weights, from the records and the sweep's d_act
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -3234,6 +3235,194 @@ __global__ __launch_bounds__(BLOCK) void k_fnn_param_reduce(const float* part, i
     if (w + 2 < n_wg) a2 += part[(size_t)(w + 2) * psize + p];
     const float s = (a0 + a1) + (a2 + a3);
     d_params[q] = accumulate ? d_params[q] + s : s;
+}
+
+// ------------------------------------------------------------------------------ parameter gradients of the linear policy
+// vs_lin_param_grad: what k_rollout_vjp_lin leaves to the caller -- d Phi / d W = sum over the rows (t < L_i, i < n) of
+//     dW[j][q] += abar[t][j][i] phi_q(x_t,i)
+// with abar = d_act as the sweep wrote it (lanes-last) and phi evaluated with k_rollout_lin's expressions, statement for statement, on
+// the RECORDED observation (columns 0 .. O - 1 of the record row, run-time widths, as in k_fnn_param_grad: the kernel needs nothing of
+// the family).  Nothing here is matrix-shaped either: the contraction is A <= 2 wide, plain fp32 FMAs.
+//   * One wave per workgroup (k_rollout_lin's granularity), a contiguous run of tiles per wave (64 lanes x one step, lane-group major;
+//     L once per lane group).  A tile no lane reaches is skipped before its loads.
+//   * Phase one, lane = env: the lane loads its observation and abar only where t < L and i < n (nothing else is ever read), evaluates
+//     the stack's features -- a kind the stack does not hold costs a scalar branch -- and stores phi into its LDS row [env][slot] in the
+//     packed slot order of Lin::w.  The row pitch is LIN_SLOTS + 1 floats: the 64 lanes' stores of one slot fall into 32 distinct banks
+//     twice, and column LIN_SLOTS of a row holds 0.
+//   * Phase two, lane = slot (slots lane and lane + 64 of an action row): the wave walks the set bits of the tile's ballot (a lane that
+//     is not live is skipped, not multiplied by zero) and does acc[j][s] += abar[e][j] phi[e][slot]; the phi reads are consecutive
+//     addresses, the abar reads one address for the wave.  A slot the stack does not use reads column LIN_SLOTS: its sum stays 0.
+//   * Deterministic, no atomics: the accumulators of a wave ARE its partial vector, in the layout of Lin::w; it goes to row blockIdx.x
+//     of the workspace and k_fnn_param_reduce adds the rows in its fixed order through the setter's index map (unused slots: -1, never
+//     written).  The grid depends on (ld, t_steps, device) only.
+// (NA: the family's action dimensions, which makes this a template, so the translation unit that launches it is the one that holds it.)
+constexpr int LING_PITCH = LIN_SLOTS + 1;
+template <int NA>
+__global__ __launch_bounds__(64) void k_lin_param_grad(FnnRows R, const float* abar, Lin P, int t_steps, float* part) {
+    static_assert(NA >= 1 && NA <= MAXA && LIN_SLOTS == 128 && MAXO == 8, "two slots per lane, eight rows per kind");
+    __shared__ float l_phi[64 * LING_PITCH];  // the tile's features: [env][slot | 0]
+    __shared__ float l_ab[64 * NA];           // abar: [env][NA]
+    const int lane = threadIdx.x;
+    const unsigned kinds = P.kinds;
+    const int n_vis = P.n_vis;
+
+    // ---- the lane's two slots in phase two: the column of an env's row it reads (LIN_SLOTS, the zero, when the stack has no such slot)
+    int col[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int slot = lane + 64 * s;
+        const bool used = slot < LIN_CONST_SLOT    ? ((kinds >> (slot / MAXO)) & 1u) != 0u && slot % MAXO < n_vis
+                          : slot == LIN_CONST_SLOT ? ((kinds >> LIN_CONST) & 1u) != 0u
+                                                   : slot - LIN_CONST_SLOT - 1 < P.n_x;
+        col[s] = used ? slot : LIN_SLOTS;
+    }
+    float acc[NA][2];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) acc[j][0] = acc[j][1] = 0.f;
+
+    // ---- the wave's run of tiles: tile = lane group * t_steps + step
+    const size_t ld = (size_t)R.ld;
+    const int tiles = (R.ld / 64) * t_steps;
+    const int chunk = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
+    const long long first = (long long)blockIdx.x * chunk;
+    const int tile0 = first < tiles ? (int)first : tiles;
+    const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
+    const int NQ = R.F / 4, H2 = (R.F % 4) >= 2 ? 1 : 0;
+    float* const prow = l_phi + lane * LING_PITCH;  // phase one: the lane's own row
+    int g_of_L = -1, L = 0;
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform
+        const int i = g * 64 + lane;
+        if (g != g_of_L) {
+            // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (k_rollout_vjp_lin's)
+            g_of_L = g;
+            L = 0;
+            if (i < R.n) {
+                L = t_steps;
+                for (int w = 0; w * 32 < t_steps; ++w) {
+                    uint32_t m = R.done[(size_t)w * ld + i];
+                    const int rem = t_steps - w * 32;
+                    if (rem < 32) m &= (1u << rem) - 1u;
+                    if (m) {
+                        L = w * 32 + __ffs((int)m);
+                        break;
+                    }
+                }
+            }
+        }
+        const bool live = t < L;
+        unsigned long long mask = __ballot(live);
+        if (mask == 0ull) continue;  // no lane of the tile reaches step t: nothing is loaded
+        wave_lds_fence();            // the walk of the previous tile has read its rows
+        if (live) {
+            const float* row = R.rec + (size_t)t * R.F * ld;
+            float ob[MAXO];
+#pragma unroll
+            for (int c = 0; c < MAXO; ++c) {  // column c of the record planes (Planes<F>, F at run time)
+                ob[c] = 0.f;
+                if (c < R.O) {
+                    const size_t at = c < 4 * NQ ? (size_t)(c / 4) * 4 * ld + 4 * (size_t)i + (c & 3)
+                                      : (H2 && c < 4 * NQ + 2) ? (size_t)NQ * 4 * ld + 2 * (size_t)i + (c - 4 * NQ)
+                                                               : ((size_t)NQ * 4 + H2 * 2) * ld + i;
+                    ob[c] = row[at];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NA; ++j) l_ab[lane * NA + j] = abar[((size_t)t * NA + j) * ld + i];
+            // ---- what the policy saw of obs_t, as in k_rollout_lin
+            float x[MAXO];
+            if (P.ident) {
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k) x[k] = ob[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k) {
+                    float v = 0.f;
+#pragma unroll
+                    for (int j = 0; j < MAXO; ++j) v = (k < n_vis && P.obs_idx[k] == j) ? ob[j] : v;  // wave-uniform selects
+                    x[k] = v;
+                }
+            }
+            // ---- phi(x), kind by kind, in k_rollout_lin's expressions (f: the feature of row k as an expression of v = x[k])
+#define VS_LING_KIND(q, f)                                        \
+    if (kinds & (1u << (q))) {                                    \
+        _Pragma("unroll") for (int k = 0; k < MAXO; ++k) {        \
+            const float v = x[k];                                 \
+            if (k < n_vis) prow[(q) * MAXO + k] = (f);            \
+        }                                                         \
+    }
+            VS_LING_KIND(LIN_ID, v)
+            VS_LING_KIND(LIN_SIGN, v > 0.f ? 1.0f : (v < 0.f ? -1.0f : v))  // torch.sign: 0 stays 0, NaN stays NaN
+            VS_LING_KIND(LIN_ABS, fabsf(v))
+            VS_LING_KIND(LIN_SQ, v * v)
+            VS_LING_KIND(LIN_CUBIC, v * v * v)
+            VS_LING_KIND(LIN_SIG, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)))
+            VS_LING_KIND(LIN_BELL, __builtin_amdgcn_exp2f(-0.7213475204444817f * (v * v)))  // exp(-v^2 / 2)
+#undef VS_LING_KIND
+            if (kinds & ((1u << LIN_SIN) | (1u << LIN_COS) | (1u << LIN_SINSIN) | (1u << LIN_SINCOS))) {
+                float sn[MAXO], cs[MAXO];
+#pragma unroll
+                for (int k = 0; k < MAXO; ++k) {
+                    sn[k] = cs[k] = 0.f;
+                    if (k < n_vis) sincos_fast(x[k], &sn[k], &cs[k]);  // one call per row serves the four kinds
+                }
+#define VS_LING_TRIG(q, f)                                        \
+    if (kinds & (1u << (q))) {                                    \
+        _Pragma("unroll") for (int k = 0; k < MAXO; ++k)          \
+            if (k < n_vis) prow[(q) * MAXO + k] = (f);            \
+    }
+                VS_LING_TRIG(LIN_SIN, sn[k])
+                VS_LING_TRIG(LIN_COS, cs[k])
+                VS_LING_TRIG(LIN_SINSIN, sn[k] * sn[k])
+                VS_LING_TRIG(LIN_SINCOS, sn[k] * cs[k])
+#undef VS_LING_TRIG
+            }
+            if (kinds & (1u << LIN_CONST)) prow[LIN_CONST_SLOT] = 1.0f;
+            for (int e = 0; e < P.n_x; ++e) {  // MultFeat / ATan2Feat terms (uniform)
+                const unsigned xt = P.xterm[e];
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int orow = (int)((xt >> (3 * r)) & 7u);
+                    float u = 0.f;
+#pragma unroll
+                    for (int j = 0; j < MAXO; ++j) u = orow == j ? ob[j] : u;  // wave-uniform selects
+                    v[r] = u;
+                }
+                float ph;
+                if (xt >> 31) {
+                    ph = atan2f(v[0], v[1]);
+                } else {
+                    const int more = (int)((xt >> 12) & 3u);  // rows beyond the first two
+                    ph = v[0] * v[1];
+                    ph = more >= 1 ? ph * v[2] : ph;
+                    ph = more >= 2 ? ph * v[3] : ph;
+                }
+                prow[LIN_CONST_SLOT + 1 + e] = ph;
+            }
+            prow[LIN_SLOTS] = 0.f;  // what a slot outside the stack reads
+        }
+        wave_lds_fence();
+        // ---- the tile's live envs one after the other, lane = slot
+#pragma unroll 1
+        while (mask) {
+            const int e = __builtin_ctzll(mask);  // t >= L, lane >= n: not in the mask -- skipped, not multiplied by zero
+            mask &= mask - 1ull;
+            const float* er = l_phi + e * LING_PITCH;
+            const float p0 = er[col[0]], p1 = er[col[1]];
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const float ab = l_ab[e * NA + j];
+                acc[j][0] = fmaf(ab, p0, acc[j][0]);
+                acc[j][1] = fmaf(ab, p1, acc[j][1]);
+            }
+        }
+    }
+    // ---- the wave's partial vector [NA][LIN_SLOTS], row blockIdx.x of the workspace
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) part[(size_t)blockIdx.x * (NA * LIN_SLOTS) + j * LIN_SLOTS + 64 * s + lane] = acc[j][s];
 }
 
 // --------------------------------------------------------------------- reverse-mode sweep with a recurrent policy in the loop

@@ -227,9 +227,9 @@ class _ClosedLoopRollout(_RecordedBatches):
     self.policy (what the caller gave), self._mean (the module whose parameters get gradients: the policy without its exploration
     noise) and says how the policy reaches a handle (_set_policy), which sweep runs (_sweep) and what the noise's std is now.
     A policy with more than the action adjoint to pull back (a hidden state) also says what it keeps of a batch's sweep (_keep)
-    and how the parameter gradients come from it (_param_grads): that is the torch pass.  A subclass with a parameter pass on the
-    device takes param_pass ("kernel" or "torch") through _check_param_pass and _set_param_pass and says which handle method the
-    device pass is (_device_pass).  Under "kernel" it runs per batch on a running flat gradient -- the first batch writes it,
+    and how the parameter gradients come from it (_param_grads): that is the torch pass.  Every subclass takes param_pass
+    ("kernel" or "torch") through _check_param_pass and _set_param_pass and says which handle method the device pass is
+    (_device_pass).  Under "kernel" it runs per batch on a running flat gradient -- the first batch writes it,
     later batches add to it -- and _needs_rows is False: the [N, T, .] copies of abar and of the observations are not made."""
 
     _needs_rows = True  # _param_grads reads abar [N, T, A] and the recorded observations [N, T, O]
@@ -337,7 +337,7 @@ class _ClosedLoopRollout(_RecordedBatches):
         """(gradients of the policy's parameters, d init_states)"""
         A, S, O = self._dims()
         N, T, dev = init_states.shape[0], setup[3], init_states.device
-        kernel = getattr(self, "param_pass", "torch") == "kernel"  # (the linear class has no param_pass: its pass is in torch)
+        kernel = self.param_pass == "kernel"
         rows = self._needs_rows
         abar = torch.empty(N, T, A, dtype=torch.float32, device=dev) if rows else None
         seen = torch.empty(N, T, O, dtype=torch.float32, device=dev) if rows else None
@@ -377,12 +377,18 @@ class DifferentiablePolicyRollout(_ClosedLoopRollout):
     dynamics AND through the policy's dependence on the observations.  The exploration noise (keyed by noise_seed) is a constant
     of the graph: its std gets no gradient; domain_params get none either.
     Forward: set_policy_linear from the module's current weights, reset(init_state), one recording step_policy(T).  Backward: one
-    rollout_vjp_policy per batch for the action adjoints and d init_states, then ONE batched pass of the policy over the recorded
-    [N T] observations for the parameter gradients."""
+    rollout_vjp_policy per batch for the action adjoints and d init_states, and the weight gradient by param_pass:
+      "torch"   (the default) ONE batched pass of the policy over the recorded [N T] observations;
+      "kernel"  one lin_param_grad per batch (vs_lin_param_grad), straight on the sweep's action adjoints and the handle's records:
+                the first batch writes the flat gradient, later batches add to it; no [N, T, .] copy of the adjoints or of the
+                observations and no [N T, num_feat] feature matrix is made.  Deterministic: backward() twice returns the same bits.
+    A policy whose weight is not float32 takes the torch pass whatever is asked (self.param_pass says which one runs); any other
+    value raises ValueErr."""
 
-    def __init__(self, env, policy, batch_lanes: int = 65536):
+    def __init__(self, env, policy, batch_lanes: int = 65536, param_pass: str = "torch"):
         from .policies import LinearPolicy, NormalActNoiseExplStrat, linear_kernel_spec
 
+        self._check_param_pass(param_pass)
         inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
         if not isinstance(inner, LinearPolicy):
             raise TypeErr(msg="DifferentiablePolicyRollout takes a LinearPolicy, optionally inside a NormalActNoiseExplStrat, got "
@@ -394,6 +400,13 @@ class DifferentiablePolicyRollout(_ClosedLoopRollout):
         super().__init__(env, "DifferentiablePolicyRollout", batch_lanes)
         self._check_dims(inner.env_spec.obs_space.flat_dim, inner.env_spec.act_space.flat_dim)
         self.policy, self._mean, self._terms = policy, inner, spec["terms"]
+        self._set_param_pass(param_pass)
+
+    def _device_pass(self, v, T, da, more, out, accumulate):
+        return v.lin_param_grad(T, da, out=out, accumulate=accumulate)
+
+    def _param_grads(self, seen, abar, kept):  # (the rows in the weight's dtype: a no-op for a float32 policy)
+        return super()._param_grads(seen.to(next(self._mean.parameters()).dtype), abar, kept)
 
     def _noise_std(self):
         from .policies import linear_kernel_spec

@@ -602,7 +602,7 @@ class VecSimEnv:
         featurisation [o_0, sin o_1, cos o_1, o_2 ..]; obs_idx: the observation rows the policy sees (ObsPartialWrapper);
         noise_std: exploration noise per action dimension.  params=None removes the network."""
         self._rnn_hs = 0  # (a network replaces a recurrent policy)
-        self._fnn_n_params = 0
+        self._fnn_n_params = self._lin_n_params = 0
         if params is None:
             self._check(self._lib.vs_set_policy_fnn(self._h, None, None, 0), "vs_set_policy_fnn")
             return
@@ -632,6 +632,7 @@ class VecSimEnv:
         step_policy.  params: parameters_to_vector(policy.parameters()) in torch order; cell: 'tanh' | 'relu' (nn.RNN) | 'gru' |
         'lstm'; obs_idx / noise_std as in set_policy_fnn.  Zeroes the running hidden state (policy_hidden()).  params=None
         removes the policy."""
+        self._lin_n_params = 0  # (a recurrent policy replaces a linear one)
         if params is None:
             self._check(self._lib.vs_set_policy_rnn(self._h, None, None, 0), "vs_set_policy_rnn")
             self._rnn_hs = 0
@@ -661,6 +662,7 @@ class VecSimEnv:
         for MultFeat, ('atan2', (i_sin, i_cos)) for ATan2Feat, the indices counting the rows the policy sees; obs_idx / noise_std
         as in set_policy_fnn.  params=None removes the policy."""
         self._rnn_hs = 0  # (a linear policy replaces a recurrent one)
+        self._lin_n_params = 0
         if params is None:
             self._check(self._lib.vs_set_policy_linear(self._h, None, None, 0), "vs_set_policy_linear")
             return
@@ -682,6 +684,7 @@ class VecSimEnv:
         flat = self._flat_params(params)
         self._check(self._lib.vs_set_policy_linear(self._h, C.byref(d), flat.ctypes.data_as(C.c_void_p), flat.size),
                     "vs_set_policy_linear")
+        self._lin_n_params = int(flat.size)  # (what lin_param_grad returns)
 
     def _table_arg(self, x):
         """a float32 table for the library: a device tensor stays where it is, anything else becomes a host array"""
@@ -703,6 +706,7 @@ class VecSimEnv:
         recording (None: t_len), past which the action is 0; lane_rec [n_envs]: the recording every lane replays (None: lane i
         replays (index offset + i) % n_rec).  The row is the env's own step counter.  actions=None removes the policy."""
         self._rnn_hs = 0  # (a playback policy replaces a recurrent one)
+        self._lin_n_params = 0
         if actions is None:
             self._check(self._lib.vs_set_policy_playback(self._h, None, 0, 0, None, None), "vs_set_policy_playback")
             return
@@ -918,7 +922,7 @@ class VecSimEnv:
         return res
 
     def _param_grad(self, entry, t_steps, inputs, n_params, out, accumulate):
-        """the parameter-gradient pass `entry` (vs_fnn_param_grad / vs_rnn_param_grad) on its inputs [(name, tensor, width)], each
+        """the parameter-gradient pass `entry` (vs_fnn_param_grad / vs_rnn_param_grad / vs_lin_param_grad) on its inputs [(name, tensor, width)], each
         a contiguous float32 device tensor [t_steps, width, ld]; returns the flat gradient [n_params]: `out`, or a new tensor"""
         import torch
 
@@ -949,6 +953,18 @@ class VecSimEnv:
         (d_act [T, A, ld], d_init [S + H, ld]): d_act[t] is the TOTAL adjoint of a_t (= d Phi / d n_t; the parameter gradient is
         sum_t d_act[t] phi(obs_t)^T), d_init includes the feedback through the policy."""
         return self._closed_loop_vjp("vs_rollout_vjp_policy", t_steps, g_rew, g_obs, g_act, g_state_last)
+
+    def lin_param_grad(self, t_steps, abar, out=None, accumulate=False):
+        """The weight gradient that goes with rollout_vjp_policy, in one device pass over the same records (vs_lin_param_grad):
+        sum over the rows t < L of the lanes < n_envs of abar[t] phi(x_t)^T, x_t the recorded observation as the policy saw it and
+        phi the stack of set_policy_linear in the rollout kernel's expressions.  abar [t_steps, A, ld] is rollout_vjp_policy's d_act
+        as returned (lanes last); what it holds behind a lane's end and at lanes >= n_envs is never read.  Returns the flat float32
+        gradient of net.weight ([A][num_feat] row-major, stack order) on the handle's device: a new tensor, or `out` [n_params], to
+        which accumulate=True adds instead of overwriting.  Deterministic: two calls on the same inputs return the same bits."""
+        n_params = getattr(self, "_lin_n_params", 0)
+        if not n_params:
+            raise ValueErr(msg="no linear policy set (set_policy_linear)")
+        return self._param_grad("vs_lin_param_grad", t_steps, (("abar", abar, self.dims["A"]),), n_params, out, accumulate)
 
     def rollout_vjp_fnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
         """rollout_vjp_policy for records made with the feed-forward network of set_policy_fnn that is still on the handle (one or
