@@ -662,7 +662,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 318; }
+int vs_version(void) { return 319; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];

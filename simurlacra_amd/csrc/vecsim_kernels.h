@@ -2561,7 +2561,7 @@ __global__ __launch_bounds__(64) void k_rollout_vjp_dp(Task T, Dev d, Vjp V, Vjp
 //     through obs_idx.  Per slot of a kind the stack holds  wbar = sum_j abar_t[j] W[j][slot]  (weight = uniform operand) and
 //     gx[k] = fmaf(wbar, phi'(x_k), gx[k]);  sincos_fast, v_exp_f32 and v_rcp_f32 in the forward kernel's expressions, so the derivative
 //     is that of the function that ran.  sign and const have derivative 0 and cost nothing; |v|' = sign(v), 0 at 0, as torch has it.
-//     MultFeat: the product rule per position (a row named twice gets both terms); ATan2Feat(y, x): (x, -y) / (x^2 + y^2); both add to
+//     MultFeat: the product rule per position (a row named twice gets both terms); ATan2Feat(y, x): (x, -y) / (x^2 + y^2), the rows scaled by a power of two first; both add to
 //     the observation rows directly.  gx goes back to observation rows through obs_idx by wave-uniform selects: the next gpol.
 //   * After t = 0: vjp_observe with g_obs[0] + gpol, d_init = lambda.  Rows t >= L of d_act and lanes >= n are 0 and read no cotangent.
 // With a stack whose features are all constant gpol stays +0 and every float operation is k_rollout_vjp's: the same bits.
@@ -2705,10 +2705,17 @@ __global__ __launch_bounds__(64) void k_rollout_vjp_lin(Task T, Dev d, Vjp V, co
                 for (int j = 0; j < E::A; ++j) wb = fmaf(W[j * LIN_SLOTS + LIN_CONST_SLOT + 1 + e], ab[j], wb);
                 int rows;
                 if (xt >> 31) {  // atan2(y = v[0], x = v[1])
+                    // both rows scaled by ONE power of two next to 1 / max(|y|, |x|) (exact), so that x^2 + y^2 lies in [1/4, 2): with
+                    // the rows as they are the sum underflows below 1e-19 and wb / (x^2 + y^2) overflows where the gradient itself
+                    // (of size 1 / max) is finite -- at (1e-20, 0) it was (NaN, -inf) for (0, -1e20).  The same bits wherever
+                    // nothing under- or overflowed; at (0, 0) NaN as before (0 / 0).
                     rows = 2;
-                    const float q = wb / fmaf(v[1], v[1], v[0] * v[0]);
-                    g[0] = v[1] * q;
-                    g[1] = -v[0] * q;
+                    int ex;
+                    (void)frexpf(fmaxf(fabsf(v[0]), fabsf(v[1])), &ex);
+                    const float ys = ldexpf(v[0], -ex), xs = ldexpf(v[1], -ex);
+                    const float q = wb / fmaf(xs, xs, ys * ys);
+                    g[0] = ldexpf(xs * q, -ex);
+                    g[1] = ldexpf(-ys * q, -ex);
                     g[2] = g[3] = 0.f;
                 } else {  // the product rule per position
                     rows = 2 + (int)((xt >> 12) & 3u);
