@@ -24,6 +24,15 @@ the derivative tests have three kinds of arrays, hence three rules -- all intend
     instead, the lanes of a column being of one size.  The coefficients are the same.  Columns the oracle holds (almost) at zero have
     no unit of their own: null_columns() finds them, NULL_COLUMNS says why each is one, and their callers check them apart.  Right
     whenever the columns are not hand-picked.  Users: test_gpu_param_derivatives_all, test_param_derivative_columns_host.
+
+The hidden env state (the cartpole's previous th_ddot, the ball balancer's two plate angles) is part of the differentiated input of
+every reverse-mode sweep, rows S .. S + H - 1 of d_init, and of the carried tangents VS_ROLLOUT_SENS.  Both go by the PER-COLUMN rule
+(check_hidden_block, check_tangents), each hidden column per HIDDEN_SCALE, and are NOT further columns of the per-lane rule: inside one
+lane the hidden column is not of the size of that lane's state columns.  A cartpole lane's d Phi / d th_ddot_prev -- the Coulomb
+friction's normal-force term, d f_normal / d th_ddot_prev = -m_p l_p / 2 sin th -- is between 2e-9 and 1.1e-4 of the lane's largest
+state column (median 8e-7), all of it below the lane's floor 3e-4 max |g_smooth|: per lane a sweep that returned 0 or the wrong sign
+there would pass (test_hidden_adjoint_host pins that).  Over the lanes the entries of one hidden column ARE of one size, which is
+what the per-column floor needs.  The hidden columns also have central-difference steps of their own, HIDDEN_STEPS: see there.
 """
 import functools
 from typing import NamedTuple
@@ -43,6 +52,16 @@ WRT = {"omo": [0, 1, 2], "bob": [0, 1, 3, 6], "qq-su": [1, 2, 6, 8], "qcp-su": [
 # full initial states well inside the state space: uniform in +- these
 INIT_SCALE = {"omo": [0.5, 1.0], "bob": [0.5, 0.1, 0.3, 0.1], "qq-su": [0.5, 1.0, 2.0, 3.0], "qcp-su": [0.1, 1.0, 0.3, 2.0],
               "pend": [2.0, 2.0], "qbb": [0.1, 0.1, 0.05, 0.05, 0.5, 0.5, 0.1, 0.1]}
+# the unit of a hidden column (as INIT_SCALE is the unit of a state column) and the half-width of the non-trivial hidden start: 20 rad/s^2
+# of th_ddot_prev keeps the cartpole's normal force positive (the smooth branch), 0.05 rad is the size of the plate angles themselves
+HIDDEN_SCALE = {"qcp-su": [20.0], "qbb": [0.05, 0.05]}
+# Relative central-difference steps for HIDDEN columns, in units of HIDDEN_SCALE.  NOT the (1e-6, 1e-5) of every other column, and not
+# to be unified with them: |Phi| is about 10 and a cartpole entry about 2e-5, so at 1e-6 the difference of two Phi cancels to the last
+# three digits of fp64 and half the cartpole entries come out "not smooth" by rounding alone.  Phi is smooth in h_0 on the scale of
+# HIDDEN_SCALE (the normal force keeps its sign), so the larger steps cost no truncation error: at (1e-4, 1e-3) every entry is smooth.
+HIDDEN_STEPS = (1e-4, 1e-3)
+HIDDEN_FAMILIES = ("qcp-su", "qbb")
+STARTS = ("reset", "perturbed")  # the hidden state that reset leaves, and hidden_start()
 # 150 lanes (three waves, the last one partial), T = 24 steps in launches of 7 + 1 + 16 against one uncut launch, lanes 0 .. 9 at the edge
 N, MAX_STEPS, T, SPLITS, N_EDGE = 150, 50, 24, (7, 1, 16), 10
 # what a derivative call must leave untouched on the handle
@@ -88,6 +107,25 @@ def frozen(c, *more):
     return c
 
 
+def reset_hidden(c):
+    """[N, H] float64: the hidden state the oracle's reset leaves under the case's parameters and initial states"""
+    return c["ref"].reset(c["params"].astype(np.float64), c["init"].astype(np.float64), True)["hidden"]
+
+
+def hidden_start(name, c):
+    """[N, H] float32, read-only: a non-trivial initial hidden state for the case c (ref, params, init), the oracle's reset hidden state
+    plus uniform +-HIDDEN_SCALE -- the same draws for every case of a family"""
+    h0 = reset_hidden(c)
+    out = (h0 + np.random.default_rng(29).uniform(-1.0, 1.0, h0.shape) * np.array(HIDDEN_SCALE[name])).astype(np.float32)
+    out.setflags(write=False)
+    return out
+
+
+def start_hidden(name, c, start):
+    """[N, H] float64: the oracle's initial hidden state of a start in STARTS"""
+    return reset_hidden(c) if start == "reset" else hidden_start(name, c).astype(np.float64)
+
+
 def playback_case(name):
     """the inputs of a family's playback rollouts, all float32: params [N, P], init [N, S], acts [N, T, A] strictly inside the box and
     outside the dead zones, and the cotangents g_rew [N, T], g_obs [N, T + 1, O], g_last [N, S + H] -> (the case, not yet frozen, and
@@ -96,7 +134,7 @@ def playback_case(name):
     rng = np.random.default_rng(23)
     params, init = draw_params_and_init(ref, name, rng)
     acts = (ACT_IN[name] * rng.uniform(0.3, 0.6, (N, T, ref.A)) * rng.choice([-1.0, 1.0], (N, T, ref.A))).astype(np.float32)
-    c = dict(ref=ref, params=params, init=init, acts=acts, g_rew=rng.normal(size=(N, T)).astype(np.float32),
+    c = dict(name=name, ref=ref, params=params, init=init, acts=acts, g_rew=rng.normal(size=(N, T)).astype(np.float32),
              g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
     return c, rng
 
@@ -179,18 +217,19 @@ class ParamOracle(NamedTuple):
 
 
 @functools.lru_cache(maxsize=None)
-def all_param_oracle(name):
+def all_param_oracle(name, start="reset"):
     """Central differences of Phi (phi_and_obs, the cotangents of params_case(name)) with respect to EVERY domain parameter of every
     lane, the step h PARAM_UNIT ADDED to the parameter (a relative step cannot move a zero), h = 1e-6 and 1e-5, per PARAM_UNIT; and
     from the same perturbed rollouts the gradient and the diagonal of the Gauss-Newton matrix of the weighted squared discrepancy
     against the target obs - resid under the case's weights.  The initial
-    hidden state comes from the oracle's reset under the unperturbed parameters and is held; a lane's length is held at its
-    unperturbed value (the branch taken); the actions lie strictly inside every lane's box, so a moved bound changes nothing."""
+    hidden state comes from the oracle's reset under the unperturbed parameters (start = "perturbed": it is hidden_start()) and is
+    held; a lane's length is held at its unperturbed value (the branch taken); the actions lie strictly inside every lane's box, so
+    a moved bound changes nothing."""
     c = params_case(name)
     ref = c["ref"]
     P0 = c["params"].astype(np.float64)
     s0, a0 = c["init"].astype(np.float64), c["acts"].astype(np.float64)
-    h0 = ref.reset(P0, s0, True)["hidden"]
+    h0 = start_hidden(name, c, start)
     length = lengths_of(oracle_rollout(ref, P0, s0, h0, a0).done)
     unit = PARAM_UNIT(name, P0)
     summed = ((np.arange(T + 1)[:, None] >= 1) & (np.arange(T + 1)[:, None] <= length[None, :]))[:, :, None]  # [T + 1, N, 1]
@@ -216,6 +255,134 @@ def all_param_oracle(name):
     return o
 
 
+# ------------------------------------------------------------------------------------ the hidden block and the tangents
+def hidden_differences(name, f, h0):
+    """central differences of f(hidden0) -> [N] with respect to every entry of the initial hidden state h0 [N, H] at the steps
+    HIDDEN_STEPS x HIDDEN_SCALE, per HIDDEN_SCALE: two arrays [N, H].  What f holds (lane lengths, a policy's own state, noise) is
+    held."""
+    out = []
+    for h in HIDDEN_STEPS:
+        g = np.zeros(h0.shape)
+        for j in range(h0.shape[1]):
+            d = np.zeros_like(h0)
+            d[:, j] = h * HIDDEN_SCALE[name][j]
+            g[:, j] = (f(h0 + d) - f(h0 - d)) / (2.0 * h)
+        out.append(g)
+    return out[0], out[1]
+
+
+@functools.lru_cache(maxsize=None)
+def open_loop_hidden_reference(name, start):
+    """the hidden block of the open-loop sweeps (vs_rollout_vjp, vs_rollout_vjp_params) on params_case(name) -- playback_case's draws
+    -- from a start in STARTS: hidden_differences of Phi [N, H] x 2, the oracle's lane lengths, and the initial hidden state"""
+    c = params_case(name)
+    P0, s0, a0 = (c[k].astype(np.float64) for k in ("params", "init", "acts"))
+    h0 = start_hidden(name, c, start)
+    length = lengths_of(oracle_rollout(c["ref"], P0, s0, h0, a0).done)
+    g1, g2 = hidden_differences(name, lambda h: phi(c, P0, P0, s0, h, a0, length), h0)
+    return g1, g2, length, h0
+
+
+def hidden_conditions(tag, g1, g2):
+    """what the oracle alone must meet before a device value is looked at -> the smooth mask [N, H]: at most 1 % of the hidden block
+    not smooth, and no column without a smooth entry (tolerance_per_column raises on one)"""
+    smooth = smooth_per_column(g1, g2)
+    assert (~smooth).mean() <= 0.01, (tag, float((~smooth).mean()))
+    tolerance_per_column(g1, smooth)
+    return smooth
+
+
+def check_hidden_block(tag, got, g1, g2):
+    """got [N, H] (scaled_hidden) against the oracle's hidden block by the per-column rule; prints worst error / tolerance per column"""
+    smooth = hidden_conditions(tag, g1, g2)
+    assert np.isfinite(got).all(), tag
+    bad, worst = within_per_column(got, g1, smooth)
+    print(f"{tag}: hidden block: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance per column "
+          + ", ".join(f"{w:.4f}" for w in worst))
+    assert bad <= 2e-3, (tag, bad, worst.round(4).tolist())
+    return worst
+
+
+class TangentOracle(NamedTuple):
+    f1: np.ndarray      # [N, (S + H) G]: d (s_L, h_L)[j] / d log theta_k in column j G + k, central differences at h = 1e-6
+    f2: np.ndarray      # the same at h = 1e-5
+    length: np.ndarray  # [N]: the oracle's lane lengths
+    theta: np.ndarray   # [N, G]: the WRT parameters of every lane
+
+
+@functools.lru_cache(maxsize=None)
+def tangent_oracle(name):
+    """what VS_ROLLOUT_SENS holds after the playback rollout of params_case(name) under the WRT parameters: the state and hidden state
+    at the lane's end L per unit relative change of a parameter.  Central differences at relative steps 1e-6 and 1e-5, the initial
+    hidden state (the oracle's reset under the unperturbed parameters) and the lane's length held: the kernel's convention."""
+    c = params_case(name)
+    ref, wrt = c["ref"], WRT[name]
+    P0, s0, a0 = (c[k].astype(np.float64) for k in ("params", "init", "acts"))
+    h0 = reset_hidden(c)
+    length = lengths_of(oracle_rollout(ref, P0, s0, h0, a0).done)
+    lanes = np.arange(N)
+
+    def end_of(P):
+        r = oracle_rollout(ref, P, s0, h0, a0)
+        return np.concatenate([r.states[length, lanes], r.hiddens[length, lanes]], axis=1)  # [N, S + H]
+
+    out = []
+    for h in (1e-6, 1e-5):
+        g = np.zeros((N, ref.S + ref.H, len(wrt)))
+        for k, pk in enumerate(wrt):
+            lo, hi = P0.copy(), P0.copy()
+            hi[:, pk] *= 1.0 + h
+            lo[:, pk] *= 1.0 - h
+            g[:, :, k] = (end_of(hi) - end_of(lo)) / (2.0 * h)
+        out.append(g.reshape(N, -1))
+    o = TangentOracle(out[0], out[1], length, P0[:, wrt])
+    for a in o:
+        a.setflags(write=False)
+    return o
+
+
+# The (row of (s, h), position in WRT) columns of VS_ROLLOUT_SENS that the oracle holds at zero, under the WRT sets.  Only the ball
+# balancer has any, WRT = (ball_mass, arm_radius, motor_back_emf, motor_resistance): in this model the ball does not load the servos,
+# th_ddot = (A_m V - B_eq_v th_dot) / J_eq holds neither ball_mass nor arm_radius, so the servo angles (rows 0, 1) and their rates
+# (rows 4, 5) have no tangent along either; the plate angles of the hidden state (rows 8, 9) follow the servo angles through
+# c_kin = 2 r_arm / l_plate, which leaves them without a tangent along ball_mass alone.  (ball_mass does reach the ball's own rows: it
+# does not cancel against the ball's damping term.)
+NULL_TANGENTS = {"omo": [], "bob": [], "qq-su": [], "qcp-su": [], "pend": [],
+                 "qbb": [(0, 0), (0, 1), (1, 0), (1, 1), (4, 0), (4, 1), (5, 0), (5, 1), (8, 0), (9, 0)]}
+
+
+def tangents_conditions(name):
+    """from the oracle alone -> (the oracle, null [C] bool, smooth [N, live columns]): the null columns are NULL_TANGENTS, at most 1 %
+    of the live entries not smooth, no live column without a smooth entry"""
+    o = tangent_oracle(name)
+    null = null_columns(o.f1, o.f2)
+    assert [divmod(int(q), len(WRT[name])) for q in np.flatnonzero(null)] == NULL_TANGENTS[name], name
+    live = ~null
+    smooth = smooth_per_column(o.f1[:, live], o.f2[:, live])
+    assert (~smooth).mean() <= 0.01, (name, float((~smooth).mean()))
+    tolerance_per_column(o.f1[:, live], smooth)
+    return o, null, smooth
+
+
+def check_tangents(name, got):
+    """got [N, (S + H) G] per unit relative change of the parameter (column j G + k: row j, parameter k) against tangent_oracle by the
+    per-column rule, the null columns apart; prints worst error / tolerance per column"""
+    o, null, smooth = tangents_conditions(name)
+    live = ~null
+    assert np.isfinite(got).all(), name
+    bad, worst = within_per_column(got[:, live], o.f1[:, live], smooth)
+    G = len(WRT[name])
+    print(f"{name}: tangents: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst.max():.4f} at (row, "
+          f"parameter) {divmod(int(np.flatnonzero(live)[worst.argmax()]), G)}; null columns {[divmod(int(q), G) for q in np.flatnonzero(null)]}")
+    floor = CANCEL_FLOOR * np.abs(o.f1[:, live]).max(axis=0).min()
+    if null.any():
+        top = float(np.abs(got[:, null]).max())
+        print(f"{name}: tangents: largest entry of a null column {top:.3e}, floor {floor:.3e}")
+        assert top < floor, (name, top, floor)
+    assert bad <= 2e-3, (name, bad, worst.round(3).tolist())
+    return worst
+
+
 def action_window(name, output_nonlin):
     """(lo, hi) of |a| under a network policy made as the FNN and RNN test modules make theirs: section 8e's box, or the tanh output's"""
     return (0.51, 0.83) if output_nonlin == "tanh" else (0.30 * ACT_IN[name], 0.60 * ACT_IN[name])
@@ -236,15 +403,20 @@ def dev(x):
     return torch.as_tensor(np.array(x)).cuda()  # (a copy: the case arrays are read-only)
 
 
-def record_mode2(e, capacity, params, set_policy, init, splits, **step_kw):
+def record_mode2(e, capacity, params, set_policy, init, splits, hidden=None, **step_kw):
     """rows 0 .. sum(splits) - 1 of the handle e hold the rollouts under the policy that set_policy(e) installs, from init under params,
-    recorded in mode 2 by step_policy(k, record=True, **step_kw) in launches of `splits` steps -> e"""
+    recorded in mode 2 by step_policy(k, record=True, **step_kw) in launches of `splits` steps -> e.  hidden [n, H] float32: the
+    initial hidden state in place of the one reset leaves (the caller checks it with check_hidden_start)"""
     e.set_auto_reset(False)
     e.set_record_mode(2)
     e.set_traj_capacity(capacity)
     e.set_params(params)
     set_policy(e)
     e.reset(init_state=init)
+    if hidden is not None:
+        from simurlacra_amd import _lib as L
+
+        e.put(L.VS_HIDDEN, hidden)
     t0 = 0
     for k in splits:
         e.set_traj_offset(t0)
@@ -262,12 +434,31 @@ def case_cotangents(vs, c, e, t_steps=T, last="g_state_last"):
 
 
 def scaled(vs, c, d_act, d_init, n=N):
-    """d_act [T, A, ld] and d_init [S + H, ld] of the device -> [n, T A + S] float64 per unit of the inputs' scales (ACT_IN, INIT_SCALE)"""
+    """d_act [T, A, ld] and d_init [S + H, ld] of the device -> [n, T A + S] float64 per unit of the inputs' scales (ACT_IN, INIT_SCALE).
+    The hidden rows of d_init are cut off here on purpose: they are no further columns of a lane's row (the module docstring says why)
+    and go through scaled_hidden() and check_hidden_block() in a test of their own next to every caller's oracle test."""
     ref, name = c["ref"], c["name"]
     d_act, d_init = vs.lanes_first(d_act, n).cpu().numpy(), vs.lanes_first(d_init, n).cpu().numpy()
     got = np.concatenate([d_act.reshape(n, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
     assert np.isfinite(got).all()
     return got.astype(np.float64)
+
+
+def scaled_hidden(vs, c, d_init, n=N):
+    """d_init [S + H, ld] of the device -> [n, H] float64: its hidden rows per HIDDEN_SCALE; lanes >= n of them must hold 0"""
+    ref = c["ref"]
+    assert not bool(d_init[ref.S:, n:].any())
+    got = vs.lanes_first(d_init, n).cpu().numpy()[:, ref.S:].astype(np.float64) * np.array(HIDDEN_SCALE[c["name"]])
+    assert got.shape == (n, ref.H) and np.isfinite(got).all()
+    return got
+
+
+def check_hidden_start(e, hidden, length, n=N, t_steps=T):
+    """after record_mode2(..., hidden=hidden): row 0 of the mode-2 record holds exactly those bits, and the lanes' lengths are the
+    oracle's from the same initial hidden state"""
+    row0 = e.traj_tensors(1, n)["hidden"][0].cpu().numpy()
+    assert np.array_equal(row0.view(np.uint32), np.asarray(hidden[:n]).view(np.uint32))
+    assert np.array_equal(e.rollout_lengths(n, t_steps)[0].cpu().numpy(), length[:n])
 
 
 # ---------------------------------------------------------------------------------------------- the tolerance, per lane

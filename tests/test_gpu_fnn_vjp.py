@@ -32,9 +32,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, TANH_OUT_AMP, TANH_OUT_AT,  # noqa: E402
-                              check_net_keeps_the_box, dev, draw_params_and_init, frozen, lengths_of, record_mode2, scaled,
-                              smooth_per_lane, tolerance_per_lane, worst_of)
+from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T, TANH_OUT_AMP,  # noqa: E402
+                              TANH_OUT_AT, check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev, draw_params_and_init, frozen,
+                              hidden_conditions, hidden_differences, hidden_start, lengths_of, record_mode2, scaled, scaled_hidden,
+                              smooth_per_lane, start_hidden, tolerance_per_lane, worst_of)
 
 # case -> (family, hidden sizes, hidden nonlinearities, output nonlinearity, feat, obs_idx, seed, gain of the output layer)
 CASES = {
@@ -158,9 +159,10 @@ def case(key):
     return frozen(c, *net["W"], *net["b"])
 
 
-def phi(c, state0, offs, length, open_acts=None):
+def phi(c, state0, offs, length, open_acts=None, hidden0=None):
     """test_gpu_policy_vjp's phi for the network's closed loop"""
-    states, hiddens, obs, rew, _, acts, _ = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"], c["net"], offs, open_acts)
+    states, hiddens, obs, rew, _, acts, _ = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"] if hidden0 is None else hidden0,
+                                                        c["net"], offs, open_acts)
     k = np.arange(T + 1)[:, None]
     n = np.arange(state0.shape[0])
     inside = k[:T] < length[None, :]
@@ -171,12 +173,14 @@ def phi(c, state0, offs, length, open_acts=None):
     return out + (c["g_last"].astype(np.float64) * last).sum(axis=1)
 
 
-def reference(c, offs0):
+def reference(c, offs0, h0=None):
     """test_gpu_policy_vjp's reference: central differences of Phi at relative steps 1e-6 and 1e-5 [N, T A + S] (offsets first, step-major), the lane
-    lengths, the oracle's actions [T, N, A], d_init [N, S] of the OPEN loop along them, and the hidden pre-activations"""
+    lengths, the oracle's actions [T, N, A], d_init [N, S] of the OPEN loop along them, and the hidden pre-activations; h0: the initial
+    hidden state (None: the one the oracle's reset leaves)"""
     ref, name = c["ref"], c["name"]
     s0 = c["init"].astype(np.float64)
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, c["h0"], c["net"], offs0)
+    h0 = c["h0"] if h0 is None else h0
+    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["net"], offs0)
     length, acts = lengths_of(roll[4]), roll[5]
     out = []
     for h in (1e-6, 1e-5):
@@ -185,25 +189,38 @@ def reference(c, offs0):
             for j in range(ref.A):
                 d = np.zeros_like(offs0)
                 d[:, t, j] = h * ACT_IN[name]
-                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length) - phi(c, s0, offs0 - d, length)) / (2.0 * h)
+                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length, hidden0=h0) - phi(c, s0, offs0 - d, length, hidden0=h0)) / (2.0 * h)
         for j in range(ref.S):
             d = np.zeros_like(s0)
             d[:, j] = h * INIT_SCALE[name][j]
-            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length) - phi(c, s0 - d, offs0, length)) / (2.0 * h)
+            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length, hidden0=h0) - phi(c, s0 - d, offs0, length, hidden0=h0)) / (2.0 * h)
         out.append(g)
     open_init = np.zeros((N, ref.S))
     fixed = acts.transpose(1, 0, 2)
     for j in range(ref.S):
         d = np.zeros_like(s0)
         d[:, j] = 1e-6 * INIT_SCALE[name][j]
-        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed) - phi(c, s0 - d, offs0, length, fixed)) / 2e-6
+        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed, hidden0=h0) - phi(c, s0 - d, offs0, length, fixed, hidden0=h0)) / 2e-6
     return out[0], out[1], length, acts, open_init, roll[6]
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_reference(key):
+def oracle_reference(key, start="reset"):
     c = case(key)
-    return reference(c, np.zeros((N, T, c["ref"].A)))
+    return reference(c, np.zeros((N, T, c["ref"].A)), start_hidden(c["name"], c, start))
+
+
+@functools.lru_cache(maxsize=None)
+def hidden_reference(key, start):
+    """the hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the network has no state of its
+    own and no noise; the lane lengths are held), and the oracle's lane lengths"""
+    c = case(key)
+    h0 = start_hidden(c["name"], c, start)
+    offs0 = np.zeros((N, T, c["ref"].A))
+    s0 = c["init"].astype(np.float64)
+    length = lengths_of(closed_loop(c["ref"], c["params"].astype(np.float64), s0, h0, c["net"], offs0)[4])
+    g1, g2 = hidden_differences(c["name"], lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
+    return g1, g2, length
 
 
 def set_net(e, net, noise_std=None):
@@ -211,8 +228,9 @@ def set_net(e, net, noise_std=None):
                      feat=net["feat"], obs_idx=net["obs_idx"], noise_std=noise_std)
 
 
-def recorded(vs, key, splits=(T,), noise_seed=0, n=N, shape=None, net=None, spec=None):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case (lanes >= N repeat its lanes), recorded in mode 2"""
+def recorded(vs, key, splits=(T,), noise_seed=0, n=N, shape=None, net=None, spec=None, hidden=None):
+    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case (lanes >= N repeat its lanes), recorded in mode 2; hidden
+    [n, H]: the initial hidden state in place of reset's"""
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
@@ -226,7 +244,7 @@ def recorded(vs, key, splits=(T,), noise_seed=0, n=N, shape=None, net=None, spec
             e.set_policy_shape(shape)
 
     return record_mode2(e, T, np.resize(c["params"], (n, c["params"].shape[1])), policy, np.resize(c["init"], (n, c["init"].shape[1])), splits,
-                        noise_seed=noise_seed)
+                        hidden=hidden, noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True, n=N):
@@ -276,6 +294,8 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     cot = cotangents(vs, key, e)
     got = scaled(vs, c, *e.rollout_vjp_fnn(T, **cot))
     # ---- 2. the feedback is there: along the same records the open-loop sweep's d_init is off where the oracle says it must be
+    # (state columns only: the feedback enters through the observations, which no hidden state reaches; the hidden rows of both sweeps
+    # have their own tests, test_hidden_adjoint_against_the_closed_loop_fp64_oracle here and in test_gpu_rollout_vjp.py)
     _, oi = e.rollout_vjp(T, **{k: v for k, v in cot.items() if k != "g_act"})
     open_got = vs.lanes_first(oi, N).cpu().numpy()[:, :ref.S].astype(np.float64) * np.array(INIT_SCALE[c["name"]])
     init_cols = slice(T * ref.A, None)
@@ -287,6 +307,42 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
           f"worst error / tolerance {worst:.3f}")
     assert differs[length == T].mean() >= 0.5, (key, float(differs[length == T].mean()))
     assert worst <= 1.0, (key, worst)
+
+
+HIDDEN_CASES = {"qcp-su": "qcp-su-32x33", "qbb": "qbb-31x64-tanh-out"}
+
+
+@pytest.mark.parametrize("start", STARTS)
+@pytest.mark.parametrize("name", HIDDEN_FAMILIES)
+def test_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, name, start):
+    """Rows S .. S + H - 1 of d_init (scaled() cuts them off: they have another unit and another rule) against central differences of the
+    closed loop's Phi at HIDDEN_STEPS x HIDDEN_SCALE, per column and per HIDDEN_SCALE, from the hidden state that reset leaves and from
+    hidden_start(); edge lanes like any other, lanes >= n exactly 0.  From hidden_start() the offset and state columns go through test
+    1's check as well (every entry smooth, every entry held), the network keeps the box and stays off its kinks.  Worst error /
+    tolerance per column as measured on the MI355X (printed with -s): DESIGN.md section 8d."""
+    key = HIDDEN_CASES[name]
+    c = case(key)
+    g1, g2, length = hidden_reference(key, start)
+    hidden_conditions(key, g1, g2)  # from the oracle alone, before the device is asked
+    hidden = hidden_start(name, c) if start == "perturbed" else None
+    e = recorded(vs, key, hidden=hidden)
+    if hidden is None:
+        assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    else:
+        check_hidden_start(e, hidden, length)
+    da, di = e.rollout_vjp_fnn(T, **cotangents(vs, key, e))
+    assert e.error_count() == 0 and e.ld > N and not da[..., N:].any() and not di[..., N:].any()
+    e.close()
+    check_hidden_block(f"{key} vs_rollout_vjp_fnn from {start}", scaled_hidden(vs, c, di), g1, g2)
+    if start == "perturbed":
+        f1, f2, length2, acts, _, pres = oracle_reference(key, start)
+        smooth = smooth_per_lane(f1, f2)
+        assert np.array_equal(length2, length) and smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
+        check_net_keeps_the_box(c, acts, length)
+        check_no_unit_near_a_kink(c, pres, length)
+        worst = worst_of(scaled(vs, c, da, di), f1, smooth)
+        print(f"{key} from {start}: offsets and states: worst error / tolerance {worst:.3f}")
+        assert worst <= 1.0, (key, worst)
 
 
 def test_exploration_noise_is_an_additive_constant(vs):

@@ -30,8 +30,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (CANCEL_FLOOR, FAMILIES, KW, MAX_STEPS, N, N_EDGE, NULL_COLUMNS, STATE_BUFFERS, T, all_param_oracle,  # noqa: E402
-                              case_cotangents, dev, null_columns, params_case, record_mode2, smooth_per_column, within_per_column)
+from derivative_cases import (CANCEL_FLOOR, FAMILIES, HIDDEN_FAMILIES, KW, MAX_STEPS, N, NULL_COLUMNS, N_EDGE, STARTS, STATE_BUFFERS, T,  # noqa: E402
+                              all_param_oracle, case_cotangents, check_hidden_block, check_hidden_start, dev, hidden_conditions, hidden_start,
+                              null_columns, open_loop_hidden_reference, params_case, record_mode2, scaled_hidden, smooth_per_column,
+                              within_per_column)
 
 ENVS = {"qq-su": "QQubeSwingUpSim", "qcp-su": "QCartPoleSwingUpSim", "qbb": "QBallBalancerSim"}
 
@@ -50,11 +52,12 @@ def passes_of_four(P):
     return [list(range(j, min(j + 4, P))) for j in range(0, P, 4)]
 
 
-def recorded(vs, name):
-    """a handle whose rows 0 .. T - 1 hold the playback rollouts of the case, recorded in mode 2 in one launch"""
+def recorded(vs, name, hidden=None):
+    """a handle whose rows 0 .. T - 1 hold the playback rollouts of the case, recorded in mode 2 in one launch; hidden [N, H]: the
+    initial hidden state in place of reset's"""
     c = params_case(name)
     e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
-    return record_mode2(e, T, c["params"], lambda e: e.set_policy_playback(c["acts"]), c["init"], (T,))
+    return record_mode2(e, T, c["params"], lambda e: e.set_policy_playback(c["acts"]), c["init"], (T,), hidden=hidden)
 
 
 def sweep_all(vs, e, P, **cot):
@@ -117,6 +120,38 @@ def test_reverse_mode_every_parameter_against_the_fp64_oracle(vs, name):
     assert e.error_count() == 0
     e.close()
     check_columns(name, "reverse mode", got, o.f1, o.f2)
+
+
+@pytest.mark.parametrize("start", STARTS)
+@pytest.mark.parametrize("name", HIDDEN_FAMILIES)
+def test_reverse_mode_hidden_adjoint_and_the_same_bits(vs, name, start):
+    """vs_rollout_vjp_params promises vs_rollout_vjp's bits for d_act and d_init: the full [S + H] rows are compared with array_equal
+    from the hidden state that reset leaves and from hidden_start(), and the hidden rows are held to the oracle per column like
+    vs_rollout_vjp's own (test_gpu_rollout_vjp.py).  From hidden_start() all P columns of d_params are compared with the all-parameter
+    oracle recomputed from that start.  Worst error / tolerance is printed with -s (DESIGN.md sections 8d and 8k)."""
+    c = params_case(name)
+    g1, g2, length, _ = open_loop_hidden_reference(name, start)
+    hidden_conditions(name, g1, g2)  # from the oracle alone, before the device is asked
+    hidden = hidden_start(name, c) if start == "perturbed" else None
+    e = recorded(vs, name, hidden=hidden)
+    if hidden is None:
+        assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    else:
+        check_hidden_start(e, hidden, length)
+    cot = case_cotangents(vs, c, e, T, last="g_last")
+    P = vs.env_dims(name)["P"]
+    da, di, _ = e.rollout_vjp_params(T, [0], **cot)
+    ra, ri = e.rollout_vjp(T, g_rew=cot["g_rew"], g_obs=cot["g_obs"], g_state_last=cot["g_last"])
+    assert tuple(di.shape) == (c["ref"].S + c["ref"].H, e.ld) and torch.equal(da, ra) and torch.equal(di, ri)
+    assert e.ld > N and not di[:, N:].any()
+    check_hidden_block(f"{name} vs_rollout_vjp_params from {start}", scaled_hidden(vs, c, di), g1, g2)
+    if start == "perturbed":
+        o = all_param_oracle(name, start)
+        assert np.array_equal(o.length, length)
+        got = sweep_all(vs, e, P, **cot).cpu().numpy().astype(np.float64) * o.unit  # (every pass: the first pass's d_act and d_init)
+        check_columns(name, f"reverse mode from {start}", got, o.f1, o.f2)
+    assert e.error_count() == 0
+    e.close()
 
 
 # --------------------------------------------------------------------------------------------------------- forward mode

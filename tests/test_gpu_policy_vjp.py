@@ -28,9 +28,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, case_cotangents, dev,  # noqa: E402
-                              draw_params_and_init, frozen, lengths_of, record_mode2, scaled, smooth_per_lane, tolerance_per_lane,
-                              within_per_lane)
+from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STARTS, STATE_BUFFERS, T,  # noqa: E402
+                              case_cotangents, check_hidden_block, check_hidden_start, dev, draw_params_and_init, frozen, hidden_conditions,
+                              hidden_differences, hidden_start, lengths_of, record_mode2, scaled, scaled_hidden, smooth_per_lane, start_hidden,
+                              tolerance_per_lane, within_per_lane)
 
 ELEM = ("identity", "squared", "cubic", "sig", "bell", "sin", "cos", "sinsin", "sincos")
 SMALL = ("identity", "sin", "const", ("mult", (0, 1)))
@@ -136,10 +137,11 @@ def case(key):
                        g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32)))
 
 
-def phi(c, state0, offs, length, open_acts=None):
-    """[N]: sum g_rew r + sum g_obs . obs + sum g_act . a + g_last . (s_L, h_L) of every lane over its first length[n] steps"""
-    states, hiddens, obs, rew, _, acts = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"], c["terms"], c["obs_idx"],
-                                                     c["W"].astype(np.float64), offs, open_acts)
+def phi(c, state0, offs, length, open_acts=None, hidden0=None):
+    """[N]: sum g_rew r + sum g_obs . obs + sum g_act . a + g_last . (s_L, h_L) of every lane over its first length[n] steps, from the
+    initial hidden state hidden0 (None: the one the oracle's reset leaves)"""
+    states, hiddens, obs, rew, _, acts = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"] if hidden0 is None else hidden0,
+                                                     c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs, open_acts)
     k = np.arange(T + 1)[:, None]
     n = np.arange(state0.shape[0])
     inside = k[:T] < length[None, :]
@@ -150,12 +152,14 @@ def phi(c, state0, offs, length, open_acts=None):
     return out + (c["g_last"].astype(np.float64) * last).sum(axis=1)
 
 
-def reference(c, offs0):
+def reference(c, offs0, h0=None):
     """central differences of Phi at relative steps 1e-6 and 1e-5: two arrays [N, T * A + S] (offsets first, step-major), the
-    oracle's lane lengths, its actions [T, N, A], and d_init [N, S] of the OPEN loop along those actions (step 1e-6)"""
+    oracle's lane lengths, its actions [T, N, A], and d_init [N, S] of the OPEN loop along those actions (step 1e-6); h0: the initial
+    hidden state (None: the one the oracle's reset leaves)"""
     ref, name = c["ref"], c["name"]
     s0 = c["init"].astype(np.float64)
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, c["h0"], c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)
+    h0 = c["h0"] if h0 is None else h0
+    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)
     length, acts = lengths_of(roll[4]), roll[5]
     out = []
     for h in (1e-6, 1e-5):
@@ -164,29 +168,43 @@ def reference(c, offs0):
             for j in range(ref.A):
                 d = np.zeros_like(offs0)
                 d[:, t, j] = h * ACT_IN[name]
-                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length) - phi(c, s0, offs0 - d, length)) / (2.0 * h)
+                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length, hidden0=h0) - phi(c, s0, offs0 - d, length, hidden0=h0)) / (2.0 * h)
         for j in range(ref.S):
             d = np.zeros_like(s0)
             d[:, j] = h * INIT_SCALE[name][j]
-            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length) - phi(c, s0 - d, offs0, length)) / (2.0 * h)
+            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length, hidden0=h0) - phi(c, s0 - d, offs0, length, hidden0=h0)) / (2.0 * h)
         out.append(g)
     open_init = np.zeros((N, ref.S))
     fixed = acts.transpose(1, 0, 2)
     for j in range(ref.S):
         d = np.zeros_like(s0)
         d[:, j] = 1e-6 * INIT_SCALE[name][j]
-        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed) - phi(c, s0 - d, offs0, length, fixed)) / 2e-6
+        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed, hidden0=h0) - phi(c, s0 - d, offs0, length, fixed, hidden0=h0)) / 2e-6
     return out[0], out[1], length, acts, open_init
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_reference(key):
+def oracle_reference(key, start="reset"):
     c = case(key)
-    return reference(c, np.zeros((N, T, c["ref"].A)))
+    return reference(c, np.zeros((N, T, c["ref"].A)), start_hidden(c["name"], c, start))
 
 
-def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case, recorded in mode 2 by step_policy in the given launches"""
+@functools.lru_cache(maxsize=None)
+def hidden_reference(key, start):
+    """the hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the policy has no state of its
+    own and no noise; the lane lengths are held), and the oracle's lane lengths"""
+    c = case(key)
+    h0 = start_hidden(c["name"], c, start)
+    offs0 = np.zeros((N, T, c["ref"].A))
+    s0 = c["init"].astype(np.float64)
+    length = lengths_of(closed_loop(c["ref"], c["params"].astype(np.float64), s0, h0, c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)[4])
+    g1, g2 = hidden_differences(c["name"], lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
+    return g1, g2, length
+
+
+def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0, hidden=None):
+    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case, recorded in mode 2 by step_policy in the given launches;
+    hidden [N, H]: the initial hidden state in place of reset's"""
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
@@ -194,7 +212,7 @@ def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0):
     def linear(e):
         e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
 
-    return record_mode2(e, T, c["params"], linear, c["init"], splits, noise_seed=noise_seed)
+    return record_mode2(e, T, c["params"], linear, c["init"], splits, hidden=hidden, noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True):
@@ -243,6 +261,37 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     print(f"{key}: not smooth {(~smooth).mean():.4f}, feedback seen on {seen:.2f} of the full lanes, bad share {bad:.2e}, "
           f"worst error / tolerance {worst:.3f}")
     assert bad <= 2e-3, (key, bad, worst)
+
+
+@pytest.mark.parametrize("start", STARTS)
+@pytest.mark.parametrize("key", HIDDEN_FAMILIES)
+def test_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, key, start):
+    """Rows S .. S + H - 1 of d_init (scaled() cuts them off: they have another unit and another rule) against central differences of the
+    closed loop's Phi at HIDDEN_STEPS x HIDDEN_SCALE, per column and per HIDDEN_SCALE, from the hidden state that reset leaves and from
+    hidden_start(); edge lanes like any other, lanes >= n exactly 0.  From hidden_start() the offset and state columns go through test
+    1's per-lane check as well, and the policy still keeps the box.  Worst error / tolerance per column as measured on the MI355X
+    (printed with -s): DESIGN.md section 8d."""
+    c = case(key)
+    g1, g2, length = hidden_reference(key, start)
+    hidden_conditions(key, g1, g2)  # from the oracle alone, before the device is asked
+    hidden = hidden_start(c["name"], c) if start == "perturbed" else None
+    e = recorded(vs, key, hidden=hidden)
+    if hidden is None:
+        assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    else:
+        check_hidden_start(e, hidden, length)
+    da, di = e.rollout_vjp_policy(T, **cotangents(vs, key, e))
+    assert e.error_count() == 0 and e.ld > N and not da[..., N:].any() and not di[..., N:].any()
+    e.close()
+    check_hidden_block(f"{key} vs_rollout_vjp_policy from {start}", scaled_hidden(vs, c, di), g1, g2)
+    if start == "perturbed":
+        f1, f2, length2, acts, _ = oracle_reference(key, start)
+        smooth = smooth_per_lane(f1, f2)
+        assert np.array_equal(length2, length) and (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
+        check_policy_keeps_the_box(c, acts, length)
+        bad, worst = within_per_lane(scaled(vs, c, da, di), f1, smooth)
+        print(f"{key} from {start}: offsets and states: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
+        assert bad <= 2e-3, (key, bad, worst)
 
 
 # ------------------------------------------------------------------------------------ 3. reduction to the open-loop sweep

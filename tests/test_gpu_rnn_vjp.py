@@ -38,9 +38,10 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import test_rnn_vjp_host as cells  # noqa: E402  (the fp64 cells)
-from derivative_cases import (ACT_IN, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, TANH_OUT_AMP, TANH_OUT_AT,  # noqa: E402
-                              case_cotangents, check_net_keeps_the_box, dev, draw_params_and_init, frozen, lengths_of, record_mode2,
-                              smooth_per_lane, tolerance_per_lane, worst_of)
+from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T, TANH_OUT_AMP,  # noqa: E402
+                              TANH_OUT_AT, case_cotangents, check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev,
+                              draw_params_and_init, frozen, hidden_conditions, hidden_differences, hidden_start, lengths_of, record_mode2,
+                              scaled_hidden, smooth_per_lane, start_hidden, tolerance_per_lane, worst_of)
 
 # case -> (family, cell, layers, units, output nonlinearity, obs_idx, seed, gain of the output layer, whh)
 CASES = {
@@ -179,10 +180,12 @@ def case(key):
                        g_hid=rng.normal(size=(N, Hs)).astype(np.float32)))
 
 
-def phi(c, state0, offs, length, reps=1, **kw):
-    """[reps N]: Phi of every lane over its first length[n] steps; the lanes are `reps` copies of the case's"""
+def phi(c, state0, offs, length, reps=1, hidden0=None, **kw):
+    """[reps N]: Phi of every lane over its first length[n] steps; the lanes are `reps` copies of the case's; hidden0 [N, H]: the initial
+    hidden state of the env (None: the one the oracle's reset leaves)"""
     rp = lambda x: np.concatenate([x.astype(np.float64)] * reps)  # noqa: E731
-    states, hiddens, obs, rew, _, acts, ps, _ = closed_loop(c["ref"], rp(c["params"]), state0, rp(c["h0"]), c["net"], offs, **kw)
+    states, hiddens, obs, rew, _, acts, ps, _ = closed_loop(c["ref"], rp(c["params"]), state0, rp(c["h0"] if hidden0 is None else hidden0),
+                                                            c["net"], offs, **kw)
     length = np.concatenate([length] * reps)
     k = np.arange(T + 1)[:, None]
     n = np.arange(state0.shape[0])
@@ -197,12 +200,13 @@ def phi(c, state0, offs, length, reps=1, **kw):
 H1, H2 = 1e-6, 1e-5
 
 
-def central(c, length, s0, offs0, d_s=None, d_offs=None, d_p0=None, hid_off=None):
-    """central differences of Phi along one direction at both relative steps, the four perturbed rollouts in one batch of 4 N lanes"""
+def central(c, length, s0, offs0, d_s=None, d_offs=None, d_p0=None, hid_off=None, h0=None):
+    """central differences of Phi along one direction at both relative steps, the four perturbed rollouts in one batch of 4 N lanes; h0:
+    the env's initial hidden state (None: reset's)"""
     mult = np.repeat([H1, -H1, H2, -H2], N)
     st = np.concatenate([s0] * 4) + (0.0 if d_s is None else mult[:, None] * np.concatenate([d_s] * 4))
     of = np.concatenate([offs0] * 4) + (0.0 if d_offs is None else mult[:, None, None] * np.concatenate([d_offs] * 4))
-    kw = {}
+    kw = {} if h0 is None else {"hidden0": h0}
     if d_p0 is not None:
         kw["p0"] = mult[:, None] * np.concatenate([d_p0] * 4)
     if hid_off is not None:
@@ -252,6 +256,35 @@ def oracle_reference(key):
     return reference(c, np.zeros((N, T, c["ref"].A)))
 
 
+@functools.lru_cache(maxsize=None)
+def hidden_reference(key, start):
+    """the ENV's hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the policy's own initial
+    state p_0 = 0, no noise and the lane lengths are held); from hidden_start() also the first block of reference() -- action offsets and
+    initial state [N, T A + S] x 2 at the usual steps -- with the actions and Elman pre-activations; and the oracle's lane lengths"""
+    c = case(key)
+    ref, name = c["ref"], c["name"]
+    h0 = start_hidden(name, c, start)
+    offs0 = np.zeros((N, T, ref.A))
+    s0 = c["init"].astype(np.float64)
+    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["net"], offs0)
+    length = lengths_of(roll[4])
+    g1, g2 = hidden_differences(name, lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
+    if start == "reset":
+        return g1, g2, length, None
+    cols = []
+    for t in range(T):
+        for j in range(ref.A):
+            d = np.zeros_like(offs0)
+            d[:, t, j] = ACT_IN[name]
+            cols.append(central(c, length, s0, offs0, d_offs=d, h0=h0))
+    for j in range(ref.S):
+        d = np.zeros_like(s0)
+        d[:, j] = INIT_SCALE[name][j]
+        cols.append(central(c, length, s0, offs0, d_s=d, h0=h0))
+    f1, f2 = (np.stack([col[k] for col in cols], axis=1) for k in (0, 1))
+    return g1, g2, length, (f1, f2, roll[5], roll[7])
+
+
 def blocks_of(c):
     """column slices: (action offsets and initial state, the hidden entries)"""
     n1 = T * c["ref"].A + c["ref"].S
@@ -273,8 +306,9 @@ def set_rnn(e, net, noise_std=None):
     e.set_policy_hidden_record(cells.hidden_size(cn))
 
 
-def recorded(vs, key, splits=(T,), noise_seed=0, net=None, spec=None, cap=T, noise_std=None):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case and the hidden states before every step"""
+def recorded(vs, key, splits=(T,), noise_seed=0, net=None, spec=None, cap=T, noise_std=None, hidden=None):
+    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case and the hidden states before every step; hidden [N, H]:
+    the ENV's initial hidden state in place of reset's"""
     c = case(key)
     name = c["name"]
     e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
@@ -286,7 +320,7 @@ def recorded(vs, key, splits=(T,), noise_seed=0, net=None, spec=None, cap=T, noi
             e.set_policy_rnn(**spec)
             e.set_policy_hidden_record(c["Hs"])
 
-    return record_mode2(e, cap, c["params"], policy, c["init"], splits, noise_seed=noise_seed)
+    return record_mode2(e, cap, c["params"], policy, c["init"], splits, hidden=hidden, noise_seed=noise_seed)
 
 
 def cotangents(vs, key, e, with_act=True, with_hid=True):
@@ -300,6 +334,9 @@ def cotangents(vs, key, e, with_act=True, with_hid=True):
 
 
 def scaled(vs, c, d_act, d_init, d_hid, d_hid0):
+    """the four outputs as one array [N, T A + S + Hs + pairs] in the units of reference().  The ENV's hidden rows of d_init are cut off:
+    they are no further columns of a lane's row (derivative_cases.py says why) and go through scaled_hidden() and
+    check_hidden_block() in test_env_hidden_adjoint_against_the_closed_loop_fp64_oracle."""
     ref, name = c["ref"], c["name"]
     d_act, d_init, d_hid, d_hid0 = (vs.lanes_first(x, N).cpu().numpy() for x in (d_act, d_init, d_hid, d_hid0))
     picked = np.stack([d_hid[:, t, u] for t, u in c["pairs"]], axis=1)
@@ -354,6 +391,8 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     got = scaled(vs, c, *e.rollout_vjp_rnn(T, **cot))
     # ---- the feedback and the hidden adjoint are there: along the same records the open-loop sweep's d_init is off where the oracle
     # says it must be, and the device's d_init is off from the oracle's with eta cut
+    # (state columns only: gpol and eta enter through the observations, which no env hidden state reaches; the hidden rows of both
+    # sweeps have their own tests, test_env_hidden_adjoint_against_the_closed_loop_fp64_oracle here and in test_gpu_rollout_vjp.py)
     _, oi = e.rollout_vjp(T, **{k: v for k, v in cot.items() if k not in ("g_act", "g_hid_last")})
     open_got = vs.lanes_first(oi, N).cpu().numpy()[:, :ref.S].astype(np.float64) * np.array(INIT_SCALE[c["name"]])
     cols = slice(T * ref.A, T * ref.A + ref.S)
@@ -368,6 +407,43 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
           f"worst error / tolerance {worst:.4f}")
     assert dev_open >= 0.5 and dev_cut >= 0.5, (key, dev_open, dev_cut)
     assert worst <= 1.0, (key, worst)
+
+
+HIDDEN_CASES = {"qcp-su": "qcp-su-lstm-33", "qbb": "qbb-lstm-2x64-tanh-out"}
+
+
+@pytest.mark.parametrize("start", STARTS)
+@pytest.mark.parametrize("name", HIDDEN_FAMILIES)
+def test_env_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, name, start):
+    """Rows S .. S + H - 1 of d_init -- the adjoint of the ENV's hidden state, which scaled() cuts off: it has another unit and another rule
+    than a lane's state columns -- against central differences of the closed loop's Phi at HIDDEN_STEPS x HIDDEN_SCALE, per column and per
+    HIDDEN_SCALE, from the hidden state that reset leaves and from hidden_start(); edge lanes like any other, lanes >= n exactly 0.  From
+    hidden_start() the first block of test 1 (action offsets, initial state) goes through its check as well: every entry smooth, every
+    entry held, the policy inside the box.  Worst error / tolerance per column as measured on the MI355X (printed with -s): DESIGN.md
+    section 8d."""
+    key = HIDDEN_CASES[name]
+    c = case(key)
+    g1, g2, length, first = hidden_reference(key, start)
+    hidden_conditions(key, g1, g2)  # from the oracle alone, before the device is asked
+    hidden = hidden_start(name, c) if start == "perturbed" else None
+    e = recorded(vs, key, hidden=hidden)
+    if hidden is None:
+        assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    else:
+        check_hidden_start(e, hidden, length)
+    out = e.rollout_vjp_rnn(T, **cotangents(vs, key, e))
+    assert e.error_count() == 0 and e.ld > N and not any(bool(x[..., N:].any()) for x in out)
+    e.close()
+    check_hidden_block(f"{key} vs_rollout_vjp_rnn from {start}", scaled_hidden(vs, c, out[1]), g1, g2)
+    if first is not None:
+        f1, f2, acts, pres = first
+        smooth = smooth_per_lane(f1, f2)
+        assert smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
+        check_net_keeps_the_box(c, acts, length)
+        check_no_unit_near_a_kink(c, pres, length)
+        worst = worst_of(scaled(vs, c, *out)[:, blocks_of(c)[0]], f1, smooth)
+        print(f"{key} from {start}: action offsets and initial state: worst error / tolerance {worst:.4f}")
+        assert worst <= 1.0, (key, worst)
 
 
 def test_exploration_noise_is_an_additive_constant(vs):

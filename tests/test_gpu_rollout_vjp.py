@@ -9,6 +9,10 @@ Gradients are compared per unit change of an input in its own scale (d_act times
 which puts the entries of one lane in one unit, so that the project's tolerance of test_step_jacobians_against_finite_differences
 applies per lane: 3e-3 |g| + 3e-4 max |g_smooth| of the lane, at most a 2e-3 share of bad entries, entries smooth where central
 differences of the fp64 oracle at relative steps 1e-6 and 1e-5 agree to 1e-4.
+
+The hidden rows S .. S + H - 1 of d_init (cartpole, ball balancer) are not columns of that per-lane array: they are compared per column,
+each per HIDDEN_SCALE, from the hidden state that reset leaves and from a non-trivial one (test_hidden_adjoint_against_the_fp64_oracle;
+derivative_cases.py says why).
 """
 import ctypes as C
 import functools
@@ -20,8 +24,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (ACT_IN, FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STATE_BUFFERS, T, case_cotangents, dev,  # noqa: E402
-                              frozen, lengths_of, oracle_rollout, playback_case, record_mode2, smooth_per_lane, within_per_lane)
+from derivative_cases import (ACT_IN, FAMILIES, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STARTS, STATE_BUFFERS, T,  # noqa: E402
+                              case_cotangents, check_hidden_block, check_hidden_start, dev, frozen, hidden_conditions, hidden_start, lengths_of,
+                              open_loop_hidden_reference, oracle_rollout, playback_case, record_mode2, scaled_hidden, smooth_per_lane,
+                              start_hidden, within_per_lane)
 
 
 @pytest.fixture(scope="module")
@@ -52,14 +58,15 @@ def phi(c, state0, hidden0, acts, length):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_reference(name):
+def oracle_reference(name, start="reset"):
     """central differences of Phi at relative steps 1e-6 and 1e-5 with respect to every action entry and every initial-state entry,
     per unit of the input's scale: two arrays [N, T * A + S] (actions first, step-major), and the oracle's lane lengths.  The hidden
-    state starts from the oracle's reset; a lane's length is held at its unperturbed value (the branch taken)."""
+    state starts from the oracle's reset (start = "perturbed": from hidden_start()); a lane's length is held at its unperturbed value
+    (the branch taken)."""
     c = case(name)
     ref = c["ref"]
     s0, a0 = c["init"].astype(np.float64), c["acts"].astype(np.float64)
-    h0 = ref.reset(c["params"].astype(np.float64), s0, True)["hidden"]
+    h0 = start_hidden(name, c, start)
     length = lengths_of(oracle_rollout(ref, c["params"].astype(np.float64), s0, h0, a0).done)
     out = []
     for h in (1e-6, 1e-5):
@@ -77,11 +84,13 @@ def oracle_reference(name):
     return out[0], out[1], length
 
 
-def recorded(vs, name, splits=(T,), acts=None, n=N):
-    """a handle whose rows 0 .. T - 1 hold the playback rollouts of the case, recorded in mode 2 by step_policy in the given launches"""
+def recorded(vs, name, splits=(T,), acts=None, n=N, hidden=None):
+    """a handle whose rows 0 .. T - 1 hold the playback rollouts of the case, recorded in mode 2 by step_policy in the given launches;
+    hidden [N, H]: the initial hidden state in place of reset's"""
     c = case(name)
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-    return record_mode2(e, T, c["params"][:n], lambda e: e.set_policy_playback(c["acts"][:n] if acts is None else acts), c["init"][:n], splits)
+    return record_mode2(e, T, c["params"][:n], lambda e: e.set_policy_playback(c["acts"][:n] if acts is None else acts), c["init"][:n], splits,
+                        hidden=None if hidden is None else hidden[:n])
 
 
 def cotangents(vs, name, e, t_steps=T):
@@ -109,6 +118,7 @@ def test_against_the_fp64_oracle(vs, name):
     d_act, d_init = host(vs, *e.rollout_vjp(T, **cotangents(vs, name, e)))
     assert e.error_count() == 0
     e.close()
+    # (the hidden rows of d_init have a unit and a test of their own: test_hidden_adjoint_against_the_fp64_oracle)
     got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
     assert np.isfinite(got).all()
     bad, worst = within_per_lane(got.astype(np.float64), f1, smooth)
@@ -116,11 +126,46 @@ def test_against_the_fp64_oracle(vs, name):
     assert bad <= 2e-3, (name, bad, worst)
 
 
+@pytest.mark.parametrize("start", STARTS)
+@pytest.mark.parametrize("name", HIDDEN_FAMILIES)
+def test_hidden_adjoint_against_the_fp64_oracle(vs, name, start):
+    """Rows S .. S + H - 1 of d_init, d Phi / d h_0, against central differences of the same Phi at HIDDEN_STEPS x HIDDEN_SCALE, per column
+    and per HIDDEN_SCALE, from the hidden state that reset leaves and from hidden_start(); edge lanes like any other, lanes >= n exactly
+    0.  From hidden_start() the action and state columns go through test_against_the_fp64_oracle's per-lane check as well.  vs_step_jac
+    has no h in its x, so nothing else sees this column (test_against_chained_one_step_jacobians leaves both families out).
+    Worst error / tolerance per column measured on the MI355X (printed with -s): DESIGN.md section 8d."""
+    c = case(name)
+    ref = c["ref"]
+    g1, g2, length, _ = open_loop_hidden_reference(name, start)
+    hidden_conditions(name, g1, g2)  # from the oracle alone, before the device is asked
+    hidden = hidden_start(name, c) if start == "perturbed" else None
+    e = recorded(vs, name, hidden=hidden)
+    if hidden is None:
+        assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
+    else:
+        check_hidden_start(e, hidden, length)
+    da, di = e.rollout_vjp(T, **cotangents(vs, name, e))
+    assert e.error_count() == 0 and e.ld > N and not da[..., N:].any() and not di[..., N:].any()
+    e.close()
+    check_hidden_block(f"{name} vs_rollout_vjp from {start}", scaled_hidden(vs, c, di), g1, g2)
+    if start == "perturbed":
+        f1, f2, length2 = oracle_reference(name, start)
+        smooth = smooth_per_lane(f1, f2)
+        assert np.array_equal(length2, length) and (~smooth).mean() <= 0.01, (name, float((~smooth).mean()))  # from the oracle alone
+        d_act, d_init = host(vs, da, di)
+        got = np.concatenate([d_act.reshape(N, T * ref.A) * ACT_IN[name], d_init[:, :ref.S] * np.array(INIT_SCALE[name])], axis=1)
+        assert np.isfinite(got).all()
+        bad, worst = within_per_lane(got.astype(np.float64), f1, smooth)
+        print(f"{name} from {start}: actions and states: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
+        assert bad <= 2e-3, (name, bad, worst)
+
+
 # ------------------------------------------------------------------------------------ 2. against the one-step Jacobians
 @pytest.mark.parametrize("name", [f for f in FAMILIES if f not in ("qcp-su", "qbb")])
 def test_against_chained_one_step_jacobians(vs, name):
-    """Families without hidden state, the first K = 12 steps: a second handle steps along the same actions with vs_step_jac and its
-    fp32 Jacobians are chained transposed in fp64 on the host.  (g_obs row 0 is 0 here: vs_step_jac has no Jacobian of the initial
+    """Families without hidden state (vs_step_jac's x = (s, a) has no h, so its Jacobians cannot be chained for the other two; their hidden
+    column is held to the oracle in test_hidden_adjoint_against_the_fp64_oracle), the first K = 12 steps: a second handle steps along
+    the same actions with vs_step_jac and its fp32 Jacobians are chained transposed in fp64 on the host.  (g_obs row 0 is 0 here: vs_step_jac has no Jacobian of the initial
     observation.)  Both sides differentiate the same dual-number step code, so the difference is the kernel's fp32 summation alone.
     Bound: one output of one step is an fma chain of M = S + 1 + O terms from 0, its rounding error at most M u times the sum of the
     absolute terms, u = 2^-24 (Higham, gamma_M, first order).  With abs_t = |J_t|^T abs_{t+1} + |g_rew[t]| |J_r| + |J_o|^T |g_obs[t+1]|
