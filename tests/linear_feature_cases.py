@@ -42,7 +42,7 @@ measurement on a finite grid).
 """
 import numpy as np
 
-import test_gpu_policy_vjp as pv  # (features: the fp64 values)
+from closed_loop_cases import features  # (the fp64 values)
 import test_lin_param_grad_host as host  # (feature_errors, U, EPS_SIG, EPS_SINCOS, EXTRA)
 
 U, EPS_SIG, EPS_SINCOS = host.U, host.EPS_SIG, host.EPS_SINCOS
@@ -156,9 +156,9 @@ def n_features(term, n_vis):
 
 
 def value(term, x):
-    """phi [n, F] of ONE term on the visible rows x [n, n_vis] (fp64): test_gpu_policy_vjp.features"""
+    """phi [n, F] of ONE term on the visible rows x [n, n_vis] (fp64): closed_loop_cases.features"""
     with np.errstate(all="ignore"):
-        return pv.features((term,), np.asarray(x, dtype=np.float64))
+        return features((term,), np.asarray(x, dtype=np.float64))
 
 
 def derivative(term, x):

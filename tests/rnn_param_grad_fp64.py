@@ -30,14 +30,12 @@ double the bound for them, the factor test_gpu_policy_fp64.py uses).  The chains
 """
 import numpy as np
 
+from closed_loop_cases import sigmoid
+
 U = 2.0 ** -24
 TANH_ABS, SIGMOID_ABS = 2e-7, 4e-7
 GATES = {"tanh": 1, "relu": 1, "gru": 3, "lstm": 4}
 RNN_XP = 8
-
-
-def sigmoid(z):
-    return 1.0 / (1.0 + np.exp(-z))
 
 
 def _act(kind, s, e_s):
@@ -90,7 +88,7 @@ def _pre(w, b_ih, b_hh, v_in, e_in, h, n_chain):
 
 
 def param_grad_fp64(net, x, p, abar, d_hid, inside, output_nonlin=None, chains=None, mistake=None):
-    """net: test_rnn_vjp_host.unpack_rnn's dict.  -> (flat gradient, flat sum of |terms|, flat bound, dict(zmax: max |gate
+    """net: closed_loop_cases.unpack_rnn's dict.  -> (flat gradient, flat sum of |terms|, flat bound, dict(zmax: max |gate
     pre-activation|, kink: min |pre-activation| of a relu cell, inf otherwise)).
     mistake: None, or one of the kernel mistakes the host test shows the bound to catch -- "no_r_scale" (W_hn, b_hn take delta_n),
     "drop_unit" (the last unit of every layer gets no delta), "ignore_c" (the c part of d_hid is not read)"""

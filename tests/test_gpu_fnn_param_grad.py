@@ -2,7 +2,7 @@
 vs_fnn_param_grad / k_fnn_param_grad + k_fnn_param_reduce: the parameter gradient of a feed-forward network policy over the recorded
 rows of a handle, VecSimEnv.fnn_param_grad and DifferentiableNetRollout(param_pass="kernel").
 
-Shapes, networks and seeds are those of test_gpu_fnn_vjp.py (whose cases are imported): 150 lanes (64 + 64 + 22), T = 24, +-5 % per-lane
+Shapes, networks and seeds are those of test_gpu_fnn_vjp.py (closed_loop_cases.py has the cases): 150 lanes (64 + 64 + 22), T = 24, +-5 % per-lane
 parameters, lanes 0 .. 9 end early.  abar is random and dense and is fed directly.
 
 Reference: test_fnn_param_grad_host.param_grad_fp64 -- the sum restated in fp64 over the RECORDED observations and lengths (held to
@@ -36,8 +36,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import closed_loop_cases as clc  # noqa: E402  (cases, networks, seeds)
 import test_fnn_param_grad_host as host  # noqa: E402  (the fp64 reference and its error bound)
-import test_gpu_fnn_vjp as fv  # noqa: E402  (cases, networks, seeds)
 from derivative_cases import ACT_IN, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, dev, record_mode2  # noqa: E402
 
 TABLE = ["omo-1-relu", "omo-63x7-relu", "qq-su-16", "qq-su-64x64-feat", "qcp-su-32x33", "qbb-31x64-tanh-out", "pend-view-8-sigmoid"]
@@ -61,16 +61,16 @@ def grid_of(ld, t_steps):
 
 
 def recorded(vs, key, n=N, t=T, lanes=None, spec=None, noise_seed=0, cap=None):
-    """fv.recorded with the number of steps free: rows 0 .. t - 1 hold the closed-loop rollouts of the case (lane k repeats lane k % N,
+    """closed_loop_cases.recorded with the number of steps free: rows 0 .. t - 1 hold the closed-loop rollouts of the case (lane k repeats lane k % N,
     or the case's lanes `lanes`)"""
-    c = fv.case(key)
+    c = clc.case(key)
     name = c["name"]
     pick = (lambda x: np.resize(x, (n,) + x.shape[1:])) if lanes is None else (lambda x: np.resize(x[lanes], (n,) + x.shape[1:]))
     e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
 
     def policy(e):
         if spec is None:
-            fv.set_net(e, c["net"])
+            clc.set_net(e, c["net"])
         else:
             e.set_policy_fnn(**spec)
 
@@ -78,7 +78,7 @@ def recorded(vs, key, n=N, t=T, lanes=None, spec=None, noise_seed=0, cap=None):
 
 
 def abar_of(key, n, t, seed=0):
-    A = fv.case(key)["ref"].A
+    A = clc.case(key)["ref"].A
     return np.random.default_rng(1000 + seed).normal(size=(n, t, A)).astype(np.float32)
 
 
@@ -144,7 +144,7 @@ def test_against_the_fp64_reference(vs, key):
     oscillator [1] 0.000 / 0.001, [63, 7] 0.002 / 0.005; QQube [16] 0.002 / 0.002, [64, 64] with feat 0.001 / 0.001; cartpole 0.001 /
     0.002; ball balancer 0.001 / 0.003; pendulum through obs_idx 0.002 / 0.003."""
     e = recorded(vs, key)
-    _, length = held(vs, e, key, fv.case(key)["net"], N, T, abar_of(key, N, T), key)
+    _, length = held(vs, e, key, clc.case(key)["net"], N, T, abar_of(key, N, T), key)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
     e.close()
 
@@ -152,11 +152,11 @@ def test_against_the_fp64_reference(vs, key):
 def test_exploration_noise(vs):
     """the network inside a NormalActNoiseExplStrat: the records hold the noisy rollout, the gradient is the mean network's"""
     key = "pend-8"
-    c = fv.case(key)
+    c = clc.case(key)
     env = vs.PendulumSim(max_steps=MAX_STEPS, **KW[c["name"]])
     policy = vs.NormalActNoiseExplStrat(vs.FNNPolicy(env.spec, list(c["net"]["hidden"]), torch.tanh, featurize=False),
                                         std_init=0.02 * ACT_IN[c["name"]])
-    policy.policy.param_values = torch.as_tensor(fv.flat_params(c["net"]))
+    policy.policy.param_values = torch.as_tensor(clc.flat_params(c["net"]))
     e = recorded(vs, key, spec=vs.fnn_kernel_spec(policy), noise_seed=77)
     quiet = recorded(vs, key)
     assert not torch.equal(e.traj_tensors(T, N)["act"], quiet.traj_tensors(T, N)["act"])  # the noise is there
@@ -170,14 +170,14 @@ def test_exploration_noise(vs):
 def test_small_batches(vs, n, t):
     key = "qcp-su-32x33"
     e = recorded(vs, key, n=n, t=t)
-    held(vs, e, key, fv.case(key)["net"], n, t, abar_of(key, n, t), f"{key} n={n} T={t}")
+    held(vs, e, key, clc.case(key)["net"], n, t, abar_of(key, n, t), f"{key} n={n} T={t}")
     e.close()
 
 
 def test_t_steps_below_the_capacity(vs):
     key = "qq-su-64x64-feat"
     e = recorded(vs, key)
-    short, _ = held(vs, e, key, fv.case(key)["net"], N, 17, abar_of(key, N, 17), key + " 17 of 24 rows")
+    short, _ = held(vs, e, key, clc.case(key)["net"], N, 17, abar_of(key, N, 17), key + " 17 of 24 rows")
     f = recorded(vs, key, t=17)
     assert np.array_equal(f.fnn_param_grad(17, vs.lanes_last(dev(abar_of(key, N, 17)), f.ld)).cpu().numpy().astype(np.float64), short)
     f.close()
@@ -192,7 +192,7 @@ def test_every_rollout_runs_to_the_end(vs):
     e.close()
     lanes = lanes[full % lanes.size]  # the case's lanes that run through
     e = recorded(vs, key, lanes=lanes)
-    _, length = held(vs, e, key, fv.case(key)["net"], N, T, abar_of(key, N, T), key + " all lanes full")
+    _, length = held(vs, e, key, clc.case(key)["net"], N, T, abar_of(key, N, T), key + " all lanes full")
     assert (length == T).all()
     e.close()
 
@@ -207,7 +207,7 @@ def test_tiles_outnumber_the_waves(vs):
     e = recorded(vs, key, n=n, t=t)
     n_wg, acc = grid_of(e.ld, t)
     assert e.ld == 3328 and (e.ld // 64) * t > 4 * n_wg and acc == 128 and t % (acc // 64) != 0
-    held(vs, e, key, fv.case(key)["net"], n, t, abar_of(key, n, t), f"{key} n={n} T={t}")
+    held(vs, e, key, clc.case(key)["net"], n, t, abar_of(key, n, t), f"{key} n={n} T={t}")
     e.close()
 
 
@@ -215,7 +215,7 @@ def test_zero_adjoints_give_zeros(vs):
     key = "qcp-su-32x33"
     e = recorded(vs, key)
     out = torch.full((e._fnn_n_params,), 7.0, device="cuda")
-    assert e.fnn_param_grad(T, torch.zeros(T, fv.case(key)["ref"].A, e.ld, device="cuda"), out=out) is out
+    assert e.fnn_param_grad(T, torch.zeros(T, clc.case(key)["ref"].A, e.ld, device="cuda"), out=out) is out
     assert not out.any()
     e.close()
 
@@ -224,7 +224,7 @@ def test_zero_adjoints_give_zeros(vs):
 def test_nan_behind_the_rows_changes_no_bit(vs, key):
     """NaN in abar at every row t >= L, at lanes n .. ld - 1 and in rows t_steps .. of a larger buffer: the same bits as with zeros there"""
     e = recorded(vs, key)
-    A = fv.case(key)["ref"].A
+    A = clc.case(key)["ref"].A
     length = e.rollout_lengths(N, T)[0]
     assert e.ld > N and bool((length < T).any())
     big = torch.zeros(T + 5, A, e.ld, device="cuda")
@@ -266,7 +266,7 @@ def test_the_handle_is_untouched_and_goes_on_serving(vs):
     L = vs._lib
     key = "qq-su-64x64-feat"
     e = recorded(vs, key)
-    cot = fv.cotangents(vs, key, e)
+    cot = clc.cotangents(vs, key, e)
     da0, di0 = e.rollout_vjp_fnn(T, **cot)
     before = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
     planes, words = e.traj_planes()
@@ -279,16 +279,16 @@ def test_the_handle_is_untouched_and_goes_on_serving(vs):
     da1, di1 = e.rollout_vjp_fnn(T, **cot)
     assert torch.equal(da1, da0) and torch.equal(di1, di0)
     # ---- another policy, then the network again: the workspace went with the first network and comes back
-    d = vs.env_dims(fv.case(key)["name"])
+    d = vs.env_dims(clc.case(key)["name"])
     e.set_policy_linear(np.zeros(d["A"], dtype=np.float32), ["const"])
     with pytest.raises(RuntimeError, match="vs_fnn_param_grad"):
         e.fnn_param_grad(T, da0)
-    fv.set_net(e, fv.case(key)["net"])
+    clc.set_net(e, clc.case(key)["net"])
     assert torch.equal(e.fnn_param_grad(T, da0), g)
     # ---- and the handle still steps: the same launch from the same state gives the same records
     f = recorded(vs, key)
     for h in (e, f):
-        h.reset(init_state=np.resize(fv.case(key)["init"], (N, fv.case(key)["init"].shape[1])))
+        h.reset(init_state=np.resize(clc.case(key)["init"], (N, clc.case(key)["init"].shape[1])))
         h.set_traj_offset(0)
         h.step_policy(T, record=True)
     assert torch.equal(e.traj_tensors(T, N)["act"], f.traj_tensors(T, N)["act"]) and e.error_count() == 0
@@ -301,7 +301,7 @@ def test_refusals_leave_the_output_untouched(vs):
     L = vs._lib
     lib = L.load()
     key = "qq-su-16"
-    c = fv.case(key)
+    c = clc.case(key)
     d = vs.env_dims(c["name"])
     e = recorded(vs, key)
     n_params = e._fnn_n_params
@@ -331,7 +331,7 @@ def test_refusals_leave_the_output_untouched(vs):
         refused(L.VS_ERR_ARG, e, t_steps=t_steps)
     for n in (n_params - 1, n_params + 1):
         refused(L.VS_ERR_ARG, e, n=n)
-    e.set_policy_population(np.tile(fv.flat_params(c["net"])[None, :], (3, 1)), lane_set=np.arange(N) // 64)
+    e.set_policy_population(np.tile(clc.flat_params(c["net"])[None, :], (3, 1)), lane_set=np.arange(N) // 64)
     refused(L.VS_ERR_STATE, e)
     e.set_policy_population(None)
     served()
@@ -347,7 +347,7 @@ def test_refusals_leave_the_output_untouched(vs):
     n3 = (d["O"] + 1) * 8 + 2 * (8 + 1) * 8 + (8 + 1) * d["A"]
     e.set_policy_fnn(np.zeros(n3, dtype=np.float32), [8, 8, 8])  # three hidden layers
     refused(L.VS_ERR_STATE, e, n=n3)
-    fv.set_net(e, c["net"])
+    clc.set_net(e, c["net"])
     served()
     e.set_record_mode(1)
     e.set_traj_capacity(T)
@@ -372,17 +372,17 @@ def test_refusals_leave_the_output_untouched(vs):
 def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     from simurlacra_amd import diffsim
 
-    tc = fv.torch_case(name)
-    NT, TT = fv.NT, fv.TT
-    env = getattr(vs, fv.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
-    policy = vs.FNNPolicy(env.spec, hidden_sizes=list(fv.AUTOGRAD[name]), hidden_nonlin=torch.tanh, featurize=False)
-    policy.param_values = torch.as_tensor(fv.flat_params(tc["net"]))
+    tc = clc.torch_case("fnn", name)
+    NT, TT = clc.NT, clc.TT
+    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    policy = vs.FNNPolicy(env.spec, hidden_sizes=list(clc.FNN_AUTOGRAD[name]), hidden_nonlin=torch.tanh, featurize=False)
+    policy.param_values = torch.as_tensor(clc.flat_params(tc["net"]))
     weights = list(policy.parameters())
 
     def grads(roll):
         init = dev(tc["init"]).requires_grad_(True)
         obs, rew, act, lengths = roll(init, TT)
-        loss = -vs.discounted_return(rew, lengths, fv.GAMMA).sum() + 1e-3 * act.pow(2).sum()
+        loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
         g = torch.autograd.grad(loss, weights + [init], retain_graph=True)
         return g, loss, init
 
@@ -425,15 +425,15 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
 
 def test_autograd_fp64_parameters_take_the_torch_pass(vs):
     name = "qq-su"
-    tc = fv.torch_case(name)
-    env = getattr(vs, fv.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
-    policy = vs.FNNPolicy(env.spec, hidden_sizes=list(fv.AUTOGRAD[name]), hidden_nonlin=torch.tanh, featurize=False)
-    policy.param_values = torch.as_tensor(fv.flat_params(tc["net"]))
+    tc = clc.torch_case("fnn", name)
+    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    policy = vs.FNNPolicy(env.spec, hidden_sizes=list(clc.FNN_AUTOGRAD[name]), hidden_nonlin=torch.tanh, featurize=False)
+    policy.param_values = torch.as_tensor(clc.flat_params(tc["net"]))
     policy.double()
     roll = vs.DifferentiableNetRollout(env, policy, batch_lanes=32)
     assert roll.param_pass == "torch"
-    obs, rew, act, lengths = roll(dev(tc["init"]), fv.TT)
-    g = torch.autograd.grad(-vs.discounted_return(rew, lengths, fv.GAMMA).sum() + 1e-3 * act.pow(2).sum(), list(policy.parameters()))
+    obs, rew, act, lengths = roll(dev(tc["init"]), clc.TT)
+    g = torch.autograd.grad(-vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum(), list(policy.parameters()))
     assert all(x.dtype == torch.float64 and bool(torch.isfinite(x).all()) for x in g) and any(bool(x.any()) for x in g)
     with pytest.raises(vs.ValueErr, match="param_pass"):
         vs.DifferentiableNetRollout(env, policy, param_pass="triton")

@@ -5,10 +5,10 @@ two hidden layers in the loop, VecSimEnv.rollout_vjp_fnn and DifferentiableNetRo
 Shapes, cotangents, scales and the per-lane tolerance rule are those of test_gpu_policy_vjp.py, both from derivative_cases.py: 150 lanes
 (64 + 64 + 22: a partial last workgroup), T = 24, max_steps = 50, +-5 % per-lane parameters, lanes 0 .. 9 start at the edge of the state space and
 end early, random cotangents on all four inputs; per lane 3e-3 |g| + 3e-4 max |g| against central differences of the fp64 closed loop at
-relative steps 1e-6 and 1e-5 (oracle.cpu_ref for the step, the NumPy network below for the policy).  Here EVERY entry must be smooth (the
+relative steps 1e-6 and 1e-5 (oracle.cpu_ref for the step, the NumPy network of closed_loop_cases.py for the policy).  Here EVERY entry must be smooth (the
 two step sizes agree; asserted from the oracle alone) and every entry is held to the tolerance: none is excluded.
 
-The weights (make_net) keep every lane inside the action box and outside the dead zones, and no unit near a kink:
+The weights (closed_loop_cases.make_net) keep every lane inside the action box and outside the dead zones, and no unit near a kink:
   * every layer's input is measured on a rollout under the bias action alone: mid and dev = half its range per row;
   * a hidden pre-activation is b + W (x - mid) with |b| drawn from the case's range with a random sign and
     |W (x - mid)| <= amp on that rollout (relu: |b| in [0.5, 1.5], amp 0.3, rows scaled by 1 / fan-in, so that no unit comes near 0 --
@@ -26,33 +26,20 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import cpu_ref
-
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T, TANH_OUT_AMP,  # noqa: E402
-                              TANH_OUT_AT, check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev, draw_params_and_init, frozen,
-                              hidden_conditions, hidden_differences, hidden_start, lengths_of, record_mode2, scaled, scaled_hidden,
-                              smooth_per_lane, start_hidden, tolerance_per_lane, worst_of)
+import closed_loop_cases as clc  # noqa: E402
+from closed_loop_cases import (ENVS, FNN_AUTOGRAD as AUTOGRAD, FNN_ORACLE_CASES as ORACLE_CASES, GAMMA, NT, TT, case,  # noqa: E402
+                               check_no_unit_near_a_kink, cotangents, feedback_seen, flat_params, fnn_policy, hidden_reference, mlp,
+                               oracle_reference, recorded, reference, set_net)
+from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T,  # noqa: E402
+                              check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev, hidden_conditions, hidden_start, scaled,
+                              scaled_hidden, smooth_per_lane, tolerance_per_lane, worst_of)
 
-# case -> (family, hidden sizes, hidden nonlinearities, output nonlinearity, feat, obs_idx, seed, gain of the output layer)
-CASES = {
-    "qq-su-16": ("qq-su", (16,), ("tanh",), None, False, None, 1, 1.0),
-    "qq-su-64x64-feat": ("qq-su", (64, 64), ("tanh", "tanh"), None, True, None, 2, 1.0),
-    "qcp-su-32x33": ("qcp-su", (32, 33), ("tanh", "sigmoid"), None, False, None, 23, 3.0),
-    "qbb-31x64-tanh-out": ("qbb", (31, 64), ("tanh", "tanh"), "tanh", False, None, 4, 1.0),
-    "omo-1-relu": ("omo", (1,), ("relu",), None, False, None, 25, 1.0),
-    "omo-63x7-relu": ("omo", (63, 7), ("relu", "relu"), None, False, None, 6, 1.0),
-    "pend-view-8-sigmoid": ("pend", (8,), ("sigmoid",), None, False, (2, 0), 7, 2.0),   # the policy sees (th_dot, sin th)
-    "pend-8": ("pend", (8,), ("tanh",), None, False, None, 8, 1.0),
-    "bob-8": ("bob", (8,), ("tanh",), None, False, None, 9, 1.0),
-}
-ORACLE_CASES = ["qq-su-16", "qq-su-64x64-feat", "qcp-su-32x33", "qbb-31x64-tanh-out", "omo-1-relu", "omo-63x7-relu", "pend-view-8-sigmoid"]
 DEGENERATE = {"omo": "omo-63x7-relu", "bob": "bob-8", "qq-su": "qq-su-64x64-feat", "qcp-su": "qcp-su-32x33", "pend": "pend-8",
               "qbb": "qbb-31x64-tanh-out"}
-FUNCS = {"tanh": np.tanh, "relu": lambda z: np.maximum(z, 0.0), "sigmoid": lambda z: 1.0 / (1.0 + np.exp(-z)), None: lambda z: z}
 
 
 @pytest.fixture(scope="module")
@@ -64,215 +51,6 @@ def vs():
     return simurlacra_amd
 
 
-# ------------------------------------------------------------------------------------------------------ the fp64 network
-def net_input(net, ob):
-    x = ob if net["obs_idx"] is None else ob[:, list(net["obs_idx"])]
-    if net["feat"]:
-        x = np.concatenate([x[:, 0:1], np.sin(x[:, 1:2]), np.cos(x[:, 1:2]), x[:, 2:]], axis=1)
-    return x
-
-
-def mlp(net, ob, n_layers=None):
-    """(action mean [n, A], hidden pre-activations [[n, h_l]], layer inputs [[n, in_l]]) of the observations ob [n, O] in fp64; with
-    n_layers only that many hidden layers are evaluated (the action is None)"""
-    x = net_input(net, ob)
-    pre, ins = [], []
-    for l, (W, b) in enumerate(zip(net["W"], net["b"])):
-        ins.append(x)
-        if n_layers is not None and l == n_layers:
-            return None, pre, ins
-        z = x @ W.astype(np.float64).T + b.astype(np.float64)
-        if l == len(net["W"]) - 1:
-            return FUNCS[net["output_nonlin"]](z), pre, ins
-        pre.append(z)
-        x = FUNCS[net["hidden_nonlin"][l]](z)
-
-
-def flat_params(net):
-    """torch's order: hidden_layers.i.weight [out, in], .bias, ..., output_layer.weight, .bias"""
-    return np.concatenate([np.concatenate([W.reshape(-1), b]) for W, b in zip(net["W"], net["b"])]).astype(np.float32)
-
-
-def closed_loop(ref, params, state0, hidden0, net, offs, open_acts=None):
-    """test_gpu_policy_vjp's closed_loop with the network as the policy: a_t = net(obs_t) + offs[:, t] -> ..., and the hidden pre-activations
-    [T][layer][n, h]"""
-    st, hid = state0.copy(), hidden0.copy()
-    ob = ref.observe(st)
-    states, hiddens, obs, rew, done, acts, pres = [st], [hid], [ob], [], [], [], []
-    with np.errstate(all="ignore"):
-        for t in range(offs.shape[1]):
-            if open_acts is None:
-                mean, pre, _ = mlp(net, ob)
-                a = mean + offs[:, t]
-                pres.append(pre)
-            else:
-                a = open_acts[:, t]
-            out = ref.step(st, hid, a, params, np.full(st.shape[0], t))
-            st, hid, ob = out["state"], out["hidden"], out["obs"]
-            states.append(st), hiddens.append(hid), obs.append(ob), rew.append(out["rew"]), done.append(out["done"]), acts.append(a)
-    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done), np.stack(acts), pres
-
-
-def make_net(ref, name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, params, s0, h0, rng, n_steps, gain=1.0):
-    """the network of the module docstring, float32 weights; gain scales the output layer's +-0.12 ACT_IN"""
-    A = ref.A
-    sign = lambda *shape: rng.choice([-1.0, 1.0], shape)  # noqa: E731
-    n_in = (ref.O if obs_idx is None else len(obs_idx)) + (1 if feat else 0)
-    sizes = (n_in,) + tuple(hidden)
-    target = sign(A) * (TANH_OUT_AT if output_nonlin == "tanh" else 0.45 * ACT_IN[name])
-    amp_out = gain * (TANH_OUT_AMP if output_nonlin == "tanh" else 0.12 * ACT_IN[name])
-    net = dict(W=[np.zeros((h, i), dtype=np.float32) for h, i in zip(hidden, sizes)] + [np.zeros((A, hidden[-1]), dtype=np.float32)],
-               b=[np.zeros(h, dtype=np.float32) for h in hidden] + [target.astype(np.float32)],
-               hidden_nonlin=hidden_nonlin, output_nonlin=output_nonlin, feat=feat, obs_idx=obs_idx, hidden=tuple(hidden))
-    obs = closed_loop(ref, params, s0, h0, net, np.zeros((s0.shape[0], n_steps, A)))[2].reshape(-1, ref.O)  # under the bias action alone
-    for l in range(len(hidden) + 1):
-        x = mlp(net, obs, n_layers=l)[2][l]
-        mid, dv = (x.max(axis=0) + x.min(axis=0)) / 2.0, (x.max(axis=0) - x.min(axis=0)) / 2.0
-        live = dv > 1e-6 * (1.0 + np.abs(mid))
-        dv = np.where(live, dv, 1.0)          # (a row that never moves, e.g. a dead relu unit: a weight of the others' size)
-        fan = x.shape[1]
-        if l == len(hidden):
-            W = sign(A, fan) * amp_out / (fan * dv)
-            b = target - W @ mid
-        else:
-            relu = hidden_nonlin[l] == "relu"
-            amp, blo, bhi = (0.3, 0.5, 1.5) if relu else (1.0, 0.0, 0.7)
-            W = rng.uniform(0.5, 1.0, (hidden[l], fan)) * sign(hidden[l], fan) * amp / ((fan if relu else np.sqrt(fan)) * dv)
-            b = rng.uniform(blo, bhi, hidden[l]) * sign(hidden[l]) - W @ mid
-        net["W"][l], net["b"][l] = W.astype(np.float32), b.astype(np.float32)
-    return net
-
-
-@functools.lru_cache(maxsize=None)
-def case(key):
-    """the inputs of a case, float32 and left unchanged by the tests (test_gpu_policy_vjp's case, with a network for the stack)"""
-    name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, seed, gain = CASES[key]
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(100 + seed)
-    params, init = draw_params_and_init(ref, name, rng)
-    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    net = make_net(ref, name, hidden, hidden_nonlin, output_nonlin, feat, obs_idx, params.astype(np.float64), init.astype(np.float64), h0,
-                   rng, T, gain)
-    c = dict(name=name, ref=ref, params=params, init=init, h0=h0, net=net,
-             g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
-             g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32))
-    return frozen(c, *net["W"], *net["b"])
-
-
-def phi(c, state0, offs, length, open_acts=None, hidden0=None):
-    """test_gpu_policy_vjp's phi for the network's closed loop"""
-    states, hiddens, obs, rew, _, acts, _ = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"] if hidden0 is None else hidden0,
-                                                        c["net"], offs, open_acts)
-    k = np.arange(T + 1)[:, None]
-    n = np.arange(state0.shape[0])
-    inside = k[:T] < length[None, :]
-    out = np.where(inside, c["g_rew"].T.astype(np.float64) * rew, 0.0).sum(axis=0)
-    out += np.where(inside[:, :, None], c["g_act"].transpose(1, 0, 2).astype(np.float64) * acts, 0.0).sum(axis=(0, 2))
-    out += np.where((k <= length[None, :])[:, :, None], c["g_obs"].transpose(1, 0, 2).astype(np.float64) * obs, 0.0).sum(axis=(0, 2))
-    last = np.concatenate([states[length, n], hiddens[length, n]], axis=1)
-    return out + (c["g_last"].astype(np.float64) * last).sum(axis=1)
-
-
-def reference(c, offs0, h0=None):
-    """test_gpu_policy_vjp's reference: central differences of Phi at relative steps 1e-6 and 1e-5 [N, T A + S] (offsets first, step-major), the lane
-    lengths, the oracle's actions [T, N, A], d_init [N, S] of the OPEN loop along them, and the hidden pre-activations; h0: the initial
-    hidden state (None: the one the oracle's reset leaves)"""
-    ref, name = c["ref"], c["name"]
-    s0 = c["init"].astype(np.float64)
-    h0 = c["h0"] if h0 is None else h0
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["net"], offs0)
-    length, acts = lengths_of(roll[4]), roll[5]
-    out = []
-    for h in (1e-6, 1e-5):
-        g = np.zeros((N, T * ref.A + ref.S))
-        for t in range(T):
-            for j in range(ref.A):
-                d = np.zeros_like(offs0)
-                d[:, t, j] = h * ACT_IN[name]
-                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length, hidden0=h0) - phi(c, s0, offs0 - d, length, hidden0=h0)) / (2.0 * h)
-        for j in range(ref.S):
-            d = np.zeros_like(s0)
-            d[:, j] = h * INIT_SCALE[name][j]
-            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length, hidden0=h0) - phi(c, s0 - d, offs0, length, hidden0=h0)) / (2.0 * h)
-        out.append(g)
-    open_init = np.zeros((N, ref.S))
-    fixed = acts.transpose(1, 0, 2)
-    for j in range(ref.S):
-        d = np.zeros_like(s0)
-        d[:, j] = 1e-6 * INIT_SCALE[name][j]
-        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed, hidden0=h0) - phi(c, s0 - d, offs0, length, fixed, hidden0=h0)) / 2e-6
-    return out[0], out[1], length, acts, open_init, roll[6]
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_reference(key, start="reset"):
-    c = case(key)
-    return reference(c, np.zeros((N, T, c["ref"].A)), start_hidden(c["name"], c, start))
-
-
-@functools.lru_cache(maxsize=None)
-def hidden_reference(key, start):
-    """the hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the network has no state of its
-    own and no noise; the lane lengths are held), and the oracle's lane lengths"""
-    c = case(key)
-    h0 = start_hidden(c["name"], c, start)
-    offs0 = np.zeros((N, T, c["ref"].A))
-    s0 = c["init"].astype(np.float64)
-    length = lengths_of(closed_loop(c["ref"], c["params"].astype(np.float64), s0, h0, c["net"], offs0)[4])
-    g1, g2 = hidden_differences(c["name"], lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
-    return g1, g2, length
-
-
-def set_net(e, net, noise_std=None):
-    e.set_policy_fnn(flat_params(net), list(net["hidden"]), hidden_nonlin=list(net["hidden_nonlin"]), output_nonlin=net["output_nonlin"],
-                     feat=net["feat"], obs_idx=net["obs_idx"], noise_std=noise_std)
-
-
-def recorded(vs, key, splits=(T,), noise_seed=0, n=N, shape=None, net=None, spec=None, hidden=None):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case (lanes >= N repeat its lanes), recorded in mode 2; hidden
-    [n, H]: the initial hidden state in place of reset's"""
-    c = case(key)
-    name = c["name"]
-    e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-
-    def policy(e):
-        if spec is None:
-            set_net(e, c["net"] if net is None else net)
-        else:  # what fnn_kernel_spec made of a torch policy
-            e.set_policy_fnn(**spec)
-        if shape is not None:
-            e.set_policy_shape(shape)
-
-    return record_mode2(e, T, np.resize(c["params"], (n, c["params"].shape[1])), policy, np.resize(c["init"], (n, c["init"].shape[1])), splits,
-                        hidden=hidden, noise_seed=noise_seed)
-
-
-def cotangents(vs, key, e, with_act=True, n=N):
-    c = case(key)
-    rs = lambda x: np.resize(x, (n,) + x.shape[1:])  # noqa: E731
-    out = dict(g_rew=vs.lanes_last(dev(rs(c["g_rew"])), e.ld), g_obs=vs.lanes_last(dev(rs(c["g_obs"])), e.ld),
-               g_state_last=vs.lanes_last(dev(rs(c["g_last"])), e.ld))
-    if with_act:
-        out["g_act"] = vs.lanes_last(dev(rs(c["g_act"])), e.ld)
-    return out
-
-
-def check_no_unit_near_a_kink(c, pres, length):
-    """relu layers: no hidden pre-activation of the fp64 closed loop within 1e-3 of 0 (inside the lanes' lengths)"""
-    for l, kind in enumerate(c["net"]["hidden_nonlin"]):
-        if kind == "relu":
-            z = np.stack([p[l] for p in pres])  # [T, N, h]
-            inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
-            assert (np.where(inside, np.abs(z), 1.0) >= 1e-3).all(), (c["name"], l)
-
-
-def feedback_seen(c, f1, smooth, open_init, length):
-    """share of the full-length lanes on which a d_init that lacks the feedback is off by more than 10 x the tolerance"""
-    init_cols = slice(T * c["ref"].A, None)
-    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance_per_lane(f1, smooth)[:, init_cols]
-    return float(gap.any(axis=1)[length == T].mean())
-
-
 # ----------------------------------------------------------------------------------- 1. + 2. against the fp64 closed loop
 @pytest.mark.parametrize("key", ORACLE_CASES)
 def test_against_the_closed_loop_fp64_oracle(vs, key):
@@ -281,13 +59,14 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     feedback is seen on 0.61 (pendulum) to 0.98 (oscillator [1]) of the full-length lanes, by the oracle and by the device alike."""
     c = case(key)
     ref = c["ref"]
-    f1, f2, length, acts, open_init, pres = oracle_reference(key)
-    smooth = smooth_per_lane(f1, f2)
+    r = oracle_reference(key)
+    f1, length = r.f1, r.length
+    smooth = smooth_per_lane(f1, r.f2)
     assert smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone: every entry, none excluded
-    check_net_keeps_the_box(c, acts, length)
-    check_no_unit_near_a_kink(c, pres, length)
+    check_net_keeps_the_box(c, r.acts, length)
+    check_no_unit_near_a_kink(c, r.pres, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
-    seen = feedback_seen(c, f1, smooth, open_init, length)
+    seen = feedback_seen(c, f1, smooth, r.open_init, length)
     assert seen >= 0.5, (key, seen)  # from the oracle alone: the test can see the feedback
     e = recorded(vs, key)
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
@@ -335,11 +114,11 @@ def test_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, name, start):
     e.close()
     check_hidden_block(f"{key} vs_rollout_vjp_fnn from {start}", scaled_hidden(vs, c, di), g1, g2)
     if start == "perturbed":
-        f1, f2, length2, acts, _, pres = oracle_reference(key, start)
-        smooth = smooth_per_lane(f1, f2)
-        assert np.array_equal(length2, length) and smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
-        check_net_keeps_the_box(c, acts, length)
-        check_no_unit_near_a_kink(c, pres, length)
+        r = oracle_reference(key, start)
+        f1, smooth = r.f1, smooth_per_lane(r.f1, r.f2)
+        assert np.array_equal(r.length, length) and smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
+        check_net_keeps_the_box(c, r.acts, length)
+        check_no_unit_near_a_kink(c, r.pres, length)
         worst = worst_of(scaled(vs, c, da, di), f1, smooth)
         print(f"{key} from {start}: offsets and states: worst error / tolerance {worst:.3f}")
         assert worst <= 1.0, (key, worst)
@@ -361,8 +140,8 @@ def test_exploration_noise_is_an_additive_constant(vs):
     obs, act = tt["obs"].cpu().numpy().astype(np.float64), tt["act"].cpu().numpy().astype(np.float64)  # [T, N, .]
     offs = (act - mlp(c["net"], obs.reshape(T * N, ref.O))[0].reshape(T, N, ref.A)).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
-    f1, f2, length, acts, _, _ = reference(c, np.ascontiguousarray(offs))
-    smooth = smooth_per_lane(f1, f2)
+    r = reference(c, np.ascontiguousarray(offs))
+    f1, length, smooth = r.f1, r.length, smooth_per_lane(r.f1, r.f2)
     assert smooth.all()
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_fnn(T, **cotangents(vs, key, e)))
@@ -431,7 +210,7 @@ def test_edges(vs, key):
 def test_records_from_both_forward_shapes(vs):
     key, n = "qq-su-64x64-feat", 320
     c = case(key)
-    f1, f2 = oracle_reference(key)[:2]
+    f1, f2 = oracle_reference(key).f1, oracle_reference(key).f2
     res = []
     for shape in ("64", "mfma"):
         e = recorded(vs, key, n=n, shape=shape)
@@ -521,22 +300,8 @@ def test_refusals_leave_the_outputs_untouched(vs):
 
 
 # ----------------------------------------------------------------------------------------------------------- 7. autograd
-ENVS = {"qq-su": "QQubeSwingUpSim", "qcp-su": "QCartPoleSwingUpSim"}
-AUTOGRAD = {"qq-su": (16,), "qcp-su": (64, 64)}
-NT, TT, GAMMA = 70, 12, 0.99
-
-
-@functools.lru_cache(maxsize=None)
 def torch_case(name):
-    """init [NT, S] float32, the network and the oracle's pieces for the loss of test 7 (FNNPolicy(featurize=False), tanh)"""
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(37)
-    init = (rng.uniform(-1.0, 1.0, (NT, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32)
-    params = np.tile(ref.nominal_params(1).astype(np.float32).astype(np.float64), (NT, 1))
-    h0 = ref.reset(params, init.astype(np.float64), True)["hidden"]
-    hidden = AUTOGRAD[name]
-    net = make_net(ref, name, hidden, ("tanh",) * len(hidden), None, False, None, params, init.astype(np.float64), h0, rng, TT)
-    return dict(ref=ref, init=init, params=params, h0=h0, net=net)
+    return clc.torch_case("fnn", name)
 
 
 def with_params(net, flat):
@@ -551,14 +316,9 @@ def with_params(net, flat):
 
 
 def oracle_loss(name, flat, s0, length=None):
-    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop, and the lane lengths"""
+    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop under the flat parameters, and the lane lengths"""
     tc = torch_case(name)
-    _, _, _, rew, done, acts, _ = closed_loop(tc["ref"], tc["params"], s0, tc["h0"], with_params(tc["net"], flat),
-                                              np.zeros((NT, TT, tc["ref"].A)))
-    length = lengths_of(done) if length is None else length
-    inside = np.arange(TT)[:, None] < length[None, :]
-    disc = GAMMA ** np.arange(TT)[:, None]
-    return -np.where(inside, disc * rew, 0.0).sum(axis=0) + 1e-3 * np.where(inside[:, :, None], acts ** 2, 0.0).sum(axis=(0, 2)), length
+    return clc.oracle_loss(tc, fnn_policy(with_params(tc["net"], flat)), s0, length)
 
 
 def chosen_entries(name, n_params):

@@ -2,12 +2,12 @@
 vs_lin_param_grad / k_lin_param_grad (+ k_fnn_param_reduce): the weight gradient of a linear policy on a feature stack over the recorded
 rows of a handle, VecSimEnv.lin_param_grad and DifferentiablePolicyRollout(param_pass="kernel").
 
-Shapes, stacks, weights and seeds are those of test_gpu_policy_vjp.py (150 lanes = 64 + 64 + 22, T = 24, +-5 % per-lane parameters,
+Shapes, stacks, weights and seeds are those of test_gpu_policy_vjp.py (closed_loop_cases.py; 150 lanes = 64 + 64 + 22, T = 24, +-5 % per-lane parameters,
 lanes 0 .. 9 end early) plus the two stacks of test_lin_param_grad_host.EXTRA (all 128 features; a stack in a non-slot order).  abar is
 dense, fed directly, and not zero-mean (test_lin_param_grad_host's docstring says why).
 
 Reference: test_lin_param_grad_host.lin_param_grad_fp64 -- sum_rows abar (x) phi(x) in fp64 over the RECORDED observations and
-lengths, with the NumPy feature stack of test_gpu_policy_vjp (held to torch.autograd.grad of the .double() LinearPolicy at 1e-12 in
+lengths, with the NumPy feature stack of closed_loop_cases (held to torch.autograd.grad of the .double() LinearPolicy at 1e-12 in
 that file, without a device).  Tolerance, per parameter: test_lin_param_grad_host.error_bound, derived in its docstring,
     bound = sum_rows |abar| e(phi_q) + gamma(chain) sum_rows |abar phi_q|,
 the chain read off the launch's grid rule (grid_of / chain_of there, mirrored from the documented rule with the device's compute-unit
@@ -30,8 +30,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_fnn_vjp as fv  # noqa: E402  (a network for the policy-switch tests)
-import test_gpu_policy_vjp as pv  # noqa: E402  (features, torch_case, the autograd shapes)
+import closed_loop_cases as clc  # noqa: E402  (features, torch_case, the autograd shapes; a network for the policy-switch tests)
 import test_lin_param_grad_host as host  # noqa: E402  (cases, the fp64 reference and its error bound)
 from derivative_cases import ACT_IN, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, dev, record_mode2  # noqa: E402
 
@@ -129,7 +128,7 @@ def test_wiring_of_a_single_row(vs, key):
     got = e.lin_param_grad(1, torch.ones(1, A, e.ld, device="cuda")).cpu().numpy().astype(np.float64).reshape(A, -1)
     obs = e.traj_tensors(1, 1)["obs"].cpu().numpy().astype(np.float64).reshape(1, -1)
     x = obs if c["obs_idx"] is None else obs[:, list(c["obs_idx"])]
-    phi, err = pv.features(c["terms"], x)[0], host.feature_errors(c["terms"], x)[0]
+    phi, err = clc.features(c["terms"], x)[0], host.feature_errors(c["terms"], x)[0]
     assert got.shape == (A, phi.size) and np.unique(np.round(phi, 6)).size >= min(phi.size, 4) - 1  # (the entries can be told apart)
     for j in range(A):
         assert (np.abs(got[j] - phi) <= err + 4.0 * host.U * np.abs(phi)).all(), (key, j, np.abs(got[j] - phi).max())
@@ -240,7 +239,7 @@ def test_the_handle_is_untouched_and_goes_on_serving(vs):
     L = vs._lib
     key = "qq-su"
     e = recorded(vs, key)
-    cot = pv.cotangents(vs, key, e)
+    cot = clc.cotangents(vs, key, e)
     da0, di0 = e.rollout_vjp_policy(T, **cot)
     before = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
     planes, words = e.traj_planes()
@@ -262,7 +261,7 @@ def test_one_workspace_serves_linear_fnn_linear_in_turn(vs):
     grid, another packed size and map; rows 3 .. 39 of the first step were stale), the linear policy again (T = 40: the linear grid of
     160 workgroups in a buffer sized for the network's 40), and each result equals BIT FOR BIT that of the same call on a fresh handle."""
     n, long = 65, 40
-    fc, lc = fv.case("pend-8"), host.case("pend-view")
+    fc, lc = clc.case("pend-8"), host.case("pend-view")
     params, init, A = fc["params"][:n], fc["init"][:n], fc["ref"].A
 
     def dense(e, t, seed):
@@ -273,7 +272,7 @@ def test_one_workspace_serves_linear_fnn_linear_in_turn(vs):
         return e.lin_param_grad(t, dense(e, t, seed))
 
     def network(e, t, seed):
-        record_mode2(e, long, params, lambda e: fv.set_net(e, fc["net"]), init, (t,))
+        record_mode2(e, long, params, lambda e: clc.set_net(e, fc["net"]), init, (t,))
         return e.fnn_param_grad(t, dense(e, t, seed))
 
     steps = ((linear, 3, 4), (network, long, 5), (linear, long, 6))
@@ -373,9 +372,9 @@ def test_refusals_leave_the_output_untouched(vs):
 # ------------------------------------------------------------------------------------------------------- 6. autograd
 @pytest.mark.parametrize("name", ["qq-su", "qcp-su"])
 def test_autograd_kernel_against_torch(vs, name, monkeypatch):
-    tc = pv.torch_case(name)
-    NT, TT = pv.NT, pv.TT
-    env = getattr(vs, pv.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    tc = clc.torch_case("linear", name)
+    NT, TT = clc.NT, clc.TT
+    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
     with torch.no_grad():
         policy.net.weight.copy_(torch.as_tensor(tc["W"]))
@@ -384,7 +383,7 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     def grads(roll):
         init = dev(tc["init"]).requires_grad_(True)
         obs, rew, act, lengths = roll(init, TT)
-        loss = -vs.discounted_return(rew, lengths, pv.GAMMA).sum() + 1e-3 * act.pow(2).sum()
+        loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
         return torch.autograd.grad(loss, [weight, init], retain_graph=True), loss, (obs, rew, act)
 
     by_torch = vs.DifferentiablePolicyRollout(env, policy, batch_lanes=32, param_pass="torch")
@@ -403,7 +402,7 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     assert roll.param_pass == "kernel" and not roll._needs_rows
     init = dev(tc["init"]).requires_grad_(True)
     obs, rew, act, lengths = roll(init, TT)                      # the forward pass reads the records; the backward pass must not
-    loss = -vs.discounted_return(rew, lengths, pv.GAMMA).sum() + 1e-3 * act.pow(2).sum()
+    loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
     assert all(torch.equal(a, b) for a, b in zip((obs, rew, act), out_torch))
 
     def no_rows(*a, **k):
@@ -423,7 +422,7 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     assert [s[4] for s in seen] == [False, True, True] and [s[2].shape[0] for s in seen] == [32, 32, 6]  # three batches accumulate
     bound = 0.0
     for ob, inside, abar, ld, _ in seen:
-        bound = bound + host.lin_param_grad_fp64(pv.SMALL, None, ob, abar.transpose(1, 0, 2).reshape(TT * abar.shape[0], -1), inside,
+        bound = bound + host.lin_param_grad_fp64(clc.SMALL, None, ob, abar.transpose(1, 0, 2).reshape(TT * abar.shape[0], -1), inside,
                                                  chain=host.chain_of(ld, TT, n_cu()))[2]
     assert g_kernel[0].shape == weight.shape
     flat = lambda g: g.detach().cpu().numpy().astype(np.float64)  # noqa: E731
@@ -435,15 +434,15 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
 
 def test_autograd_fp64_weights_take_the_torch_pass(vs):
     name = "qq-su"
-    tc = pv.torch_case(name)
-    env = getattr(vs, pv.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    tc = clc.torch_case("linear", name)
+    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
     with torch.no_grad():
         policy.net.weight.copy_(torch.as_tensor(tc["W"]))
     policy.double()
     roll = vs.DifferentiablePolicyRollout(env, policy, batch_lanes=32, param_pass="kernel")
     assert roll.param_pass == "torch"
-    obs, rew, act, lengths = roll(dev(tc["init"]), pv.TT)
-    g, = torch.autograd.grad(-vs.discounted_return(rew, lengths, pv.GAMMA).sum() + 1e-3 * act.pow(2).sum(), [policy.net.weight])
+    obs, rew, act, lengths = roll(dev(tc["init"]), clc.TT)
+    g, = torch.autograd.grad(-vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum(), [policy.net.weight])
     assert g.dtype == torch.float64 and bool(torch.isfinite(g).all()) and bool(g.any())
     roll.close()

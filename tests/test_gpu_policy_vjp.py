@@ -5,7 +5,7 @@ in the loop), VecSimEnv.rollout_vjp_policy and DifferentiablePolicyRollout.
 Shapes are those of test_gpu_rollout_vjp.py: 150 lanes (three waves, the last one partial), T = 24 steps, max_steps = 50, +-5 % per-lane
 parameters, lanes 0 .. 9 start at the edge of the state space and end early, random cotangents on all four cotangent inputs.
 
-The reference is a closed-loop fp64 rollout: oracle.cpu_ref for the step, the NumPy feature stack below for the policy,
+The reference is a closed-loop fp64 rollout (closed_loop_cases.py): oracle.cpu_ref for the step, the NumPy feature stack for the policy,
 a_t = W phi(obs_t) + n_t with an additive per-step offset n_t (0 unless a test says otherwise).  Central differences of Phi at relative
 steps 1e-6 and 1e-5 with respect to every n_t entry (-> d_act, the total adjoint of a_t) and every initial-state entry (-> d_init), the
 lane's length held at its unperturbed value, per unit of the input's scale (ACT_IN, INIT_SCALE).  Tolerance, per lane, the project's:
@@ -22,32 +22,16 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import cpu_ref
-
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import closed_loop_cases as clc  # noqa: E402
+from closed_loop_cases import (ENVS, GAMMA, LINEAR_ORACLE_CASES as ORACLE_CASES, NT, TT, case, check_policy_keeps_the_box, cotangents,  # noqa: E402
+                               features, feedback_seen, hidden_reference, linear_policy, oracle_reference, recorded, reference)
 from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, SPLITS, STARTS, STATE_BUFFERS, T,  # noqa: E402
-                              case_cotangents, check_hidden_block, check_hidden_start, dev, draw_params_and_init, frozen, hidden_conditions,
-                              hidden_differences, hidden_start, lengths_of, record_mode2, scaled, scaled_hidden, smooth_per_lane, start_hidden,
-                              tolerance_per_lane, within_per_lane)
-
-ELEM = ("identity", "squared", "cubic", "sig", "bell", "sin", "cos", "sinsin", "sincos")
-SMALL = ("identity", "sin", "const", ("mult", (0, 1)))
-# case -> (family, the stack in order, obs_idx or None)
-CASES = {
-    "qq-su": ("qq-su", ELEM + ("const", ("mult", (4, 5)), ("mult", (0, 4, 0)), ("atan2", (0, 1))), None),
-    "omo": ("omo", ELEM + ("const", ("mult", (0, 1)), ("mult", (1, 0, 1))), None),
-    "omo-kinks": ("omo", ("identity", "sign", "abs", "const", ("mult", (0, 1))), None),
-    "bob": ("bob", SMALL, None),
-    "qcp-su": ("qcp-su", SMALL, None),
-    "pend-view": ("pend", SMALL, (2, 0)),          # the policy sees (th_dot, sin th): a permuted strict subset of the rows
-    "qbb": ("qbb", SMALL, None),
-    "pend-const": ("pend", ("const",), None), "omo-const": ("omo", ("const",), None), "bob-const": ("bob", ("const",), None),
-    "qq-su-const": ("qq-su", ("const",), None), "qcp-su-const": ("qcp-su", ("const",), None), "qbb-const": ("qbb", ("const",), None),
-}
-ORACLE_CASES = ["qq-su", "omo", "omo-kinks", "bob", "qcp-su", "pend-view", "qbb"]
+                              check_hidden_block, check_hidden_start, dev, hidden_conditions, hidden_start, scaled, scaled_hidden,
+                              smooth_per_lane, within_per_lane)
 
 
 @pytest.fixture(scope="module")
@@ -59,179 +43,6 @@ def vs():
     return simurlacra_amd
 
 
-# ------------------------------------------------------------------------------------------------ the fp64 feature stack
-def features(terms, x):
-    """phi [n, F] of the visible rows x [n, n_vis] (fp64), the stack in order"""
-    sg = 1.0 / (1.0 + np.exp(-x))
-    elem = {"identity": x, "sign": np.sign(x), "abs": np.abs(x), "squared": x ** 2, "cubic": x ** 3, "sig": sg,
-            "bell": np.exp(-x ** 2 / 2.0), "sin": np.sin(x), "cos": np.cos(x), "sinsin": np.sin(x) ** 2, "sincos": np.sin(x) * np.cos(x)}
-    cols = []
-    for t in terms:
-        if t == "const":
-            cols.append(np.ones((x.shape[0], 1)))
-        elif isinstance(t, str):
-            cols.append(elem[t])
-        elif t[0] == "mult":
-            cols.append(np.prod(x[:, list(t[1])], axis=1, keepdims=True))
-        else:
-            cols.append(np.arctan2(x[:, t[1][0]], x[:, t[1][1]])[:, None])
-    return np.concatenate(cols, axis=1)
-
-
-def closed_loop(ref, params, state0, hidden0, terms, obs_idx, W, offs, open_acts=None):
-    """the fp64 oracle under a_t = W phi(obs_t) + offs[:, t] (it does not freeze at done), or along open_acts [n, T, A] ->
-    states [T + 1, n, S], hiddens [T + 1, n, H], obs [T + 1, n, O], rew [T, n], done [T, n], acts [T, n, A]"""
-    st, hid = state0.copy(), hidden0.copy()
-    ob = ref.observe(st)
-    states, hiddens, obs, rew, done, acts = [st], [hid], [ob], [], [], []
-    with np.errstate(all="ignore"):
-        for t in range(offs.shape[1]):
-            if open_acts is None:
-                x = ob if obs_idx is None else ob[:, list(obs_idx)]
-                a = features(terms, x) @ W.T + offs[:, t]
-            else:
-                a = open_acts[:, t]
-            out = ref.step(st, hid, a, params, np.full(st.shape[0], t))
-            st, hid, ob = out["state"], out["hidden"], out["obs"]
-            states.append(st), hiddens.append(hid), obs.append(ob), rew.append(out["rew"]), done.append(out["done"]), acts.append(a)
-    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done), np.stack(acts)
-
-
-def make_weights(ref, name, terms, obs_idx, params, s0, h0, rng, n_steps):
-    """W [A, F] float32 (see the module docstring)"""
-    n_vis = ref.O if obs_idx is None else len(obs_idx)
-    F = features(terms, np.zeros((1, n_vis))).shape[1]
-    const_at = [q for q, on in enumerate(_const_mask(terms, n_vis)) if on]
-    W = np.zeros((ref.A, F))
-    if const_at:
-        W[:, const_at[0]] = 0.45 * ACT_IN[name] * rng.choice([-1.0, 1.0], ref.A)
-    obs = closed_loop(ref, params, s0, h0, terms, obs_idx, W, np.zeros((s0.shape[0], n_steps, ref.A)))[2]
-    x = obs.reshape(-1, ref.O)
-    x = x if obs_idx is None else x[:, list(obs_idx)]
-    top = np.maximum(np.abs(features(terms, x)).max(axis=0), 1e-3)
-    for q in range(F):
-        if q not in const_at:
-            W[:, q] = 0.12 * ACT_IN[name] / (F * top[q]) * rng.choice([-1.0, 1.0], ref.A)
-    return W.astype(np.float32)
-
-
-def _const_mask(terms, n_vis):
-    out = []
-    for t in terms:
-        out += [t == "const"] * (n_vis if isinstance(t, str) and t != "const" else 1)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def case(key):
-    """the inputs of a case, float32 and left unchanged by the tests: params [N, P], init [N, S], W [A, F] and the cotangents
-    g_rew [N, T], g_obs [N, T + 1, O], g_act [N, T, A], g_last [N, S + H]"""
-    name, terms, obs_idx = CASES[key]
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(29)
-    params, init = draw_params_and_init(ref, name, rng)
-    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    W = make_weights(ref, name, terms, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T)
-    return frozen(dict(name=name, terms=terms, obs_idx=obs_idx, ref=ref, params=params, init=init, h0=h0, W=W,
-                       g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
-                       g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32)))
-
-
-def phi(c, state0, offs, length, open_acts=None, hidden0=None):
-    """[N]: sum g_rew r + sum g_obs . obs + sum g_act . a + g_last . (s_L, h_L) of every lane over its first length[n] steps, from the
-    initial hidden state hidden0 (None: the one the oracle's reset leaves)"""
-    states, hiddens, obs, rew, _, acts = closed_loop(c["ref"], c["params"].astype(np.float64), state0, c["h0"] if hidden0 is None else hidden0,
-                                                     c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs, open_acts)
-    k = np.arange(T + 1)[:, None]
-    n = np.arange(state0.shape[0])
-    inside = k[:T] < length[None, :]
-    out = np.where(inside, c["g_rew"].T.astype(np.float64) * rew, 0.0).sum(axis=0)
-    out += np.where(inside[:, :, None], c["g_act"].transpose(1, 0, 2).astype(np.float64) * acts, 0.0).sum(axis=(0, 2))
-    out += np.where((k <= length[None, :])[:, :, None], c["g_obs"].transpose(1, 0, 2).astype(np.float64) * obs, 0.0).sum(axis=(0, 2))
-    last = np.concatenate([states[length, n], hiddens[length, n]], axis=1)
-    return out + (c["g_last"].astype(np.float64) * last).sum(axis=1)
-
-
-def reference(c, offs0, h0=None):
-    """central differences of Phi at relative steps 1e-6 and 1e-5: two arrays [N, T * A + S] (offsets first, step-major), the
-    oracle's lane lengths, its actions [T, N, A], and d_init [N, S] of the OPEN loop along those actions (step 1e-6); h0: the initial
-    hidden state (None: the one the oracle's reset leaves)"""
-    ref, name = c["ref"], c["name"]
-    s0 = c["init"].astype(np.float64)
-    h0 = c["h0"] if h0 is None else h0
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)
-    length, acts = lengths_of(roll[4]), roll[5]
-    out = []
-    for h in (1e-6, 1e-5):
-        g = np.zeros((N, T * ref.A + ref.S))
-        for t in range(T):
-            for j in range(ref.A):
-                d = np.zeros_like(offs0)
-                d[:, t, j] = h * ACT_IN[name]
-                g[:, t * ref.A + j] = (phi(c, s0, offs0 + d, length, hidden0=h0) - phi(c, s0, offs0 - d, length, hidden0=h0)) / (2.0 * h)
-        for j in range(ref.S):
-            d = np.zeros_like(s0)
-            d[:, j] = h * INIT_SCALE[name][j]
-            g[:, T * ref.A + j] = (phi(c, s0 + d, offs0, length, hidden0=h0) - phi(c, s0 - d, offs0, length, hidden0=h0)) / (2.0 * h)
-        out.append(g)
-    open_init = np.zeros((N, ref.S))
-    fixed = acts.transpose(1, 0, 2)
-    for j in range(ref.S):
-        d = np.zeros_like(s0)
-        d[:, j] = 1e-6 * INIT_SCALE[name][j]
-        open_init[:, j] = (phi(c, s0 + d, offs0, length, fixed, hidden0=h0) - phi(c, s0 - d, offs0, length, fixed, hidden0=h0)) / 2e-6
-    return out[0], out[1], length, acts, open_init
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_reference(key, start="reset"):
-    c = case(key)
-    return reference(c, np.zeros((N, T, c["ref"].A)), start_hidden(c["name"], c, start))
-
-
-@functools.lru_cache(maxsize=None)
-def hidden_reference(key, start):
-    """the hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the policy has no state of its
-    own and no noise; the lane lengths are held), and the oracle's lane lengths"""
-    c = case(key)
-    h0 = start_hidden(c["name"], c, start)
-    offs0 = np.zeros((N, T, c["ref"].A))
-    s0 = c["init"].astype(np.float64)
-    length = lengths_of(closed_loop(c["ref"], c["params"].astype(np.float64), s0, h0, c["terms"], c["obs_idx"], c["W"].astype(np.float64), offs0)[4])
-    g1, g2 = hidden_differences(c["name"], lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
-    return g1, g2, length
-
-
-def recorded(vs, key, splits=(T,), noise_std=None, noise_seed=0, hidden=None):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case, recorded in mode 2 by step_policy in the given launches;
-    hidden [N, H]: the initial hidden state in place of reset's"""
-    c = case(key)
-    name = c["name"]
-    e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
-
-    def linear(e):
-        e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
-
-    return record_mode2(e, T, c["params"], linear, c["init"], splits, hidden=hidden, noise_seed=noise_seed)
-
-
-def cotangents(vs, key, e, with_act=True):
-    c = case(key)
-    out = case_cotangents(vs, c, e)
-    if with_act:
-        out["g_act"] = vs.lanes_last(dev(c["g_act"]), e.ld)
-    return out
-
-
-def check_policy_keeps_the_box(c, acts, length):
-    """the oracle's actions inside the lengths: the bias +- at most 0.15 ACT_IN, hence |a| in [0.30, 0.60] ACT_IN"""
-    W, name = c["W"].astype(np.float64), c["name"]
-    n_vis = c["ref"].O if c["obs_idx"] is None else len(c["obs_idx"])
-    bias = W[:, np.array(_const_mask(c["terms"], n_vis))].sum(axis=1)
-    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
-    assert (np.abs(np.where(inside, acts - bias, 0.0)) <= 0.15 * ACT_IN[name]).all(), name
-
-
 # ----------------------------------------------------------------------------------- 1. + 2. against the fp64 oracle
 @pytest.mark.parametrize("key", ORACLE_CASES)
 def test_against_the_closed_loop_fp64_oracle(vs, key):
@@ -239,18 +50,15 @@ def test_against_the_closed_loop_fp64_oracle(vs, key):
     (oscillator with either stack, cartpole, pendulum through obs_idx), below 0.0005 (ball-on-beam, ball balancer); every entry smooth,
     no bad entry; the feedback is seen on 0.55 (cartpole) to 0.96 (ball balancer) of the full-length lanes."""
     c = case(key)
-    ref = c["ref"]
-    f1, f2, length, acts, open_init = oracle_reference(key)
-    smooth = smooth_per_lane(f1, f2)
+    r = oracle_reference(key)
+    f1, length = r.f1, r.length
+    smooth = smooth_per_lane(f1, r.f2)
     assert (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
-    check_policy_keeps_the_box(c, acts, length)
+    check_policy_keeps_the_box(c, r.acts, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
     # ---- the test can see the feedback (oracle alone): closed- and open-loop d_init differ by more than 10 x the tolerance on at
     # least half of the full-length lanes
-    init_cols = slice(T * ref.A, None)
-    gap = np.abs(f1[:, init_cols] - open_init) > 10.0 * tolerance_per_lane(f1, smooth)[:, init_cols]
-    full = length == T
-    seen = float(gap.any(axis=1)[full].mean())
+    seen = feedback_seen(c, f1, smooth, r.open_init, length)
     assert seen >= 0.5, (key, seen)
     e = recorded(vs, key)
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
@@ -285,10 +93,10 @@ def test_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, key, start):
     e.close()
     check_hidden_block(f"{key} vs_rollout_vjp_policy from {start}", scaled_hidden(vs, c, di), g1, g2)
     if start == "perturbed":
-        f1, f2, length2, acts, _ = oracle_reference(key, start)
-        smooth = smooth_per_lane(f1, f2)
-        assert np.array_equal(length2, length) and (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
-        check_policy_keeps_the_box(c, acts, length)
+        r = oracle_reference(key, start)
+        f1, smooth = r.f1, smooth_per_lane(r.f1, r.f2)
+        assert np.array_equal(r.length, length) and (~smooth).mean() <= 0.01, (key, float((~smooth).mean()))  # from the oracle alone
+        check_policy_keeps_the_box(c, r.acts, length)
         bad, worst = within_per_lane(scaled(vs, c, da, di), f1, smooth)
         print(f"{key} from {start}: offsets and states: not smooth {(~smooth).mean():.4f}, bad share {bad:.2e}, worst error / tolerance {worst:.3f}")
         assert bad <= 2e-3, (key, bad, worst)
@@ -353,8 +161,8 @@ def test_exploration_noise_is_an_additive_constant(vs):
     x = obs.reshape(T * N, ref.O)[:, list(c["obs_idx"])]
     offs = (act - (features(c["terms"], x) @ c["W"].astype(np.float64).T).reshape(T, N, ref.A)).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
-    f1, f2, length, _, _ = reference(c, np.ascontiguousarray(offs))
-    smooth = smooth_per_lane(f1, f2)
+    r = reference(c, np.ascontiguousarray(offs))
+    f1, length, smooth = r.f1, r.length, smooth_per_lane(r.f1, r.f2)
     assert (~smooth).mean() <= 0.01
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_policy(T, **cotangents(vs, key, e)))
@@ -434,30 +242,13 @@ def test_refusals_leave_the_outputs_untouched(vs):
 
 
 # ----------------------------------------------------------------------------------------------------------- 7. autograd
-ENVS = {"qq-su": "QQubeSwingUpSim", "qcp-su": "QCartPoleSwingUpSim"}
-NT, TT, GAMMA = 70, 12, 0.99
-
-
-@functools.lru_cache(maxsize=None)
 def torch_case(name):
-    """init [NT, S] float32, the policy's weights W [A, F] float32 and the oracle's pieces for the loss of test 7"""
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(37)
-    init = (rng.uniform(-1.0, 1.0, (NT, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32)
-    params = np.tile(ref.nominal_params(1).astype(np.float32).astype(np.float64), (NT, 1))
-    h0 = ref.reset(params, init.astype(np.float64), True)["hidden"]
-    W = make_weights(ref, name, SMALL, None, params, init.astype(np.float64), h0, rng, TT)
-    return dict(ref=ref, init=init, params=params, h0=h0, W=W)
+    return clc.torch_case("linear", name)
 
 
 def oracle_loss(name, W, s0, length=None):
-    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop, and the lane lengths"""
-    tc = torch_case(name)
-    _, _, _, rew, done, acts = closed_loop(tc["ref"], tc["params"], s0, tc["h0"], SMALL, None, W, np.zeros((NT, TT, tc["ref"].A)))
-    length = lengths_of(done) if length is None else length
-    inside = np.arange(TT)[:, None] < length[None, :]
-    disc = GAMMA ** np.arange(TT)[:, None]
-    return -np.where(inside, disc * rew, 0.0).sum(axis=0) + 1e-3 * np.where(inside[:, :, None], acts ** 2, 0.0).sum(axis=(0, 2)), length
+    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop under the weights W [A, F], and the lane lengths"""
+    return clc.oracle_loss(torch_case(name), linear_policy(clc.SMALL, None, W), s0, length)
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,7 +2,7 @@
 vs_rnn_param_grad / k_rnn_param_grad (+ k_fnn_param_reduce): the parameter gradient of a recurrent policy over the recorded rows of a
 handle, VecSimEnv.rnn_param_grad and DifferentiableRecurrentRollout(param_pass="kernel").
 
-Shapes: 70 lanes (ld = 128: one full lane group and one of six lanes), T = 12.  The policies are test_gpu_rnn_vjp.make_rnn's; the records
+Shapes: 70 lanes (ld = 128: one full lane group and one of six lanes), T = 12.  The policies are closed_loop_cases.make_rnn's; the records
 come from a recording step_policy launch, abar and d_hid from vs_rollout_vjp_rnn under random cotangents (g_act and g_hid_last
 included).  Lanes 0 .. 9 start at the edge of the state space and so do lanes 64 .. 69 -- the whole second lane group --, so that some
 rollouts of the first group and, where the family's edge is close enough, all of the second end before T.
@@ -28,10 +28,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import closed_loop_cases as clc  # noqa: E402  (make_rnn, flat_params, set_rnn, the autograd cases; the [8] tanh network of the pendulum)
 import rnn_param_grad_fp64 as ref64  # noqa: E402
 import test_fnn_param_grad_host as fnn_host  # noqa: E402  (the FNN pass's fp64 reference and bound)
-import test_gpu_fnn_vjp as fv  # noqa: E402  (the [8] tanh network of the pendulum)
-import test_gpu_rnn_vjp as rv  # noqa: E402  (make_rnn, flat_params, set_rnn, the autograd cases)
 from derivative_cases import ACT_IN, KW, MAX_STEPS, STATE_BUFFERS, dev, draw_params_and_init, frozen, record_mode2  # noqa: E402
 
 N, T = 70, 12
@@ -68,8 +67,8 @@ def case(key):
     lanes = np.concatenate([np.arange(64), np.arange(6)])        # the second lane group: six edge lanes
     params, init = params[lanes].copy(), init[lanes].copy()
     h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    net = rv.make_rnn(ref, name, cell, n_layers, H, out, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T, gain, whh)
-    Hs = rv.cells.hidden_size(net["cell"])
+    net = clc.make_rnn(ref, name, cell, n_layers, H, out, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T, gain, whh)
+    Hs = clc.hidden_size(net["cell"])
     cot = lambda *shape: (rng.normal(size=shape) / (N * T)).astype(np.float32)  # noqa: E731  (see the module docstring)
     return frozen(dict(name=name, ref=ref, params=params, init=init, net=net, Hs=Hs, noisy=noisy, g_rew=cot(N, T), g_obs=cot(N, T + 1, ref.O),
                        g_act=cot(N, T, ref.A), g_last=cot(N, ref.S + ref.H), g_hid=cot(N, Hs)))
@@ -79,7 +78,7 @@ def recorded(vs, key, t=T, cap=T):
     c = case(key)
     e = vs.VecSimEnv(c["name"], N, max_steps=MAX_STEPS, **KW[c["name"]])
     std = [0.02 * ACT_IN[c["name"]]] * c["ref"].A if c["noisy"] else None
-    return record_mode2(e, cap, c["params"], lambda e: rv.set_rnn(e, c["net"], std), c["init"], (t,), noise_seed=91)
+    return record_mode2(e, cap, c["params"], lambda e: clc.set_rnn(e, c["net"], std), c["init"], (t,), noise_seed=91)
 
 
 def sweep(vs, key, e, t=T):
@@ -130,7 +129,7 @@ def test_against_the_fp64_reference(vs, key):
     abar, d_hid = sweep(vs, key, e)
     want, bound, length = reference(vs, key, e, T, abar, d_hid)
     got = e.rnn_param_grad(T, abar, d_hid)
-    assert got.dtype == torch.float32 and got.is_cuda and tuple(got.shape) == (rv.flat_params(case(key)["net"]).size,)
+    assert got.dtype == torch.float32 and got.is_cuda and tuple(got.shape) == (clc.flat_params(case(key)["net"]).size,)
     got = got.cpu().numpy().astype(np.float64)
     assert np.isfinite(got).all() and e.error_count() == 0
     worst = ref64.worst_ratio(np.abs(got - want), 2.0 * bound)
@@ -290,20 +289,20 @@ def test_refusals_leave_the_output_untouched(vs):
     e.set_policy_hidden_record(0)
     refused(L.VS_ERR_STATE, e)
     e.set_policy_hidden_record(c["Hs"])
-    e.set_policy_population(np.tile(rv.flat_params(c["net"])[None, :], (2, 1)), lane_set=np.arange(N) // 64)
+    e.set_policy_population(np.tile(clc.flat_params(c["net"])[None, :], (2, 1)), lane_set=np.arange(N) // 64)
     refused(L.VS_ERR_STATE, e)
     e.set_policy_population(None)
     e.set_policy_rnn(None)                                      # no policy
     refused(L.VS_ERR_STATE, e)
     e.set_policy_linear(np.zeros(d["A"], dtype=np.float32), ["const"])
     refused(L.VS_ERR_STATE, e)
-    rv.set_rnn(e, c["net"])
+    clc.set_rnn(e, c["net"])
     e.set_record_mode(1)
     e.set_traj_capacity(T)
     refused(L.VS_ERR_STATE, e)
     e.set_record_mode(2)
     e.set_traj_capacity(T)
-    rv.set_rnn(e, c["net"])
+    clc.set_rnn(e, c["net"])
     served()                                                    # after the refusals the same handle serves a good call
     assert e.error_count() == 0
     e.close()
@@ -312,19 +311,19 @@ def test_refusals_leave_the_output_untouched(vs):
 # ------------------------------------------------------------------------------------------------------- 5. autograd
 @pytest.mark.parametrize("name", ["pend", "qcp-su"])
 def test_autograd_kernel_against_torch(vs, name, monkeypatch):
-    tc = rv.torch_case(name)
-    NT, TT = rv.NT, rv.TT
-    cell, n_layers, H = rv.AUTOGRAD[name][:3]
-    env = getattr(vs, rv.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
-    policy = rv.cells.torch_policy(env.spec, cell, n_layers, H)
-    th0 = rv.flat_params(tc["net"])
+    tc = clc.torch_case("rnn", name)
+    NT, TT = clc.NT, clc.TT
+    cell, n_layers, H = clc.RNN_AUTOGRAD[name][:3]
+    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
+    policy = clc.torch_policy(env.spec, cell, n_layers, H)
+    th0 = clc.flat_params(tc["net"])
     policy.param_values = torch.as_tensor(th0)
     weights = list(policy.parameters())
 
     def grads(roll):
         init = dev(tc["init"]).requires_grad_(True)
         obs, rew, act, lengths = roll(init, TT)
-        loss = -vs.discounted_return(rew, lengths, rv.GAMMA).sum() + 1e-3 * act.pow(2).sum()
+        loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
         return torch.autograd.grad(loss, weights + [init], retain_graph=True), loss
 
     by_torch = vs.DifferentiableRecurrentRollout(env, policy, batch_lanes=32, param_pass="torch")
@@ -388,7 +387,7 @@ def test_one_workspace_serves_both_policy_kinds_in_turn(vs):
     kernels are deterministic (test_two_calls_and_accumulate_are_exact), so a stale map, a buffer of another width or a regrow under
     a running launch would show, and nothing else can differ."""
     n, long = 65, 40
-    fc, gc = fv.case("pend-8"), case("pend-gru-8")
+    fc, gc = clc.case("pend-8"), case("pend-gru-8")
     params, init, A = fc["params"][:n], fc["init"][:n], fc["ref"].A
 
     def record(e, t, set_policy):
@@ -397,7 +396,7 @@ def test_one_workspace_serves_both_policy_kinds_in_turn(vs):
     def dense(e, t, width, seed):
         return torch.randn(t, width, e.ld, device="cuda", generator=torch.Generator("cuda").manual_seed(seed))
 
-    def fnn_short(e, set_policy=lambda e: fv.set_net(e, fc["net"])):
+    def fnn_short(e, set_policy=lambda e: clc.set_net(e, fc["net"])):
         record(e, 3, set_policy)
         ll = lambda x: vs.lanes_last(dev(x), e.ld)  # noqa: E731
         da, _ = e.rollout_vjp_fnn(3, g_rew=ll(fc["g_rew"][:n, :3]), g_obs=ll(fc["g_obs"][:n, :4]), g_act=ll(fc["g_act"][:n, :3]),
@@ -405,11 +404,11 @@ def test_one_workspace_serves_both_policy_kinds_in_turn(vs):
         return e.fnn_param_grad(3, da)
 
     def gru_long(e):
-        record(e, long, lambda e: rv.set_rnn(e, gc["net"]))
+        record(e, long, lambda e: clc.set_rnn(e, gc["net"]))
         return e.rnn_param_grad(long, dense(e, long, A, 6), dense(e, long, gc["Hs"], 7))
 
     def fnn_long(e):
-        record(e, long, lambda e: fv.set_net(e, fc["net"]))
+        record(e, long, lambda e: clc.set_net(e, fc["net"]))
         return e.fnn_param_grad(long, dense(e, long, A, 5))
 
     def handle():

@@ -5,13 +5,13 @@ relu, GRU, LSTM of one or two layers) in the loop, VecSimEnv.rollout_vjp_rnn and
 Shapes, scales and the tolerance rule are those of test_gpu_fnn_vjp.py / test_gpu_policy_vjp.py, all three from derivative_cases.py: 150 lanes
 (64 + 64 + 22), T = 24, max_steps = 50, +-5 % per-lane parameters, lanes 0 .. 9 end early, random cotangents on all FIVE inputs (g_rew,
 g_obs, g_act, g_state_last, g_hid_last); per lane 3e-3 |g| + 3e-4 max |g| against central differences of the fp64 closed loop at relative
-steps 1e-6 and 1e-5 (oracle.cpu_ref for the step, the NumPy cells of test_rnn_vjp_host.py for the policy).  The tolerance is taken
+steps 1e-6 and 1e-5 (closed_loop_cases.py: oracle.cpu_ref for the step, its NumPy cells for the policy).  The tolerance is taken
 separately over the two blocks of a lane's entries: [every action offset n_t | every initial-state entry] and [every initial-hidden
 entry (d_hid0) | additive offsets on p_{t+1} at a fixed random set of 40 (t, unit) pairs (d_hid), every layer's h and c block among
 them; all T pairs of the one-unit cell] -- stricter than one maximum over both.  EVERY entry must be smooth, from the oracle alone, and
 every entry is compared.
 
-The weights (make_rnn):
+The weights (closed_loop_cases.make_rnn):
   * the policy's input rows are measured on a rollout under the bias action alone: mid and dev = half their range;
   * W_ih (x - mid) is bounded by amp = 1 (relu: 0.3) on that rollout, rows scaled by 1 / sqrt(fan-in) (relu: 1 / fan-in); layer 1 sees
     h' in [-1, 1] (relu: [0, 2]) with the same rule; the sum b_ih + b_hh is +-U(0, 0.7) (relu: +-U(0.5, 1.5), unit 0 of every layer
@@ -31,36 +31,17 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import cpu_ref
-
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_rnn_vjp_host as cells  # noqa: E402  (the fp64 cells)
-from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T, TANH_OUT_AMP,  # noqa: E402
-                              TANH_OUT_AT, case_cotangents, check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev,
-                              draw_params_and_init, frozen, hidden_conditions, hidden_differences, hidden_start, lengths_of, record_mode2,
-                              scaled_hidden, smooth_per_lane, start_hidden, tolerance_per_lane, worst_of)
-
-# case -> (family, cell, layers, units, output nonlinearity, obs_idx, seed, gain of the output layer, whh)
-CASES = {
-    "omo-tanh-1": ("omo", "tanh", 1, 1, None, None, 31, 1.0, 1.5),
-    "omo-relu-2x3": ("omo", "relu", 2, 3, None, None, 52, 2.0, 4.0),
-    "pend-view-gru-5": ("pend", "gru", 1, 5, None, (2, 0), 3, 2.5, 1.0),   # the policy sees (th_dot, sin th)
-    "qq-su-gru-2x64": ("qq-su", "gru", 2, 64, None, None, 4, 3.0, 1.0),
-    "qcp-su-lstm-33": ("qcp-su", "lstm", 1, 33, None, None, 5, 3.0, 1.0),
-    "qbb-lstm-2x64-tanh-out": ("qbb", "lstm", 2, 64, "tanh", None, 6, 1.0, 1.0),  # the LDS worst case
-    "bob-gru-64": ("bob", "gru", 1, 64, None, None, 7, 3.0, 1.0),
-    "pend-lstm-8": ("pend", "lstm", 1, 8, None, None, 8, 3.0, 1.0),
-}
-ORACLE_CASES = [k for k in CASES if k != "pend-lstm-8"]
-# Elman tanh cells WITHOUT recurrence (whh = 0: W_hh is all zeros) -- the feed-forward network [H] tanh with bias b_ih + b_hh
-ELMAN_AS_FNN = {
-    "omo-elman-3": ("omo", "tanh", 1, 3, None, None, 61, 1.0, 0.0),        # padding to 4 units
-    "qq-su-elman-64": ("qq-su", "tanh", 1, 64, None, None, 62, 3.0, 0.0),  # the full width
-}
-N_PAIRS = 40
+import closed_loop_cases as clc  # noqa: E402
+from closed_loop_cases import (ELMAN_AS_FNN, ENVS, GAMMA, NT, RNN_AUTOGRAD as AUTOGRAD, RNN_ORACLE_CASES as ORACLE_CASES, TT, block_tolerance,  # noqa: E402
+                               blocks_of, case, check_no_unit_near_a_kink, cotangents, flat_params, hidden_reference, oracle_reference,
+                               recorded, reference, rnn_policy, rnn_step, shares, torch_policy, unpack_rnn, worst_in_blocks)
+from derivative_cases import (ACT_IN, HIDDEN_FAMILIES, INIT_SCALE, KW, MAX_STEPS, N, N_EDGE, STARTS, STATE_BUFFERS, T,  # noqa: E402
+                              check_hidden_block, check_hidden_start, check_net_keeps_the_box, dev, hidden_conditions, hidden_start,
+                              scaled_hidden, smooth_per_lane, worst_of)
 
 
 @pytest.fixture(scope="module")
@@ -70,267 +51,6 @@ def vs():
     import simurlacra_amd
 
     return simurlacra_amd
-
-
-# ------------------------------------------------------------------------------------------------ the fp64 closed loop
-def policy_input(net, ob):
-    return ob if net["obs_idx"] is None else ob[:, list(net["obs_idx"])]
-
-
-def closed_loop(ref, params, state0, hidden0, net, offs, open_acts=None, p0=None, hid_off=None, fixed_p=None):
-    """the fp64 oracle under (a_t, p_{t+1}) = F(x_t, p_t) + (offs[:, t], 0), p_0 = p0 (zeros: init_hidden()); hid_off = (t, unit, d [n]):
-    p_{t+1}[:, unit] += d; fixed_p [T + 1, n, Hs]: the policy is evaluated at these hidden states instead of its own (the hidden adjoint
-    cut); open_acts [n, T, A]: no policy.  -> states, hiddens, obs, rew, done, acts, ps [T + 1, n, Hs], Elman pre-activations"""
-    st, hid = state0.copy(), hidden0.copy()
-    n = st.shape[0]
-    p = np.zeros((n, cells.hidden_size(net["cell"]))) if p0 is None else p0.copy()
-    ob = ref.observe(st)
-    states, hiddens, obs, rew, done, acts, ps, pres = [st], [hid], [ob], [], [], [], [p], []
-    with np.errstate(all="ignore"):
-        for t in range(offs.shape[1]):
-            if open_acts is None:
-                mean, p_new, pre = cells.rnn_step(net["cell"], policy_input(net, ob), p if fixed_p is None else fixed_p[t], net["output_nonlin"])
-                a = mean + offs[:, t]
-                pres.append(pre)
-                if hid_off is not None and hid_off[0] == t:
-                    p_new = p_new.copy()
-                    p_new[:, hid_off[1]] += hid_off[2]
-                p = p_new
-            else:
-                a = open_acts[:, t]
-            out = ref.step(st, hid, a, params, np.full(n, t))
-            st, hid, ob = out["state"], out["hidden"], out["obs"]
-            states.append(st), hiddens.append(hid), obs.append(ob), rew.append(out["rew"]), done.append(out["done"]), acts.append(a)
-            ps.append(p)
-    return np.stack(states), np.stack(hiddens), np.stack(obs), np.stack(rew), np.stack(done), np.stack(acts), np.stack(ps), pres
-
-
-def flat_params(net):
-    """torch's order"""
-    c = net["cell"]
-    parts = []
-    for w in c["layers"]:
-        parts += [w["w_ih"].reshape(-1), w["w_hh"].reshape(-1), w["b_ih"], w["b_hh"]]
-    return np.concatenate(parts + [c["w_out"].reshape(-1), c["b_out"]]).astype(np.float32)
-
-
-def make_rnn(ref, name, cell, n_layers, H, output_nonlin, obs_idx, params, s0, h0, rng, n_steps, gain, whh):
-    """the policy of the module docstring; every weight is a float32 value (held in fp64 arrays)"""
-    A = ref.A
-    G = cells.GATES[cell]
-    relu = cell == "relu"
-    sign = lambda *shape: rng.choice([-1.0, 1.0], shape)  # noqa: E731
-    n_in = ref.O if obs_idx is None else len(obs_idx)
-    target = sign(A) * (TANH_OUT_AT if output_nonlin == "tanh" else 0.45 * ACT_IN[name])
-    amp_out = gain * (TANH_OUT_AMP if output_nonlin == "tanh" else 0.12 * ACT_IN[name])
-    zero = dict(cell=cell, n_layers=n_layers, hidden=H, w_out=np.zeros((A, H)), b_out=target,
-                layers=[dict(w_ih=np.zeros((G * H, n_in if l == 0 else H)), w_hh=np.zeros((G * H, H)), b_ih=np.zeros(G * H),
-                             b_hh=np.zeros(G * H)) for l in range(n_layers)])
-    net = dict(cell=zero, output_nonlin=output_nonlin, obs_idx=obs_idx)
-    obs = closed_loop(ref, params, s0, h0, net, np.zeros((s0.shape[0], n_steps, A)))[2].reshape(-1, ref.O)  # under the bias action alone
-    x = policy_input(net, obs)
-    mid, dv = (x.max(axis=0) + x.min(axis=0)) / 2.0, (x.max(axis=0) - x.min(axis=0)) / 2.0
-    dv = np.where(dv > 1e-6 * (1.0 + np.abs(mid)), dv, 1.0)
-    f32 = lambda v: v.astype(np.float32).astype(np.float64)  # noqa: E731
-    layers = []
-    for l in range(n_layers):
-        fan = n_in if l == 0 else H
-        m, d = (mid, dv) if l == 0 else ((np.ones(H), np.ones(H)) if relu else (np.zeros(H), np.ones(H)))
-        amp, blo, bhi = (0.3, 0.5, 1.5) if relu else (1.0, 0.0, 0.7)
-        w_ih = rng.uniform(0.5, 1.0, (G * H, fan)) * sign(G * H, fan) * amp / ((fan if relu else np.sqrt(fan)) * d)
-        bs = sign(G * H)
-        if relu:
-            bs[0] = 1.0
-        b = rng.uniform(blo, bhi, G * H) * bs - w_ih @ m
-        w_hh = rng.uniform(0.5, 1.0, (G * H, H)) * sign(G * H, H) * whh / (2.0 * H if relu else np.sqrt(H))
-        layers.append(dict(w_ih=f32(w_ih), w_hh=f32(w_hh), b_ih=f32(b / 2.0), b_hh=f32(b / 2.0)))
-    # ---- the output layer on the measured range of the top layer's h' (under the bias action alone, as above)
-    silent = dict(net, cell=dict(zero, layers=layers))
-    top = closed_loop(ref, params, s0, h0, silent, np.zeros((s0.shape[0], n_steps, A)))[6][1:, :, (n_layers - 1) * H:n_layers * H].reshape(-1, H)
-    hm, hd = (top.max(axis=0) + top.min(axis=0)) / 2.0, (top.max(axis=0) - top.min(axis=0)) / 2.0
-    hd = np.where(hd > 1e-6 * (1.0 + np.abs(hm)), hd, 1.0)
-    w_out = f32(sign(A, H) * amp_out / (H * hd))
-    cell_net = dict(cell=cell, n_layers=n_layers, hidden=H, layers=layers, w_out=w_out, b_out=f32(target - w_out @ hm))
-    return dict(cell=cell_net, output_nonlin=output_nonlin, obs_idx=obs_idx)
-
-
-@functools.lru_cache(maxsize=None)
-def case(key):
-    """the inputs of a case, float32 values and left unchanged by the tests"""
-    name, cell, n_layers, H, output_nonlin, obs_idx, seed, gain, whh = {**CASES, **ELMAN_AS_FNN}[key]
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(300 + seed)
-    params, init = draw_params_and_init(ref, name, rng)
-    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    net = make_rnn(ref, name, cell, n_layers, H, output_nonlin, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T,
-                   gain, whh)
-    Hs = cells.hidden_size(net["cell"])
-    # ---- the (t, unit) pairs of d_hid: one in every block of the packed state (h and c of every layer), the rest random
-    blocks = Hs // H
-    if T * Hs <= N_PAIRS:
-        pairs = [(t, u) for t in range(T) for u in range(Hs)]
-    else:
-        flat = {int(rng.integers(T)) * Hs + b * H + int(rng.integers(H)) for b in range(blocks)}
-        while len(flat) < N_PAIRS:
-            flat.add(int(rng.integers(T * Hs)))
-        pairs = [(f // Hs, f % Hs) for f in sorted(flat)]
-    return frozen(dict(name=name, ref=ref, params=params, init=init, h0=h0, net=net, Hs=Hs, pairs=tuple(pairs),
-                       g_rew=rng.normal(size=(N, T)).astype(np.float32), g_obs=rng.normal(size=(N, T + 1, ref.O)).astype(np.float32),
-                       g_act=rng.normal(size=(N, T, ref.A)).astype(np.float32), g_last=rng.normal(size=(N, ref.S + ref.H)).astype(np.float32),
-                       g_hid=rng.normal(size=(N, Hs)).astype(np.float32)))
-
-
-def phi(c, state0, offs, length, reps=1, hidden0=None, **kw):
-    """[reps N]: Phi of every lane over its first length[n] steps; the lanes are `reps` copies of the case's; hidden0 [N, H]: the initial
-    hidden state of the env (None: the one the oracle's reset leaves)"""
-    rp = lambda x: np.concatenate([x.astype(np.float64)] * reps)  # noqa: E731
-    states, hiddens, obs, rew, _, acts, ps, _ = closed_loop(c["ref"], rp(c["params"]), state0, rp(c["h0"] if hidden0 is None else hidden0),
-                                                            c["net"], offs, **kw)
-    length = np.concatenate([length] * reps)
-    k = np.arange(T + 1)[:, None]
-    n = np.arange(state0.shape[0])
-    inside = k[:T] < length[None, :]
-    out = np.where(inside, rp(c["g_rew"]).T * rew, 0.0).sum(axis=0)
-    out += np.where(inside[:, :, None], rp(c["g_act"]).transpose(1, 0, 2) * acts, 0.0).sum(axis=(0, 2))
-    out += np.where((k <= length[None, :])[:, :, None], rp(c["g_obs"]).transpose(1, 0, 2) * obs, 0.0).sum(axis=(0, 2))
-    last = np.concatenate([states[length, n], hiddens[length, n]], axis=1)
-    return out + (rp(c["g_last"]) * last).sum(axis=1) + (rp(c["g_hid"]) * ps[length, n]).sum(axis=1)
-
-
-H1, H2 = 1e-6, 1e-5
-
-
-def central(c, length, s0, offs0, d_s=None, d_offs=None, d_p0=None, hid_off=None, h0=None):
-    """central differences of Phi along one direction at both relative steps, the four perturbed rollouts in one batch of 4 N lanes; h0:
-    the env's initial hidden state (None: reset's)"""
-    mult = np.repeat([H1, -H1, H2, -H2], N)
-    st = np.concatenate([s0] * 4) + (0.0 if d_s is None else mult[:, None] * np.concatenate([d_s] * 4))
-    of = np.concatenate([offs0] * 4) + (0.0 if d_offs is None else mult[:, None, None] * np.concatenate([d_offs] * 4))
-    kw = {} if h0 is None else {"hidden0": h0}
-    if d_p0 is not None:
-        kw["p0"] = mult[:, None] * np.concatenate([d_p0] * 4)
-    if hid_off is not None:
-        kw["hid_off"] = (hid_off[0], hid_off[1], mult * hid_off[2])
-    f = phi(c, st, of, length, reps=4, **kw).reshape(4, N)
-    return (f[0] - f[1]) / (2.0 * H1), (f[2] - f[3]) / (2.0 * H2)
-
-
-def reference(c, offs0):
-    """-> (f1, f2): central differences [N, T A + S + Hs + pairs] at the two steps (action offsets step-major, initial state, initial
-    hidden state, the (t, unit) pairs of d_hid), the lane lengths, the oracle's actions [T, N, A], d_init [N, S] of the OPEN loop along
-    them, d_init [N, S] with the hidden adjoint cut, and the Elman pre-activations"""
-    ref, name, Hs = c["ref"], c["name"], c["Hs"]
-    s0 = c["init"].astype(np.float64)
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, c["h0"], c["net"], offs0)
-    length, acts, ps = lengths_of(roll[4]), roll[5], roll[6]
-    cols = []
-    for t in range(T):
-        for j in range(ref.A):
-            d = np.zeros_like(offs0)
-            d[:, t, j] = ACT_IN[name]
-            cols.append(central(c, length, s0, offs0, d_offs=d))
-    for j in range(ref.S):
-        d = np.zeros_like(s0)
-        d[:, j] = INIT_SCALE[name][j]
-        cols.append(central(c, length, s0, offs0, d_s=d))
-    for u in range(Hs):
-        d = np.zeros((N, Hs))
-        d[:, u] = 1.0
-        cols.append(central(c, length, s0, offs0, d_p0=d))
-    for t, u in c["pairs"]:
-        cols.append(central(c, length, s0, offs0, hid_off=(t, u, 1.0)))
-    f1, f2 = (np.stack([col[k] for col in cols], axis=1) for k in (0, 1))
-    open_init, cut_init = np.zeros((N, ref.S)), np.zeros((N, ref.S))
-    fixed = acts.transpose(1, 0, 2)
-    for j in range(ref.S):
-        d = np.zeros_like(s0)
-        d[:, j] = 1e-6 * INIT_SCALE[name][j]
-        open_init[:, j] = (phi(c, s0 + d, offs0, length, open_acts=fixed) - phi(c, s0 - d, offs0, length, open_acts=fixed)) / 2e-6
-        cut_init[:, j] = (phi(c, s0 + d, offs0, length, fixed_p=ps) - phi(c, s0 - d, offs0, length, fixed_p=ps)) / 2e-6
-    return f1, f2, length, acts, open_init, cut_init, roll[7]
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_reference(key):
-    c = case(key)
-    return reference(c, np.zeros((N, T, c["ref"].A)))
-
-
-@functools.lru_cache(maxsize=None)
-def hidden_reference(key, start):
-    """the ENV's hidden block of the closed loop from a start in STARTS: hidden_differences of Phi [N, H] x 2 (the policy's own initial
-    state p_0 = 0, no noise and the lane lengths are held); from hidden_start() also the first block of reference() -- action offsets and
-    initial state [N, T A + S] x 2 at the usual steps -- with the actions and Elman pre-activations; and the oracle's lane lengths"""
-    c = case(key)
-    ref, name = c["ref"], c["name"]
-    h0 = start_hidden(name, c, start)
-    offs0 = np.zeros((N, T, ref.A))
-    s0 = c["init"].astype(np.float64)
-    roll = closed_loop(ref, c["params"].astype(np.float64), s0, h0, c["net"], offs0)
-    length = lengths_of(roll[4])
-    g1, g2 = hidden_differences(name, lambda h: phi(c, s0, offs0, length, hidden0=h), h0)
-    if start == "reset":
-        return g1, g2, length, None
-    cols = []
-    for t in range(T):
-        for j in range(ref.A):
-            d = np.zeros_like(offs0)
-            d[:, t, j] = ACT_IN[name]
-            cols.append(central(c, length, s0, offs0, d_offs=d, h0=h0))
-    for j in range(ref.S):
-        d = np.zeros_like(s0)
-        d[:, j] = INIT_SCALE[name][j]
-        cols.append(central(c, length, s0, offs0, d_s=d, h0=h0))
-    f1, f2 = (np.stack([col[k] for col in cols], axis=1) for k in (0, 1))
-    return g1, g2, length, (f1, f2, roll[5], roll[7])
-
-
-def blocks_of(c):
-    """column slices: (action offsets and initial state, the hidden entries)"""
-    n1 = T * c["ref"].A + c["ref"].S
-    return slice(0, n1), slice(n1, None)
-
-
-def block_tolerance(c, want, smooth):
-    return np.concatenate([tolerance_per_lane(want[:, b], smooth[:, b]) for b in blocks_of(c)], axis=1)
-
-
-def worst_in_blocks(c, got, want, smooth):
-    return float((np.abs(got - want) / block_tolerance(c, want, smooth)).max())
-
-
-def set_rnn(e, net, noise_std=None):
-    cn = net["cell"]
-    e.set_policy_rnn(flat_params(net), cell=cn["cell"], n_layers=cn["n_layers"], hidden_size=cn["hidden"], output_nonlin=net["output_nonlin"],
-                     obs_idx=net["obs_idx"], noise_std=noise_std)
-    e.set_policy_hidden_record(cells.hidden_size(cn))
-
-
-def recorded(vs, key, splits=(T,), noise_seed=0, net=None, spec=None, cap=T, noise_std=None, hidden=None):
-    """a handle whose rows 0 .. T - 1 hold the closed-loop rollouts of the case and the hidden states before every step; hidden [N, H]:
-    the ENV's initial hidden state in place of reset's"""
-    c = case(key)
-    name = c["name"]
-    e = vs.VecSimEnv(name, N, max_steps=MAX_STEPS, **KW[name])
-
-    def policy(e):
-        if spec is None:
-            set_rnn(e, c["net"] if net is None else net, noise_std)
-        else:  # what rnn_kernel_spec made of a torch policy
-            e.set_policy_rnn(**spec)
-            e.set_policy_hidden_record(c["Hs"])
-
-    return record_mode2(e, cap, c["params"], policy, c["init"], splits, hidden=hidden, noise_seed=noise_seed)
-
-
-def cotangents(vs, key, e, with_act=True, with_hid=True):
-    c = case(key)
-    out = case_cotangents(vs, c, e)
-    if with_act:
-        out["g_act"] = vs.lanes_last(dev(c["g_act"]), e.ld)
-    if with_hid:
-        out["g_hid_last"] = vs.lanes_last(dev(c["g_hid"]), e.ld)
-    return out
 
 
 def scaled(vs, c, d_act, d_init, d_hid, d_hid0):
@@ -345,38 +65,19 @@ def scaled(vs, c, d_act, d_init, d_hid, d_hid0):
     return got.astype(np.float64)
 
 
-def check_no_unit_near_a_kink(c, pres, length):
-    """relu cells: no pre-activation of the fp64 closed loop within 1e-3 of 0 (inside the lanes' lengths); some unit of every layer alive"""
-    if c["net"]["cell"]["cell"] != "relu":
-        return
-    inside = (np.arange(T)[:, None] < length[None, :])[:, :, None]
-    for l in range(c["net"]["cell"]["n_layers"]):
-        z = np.stack([p[l] for p in pres])  # [T, N, H]
-        assert (np.where(inside, np.abs(z), 1.0) >= 1e-3).all(), (c["name"], l)
-        assert (z > 0).all(axis=(0, 1)).any(), (c["name"], l)
-
-
-def shares(c, f1, smooth, open_init, cut_init, length):
-    """shares of the full-length lanes on which a d_init without the feedback / without the hidden adjoint is off by more than 10 x the
-    tolerance"""
-    cols = slice(T * c["ref"].A, T * c["ref"].A + c["ref"].S)
-    tol = block_tolerance(c, f1, smooth)[:, cols]
-    full = length == T
-    return tuple(float((np.abs(f1[:, cols] - other) > 10.0 * tol).any(axis=1)[full].mean()) for other in (open_init, cut_init))
-
-
 def oracle_conditions(key):
     """everything the reference alone must meet (asserted before the GPU is asked) -> (c, f1, smooth, length, shares)"""
     c = case(key)
-    f1, f2, length, acts, open_init, cut_init, pres = oracle_reference(key)
-    smooth = smooth_per_lane(f1, f2)
+    r = oracle_reference(key)
+    f1, length = r.f1, r.length
+    smooth = smooth_per_lane(f1, r.f2)
     assert smooth.all(), (key, float((~smooth).mean()))  # every entry, none excluded
-    check_net_keeps_the_box(c, acts, length)
-    check_no_unit_near_a_kink(c, pres, length)
+    check_net_keeps_the_box(c, r.acts, length)
+    check_no_unit_near_a_kink(c, r.pres, length)
     assert (length[:N_EDGE] < T).any() and (length[N_EDGE:] == T).mean() > 0.9  # lanes that end early, lanes that run through
-    seen = shares(c, f1, smooth, open_init, cut_init, length)
+    seen = shares(c, f1, smooth, length, r.open_init, r.cut_init)
     assert seen[0] >= 0.5 and seen[1] >= 0.5, (key, seen)  # the test can see gpol, and it can see eta
-    return c, f1, smooth, length, seen, open_init, cut_init
+    return c, f1, smooth, length, seen, r.open_init, r.cut_init
 
 
 # --------------------------------------------------------------------------------------- 1. against the fp64 closed loop
@@ -423,7 +124,7 @@ def test_env_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, name, start)
     section 8d."""
     key = HIDDEN_CASES[name]
     c = case(key)
-    g1, g2, length, first = hidden_reference(key, start)
+    g1, g2, length = hidden_reference(key, start)
     hidden_conditions(key, g1, g2)  # from the oracle alone, before the device is asked
     hidden = hidden_start(name, c) if start == "perturbed" else None
     e = recorded(vs, key, hidden=hidden)
@@ -435,12 +136,12 @@ def test_env_hidden_adjoint_against_the_closed_loop_fp64_oracle(vs, name, start)
     assert e.error_count() == 0 and e.ld > N and not any(bool(x[..., N:].any()) for x in out)
     e.close()
     check_hidden_block(f"{key} vs_rollout_vjp_rnn from {start}", scaled_hidden(vs, c, out[1]), g1, g2)
-    if first is not None:
-        f1, f2, acts, pres = first
-        smooth = smooth_per_lane(f1, f2)
-        assert smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
-        check_net_keeps_the_box(c, acts, length)
-        check_no_unit_near_a_kink(c, pres, length)
+    if start == "perturbed":
+        r = oracle_reference(key, start)  # (from hidden_start() it is the first block alone)
+        f1, smooth = r.f1, smooth_per_lane(r.f1, r.f2)
+        assert np.array_equal(r.length, length) and smooth.all(), (key, float((~smooth).mean()))  # from the oracle alone
+        check_net_keeps_the_box(c, r.acts, length)
+        check_no_unit_near_a_kink(c, r.pres, length)
         worst = worst_of(scaled(vs, c, *out)[:, blocks_of(c)[0]], f1, smooth)
         print(f"{key} from {start}: action offsets and initial state: worst error / tolerance {worst:.4f}")
         assert worst <= 1.0, (key, worst)
@@ -460,11 +161,11 @@ def test_exploration_noise_is_an_additive_constant(vs):
     tt = e.traj_tensors(T, N)
     obs, act = tt["obs"].cpu().numpy().astype(np.float64), tt["act"].cpu().numpy().astype(np.float64)  # [T, N, .]
     hid = e.hidden_record_tensor()[:T, :, :N].permute(0, 2, 1).cpu().numpy().astype(np.float64)        # [T, N, Hs]
-    mean = cells.rnn_step(cn, obs.reshape(T * N, ref.O), hid.reshape(T * N, c["Hs"]))[0].reshape(T, N, ref.A)
+    mean = rnn_step(cn, obs.reshape(T * N, ref.O), hid.reshape(T * N, c["Hs"]))[0].reshape(T, N, ref.A)
     offs = (act - mean).transpose(1, 0, 2)
     assert 0.5 < offs[N_EDGE:].std() / (0.02 * ACT_IN[c["name"]]) < 1.5  # the noise is there
-    f1, f2, length = reference(c, np.ascontiguousarray(offs))[:3]
-    smooth = smooth_per_lane(f1, f2)
+    r = reference(c, np.ascontiguousarray(offs))
+    f1, length, smooth = r.f1, r.length, smooth_per_lane(r.f1, r.f2)
     assert smooth.all()
     assert np.array_equal(e.rollout_lengths(N, T)[0].cpu().numpy(), length)
     got = scaled(vs, c, *e.rollout_vjp_rnn(T, **cotangents(vs, key, e)))
@@ -766,33 +467,16 @@ def test_refusals_leave_the_outputs_untouched(vs):
 
 
 # ----------------------------------------------------------------------------------------------------------- 5. autograd
-ENVS = {"pend": "PendulumSim", "qcp-su": "QCartPoleSwingUpSim"}
-AUTOGRAD = {"pend": ("gru", 1, 8, 3.0, 1.0), "qcp-su": ("lstm", 1, 64, 3.0, 1.0)}
-NT, TT, GAMMA = 70, 12, 0.99
-
-
-@functools.lru_cache(maxsize=None)
 def torch_case(name):
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(37)
-    init = (rng.uniform(-1.0, 1.0, (NT, ref.S)) * np.array(INIT_SCALE[name])).astype(np.float32)
-    params = np.tile(ref.nominal_params(1).astype(np.float32).astype(np.float64), (NT, 1))
-    h0 = ref.reset(params, init.astype(np.float64), True)["hidden"]
-    cell, n_layers, H, gain, whh = AUTOGRAD[name]
-    net = make_rnn(ref, name, cell, n_layers, H, None, None, params, init.astype(np.float64), h0, rng, TT, gain, whh)
-    return dict(ref=ref, init=init, params=params, h0=h0, net=net)
+    return clc.torch_case("rnn", name)
 
 
 def oracle_loss(name, flat, s0, length=None):
-    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop, and the lane lengths"""
+    """[NT] per-lane loss -discounted return + 1e-3 sum a^2 of the fp64 closed loop under the flat parameters, and the lane lengths"""
     tc = torch_case(name)
     cn = tc["net"]["cell"]
-    net = dict(tc["net"], cell=cells.unpack_rnn(flat, cn["cell"], cn["n_layers"], cn["hidden"], tc["ref"].O, tc["ref"].A))
-    _, _, _, rew, done, acts, _, _ = closed_loop(tc["ref"], tc["params"], s0, tc["h0"], net, np.zeros((NT, TT, tc["ref"].A)))
-    length = lengths_of(done) if length is None else length
-    inside = np.arange(TT)[:, None] < length[None, :]
-    disc = GAMMA ** np.arange(TT)[:, None]
-    return -np.where(inside, disc * rew, 0.0).sum(axis=0) + 1e-3 * np.where(inside[:, :, None], acts ** 2, 0.0).sum(axis=(0, 2)), length
+    net = dict(tc["net"], cell=unpack_rnn(flat, cn["cell"], cn["n_layers"], cn["hidden"], tc["ref"].O, tc["ref"].A))
+    return clc.oracle_loss(tc, rnn_policy(net), s0, length)
 
 
 def chosen_entries(name):
@@ -847,7 +531,7 @@ def test_autograd(vs, name):
         assert smooth_per_lane(*pair).all()
     cell, n_layers, H = AUTOGRAD[name][:3]
     env = getattr(vs, ENVS[name])(max_steps=MAX_STEPS, **KW[name])
-    policy = cells.torch_policy(env.spec, cell, n_layers, H)
+    policy = torch_policy(env.spec, cell, n_layers, H)
     roll = vs.DifferentiableRecurrentRollout(env, policy)
     th0 = flat_params(tc["net"])
     which = chosen_entries(name)

@@ -3,14 +3,14 @@ vs_lin_param_grad / DifferentiablePolicyRollout(param_pass=...), the parts that 
 the refusals before any device call, the param_pass argument and the fp64 fallback decision -- and the fp64 NumPy reference of
 tests/test_gpu_lin_param_grad.py (lin_param_grad_fp64, defined here) with its error bound (error_bound).
 
-The reference is sum_rows abar (x) phi(x) with the NumPy feature stack of test_gpu_policy_vjp.features (imported, not copied); it is held
+The reference is sum_rows abar (x) phi(x) with the NumPy feature stack closed_loop_cases.features (imported, not copied); it is held
 to torch.autograd.grad of the .double() LinearPolicy at 1e-12 for every case stack.
 
-Cases: the stacks of test_gpu_policy_vjp.CASES that its oracle test runs (between them all 14 kinds, an obs_idx view, A = 2), plus
+Cases: the stacks of closed_loop_cases.LINEAR_CASES that the sweep's oracle test runs (between them all 14 kinds, an obs_idx view, A = 2), plus
   qbb-full       11 elementwise kinds x 8 rows + const + 39 MultFeat / ATan2Feat terms = 128 features: both slot halves of an action
                  row and the last extra-term slot
   qq-su-shuffled a stack given in an order that is not the kernel's slot order (const, a product, sin, identity)
-The rows of a case here are the fp64 oracle's closed loop of that case (test_gpu_policy_vjp.closed_loop: 150 lanes x 24 steps, lanes
+The rows of a case here are the fp64 oracle's closed loop of that case (closed_loop_cases.closed_loop: 150 lanes x 24 steps, lanes
 0 .. 9 ending early), rounded to float32; the GPU test runs the same stacks, weights and cotangents on the handle's own records.
 
 Cotangents: abar = (0.6 + 0.25 xi) / (N T) with xi standard normal, fixed seed -- NOT zero-mean.  With zero-mean cotangents the
@@ -34,9 +34,8 @@ from simurlacra_amd import _lib as L
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_policy_vjp as pv  # noqa: E402  (CASES, features, closed_loop, make_weights)
-from derivative_cases import KW, MAX_STEPS, N, T, draw_params_and_init, frozen, lengths_of  # noqa: E402
-from oracle import cpu_ref  # noqa: E402
+import closed_loop_cases as clc  # noqa: E402  (the linear cases, features, closed_loop)
+from derivative_cases import N, T, frozen, lengths_of  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24            # unit roundoff of fp32
@@ -56,22 +55,14 @@ EXTRA = {
     "qbb-full": ("qbb", ELEM11 + ("const",) + FULL_X, None),
     "qq-su-shuffled": ("qq-su", ("const", ("mult", (4, 5)), "sin", "identity"), None),
 }
-TABLE = list(pv.ORACLE_CASES) + ["qbb-full"]
+TABLE = list(clc.LINEAR_ORACLE_CASES) + ["qbb-full"]
 ALL_CASES = TABLE + ["qq-su-shuffled"]
 
 
 @functools.lru_cache(maxsize=None)
 def case(key):
-    """test_gpu_policy_vjp.case for its own keys; the same draws (seed 29) and the same weight rule for the stacks of EXTRA"""
-    if key in pv.CASES:
-        return pv.case(key)
-    name, terms, obs_idx = EXTRA[key]
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(29)
-    params, init = draw_params_and_init(ref, name, rng)
-    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    W = pv.make_weights(ref, name, terms, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T)
-    return frozen(dict(name=name, terms=terms, obs_idx=obs_idx, ref=ref, params=params, init=init, h0=h0, W=W))
+    """the linear sweep's case for its own keys; the same draws (seed 29) and the same weight rule for the stacks of EXTRA (no cotangents)"""
+    return clc.case(key) if key in clc.LINEAR_CASES else clc.linear_case(*EXTRA[key], cotangents=False)
 
 
 def abar_of(key, n=N, t=T, seed=0):
@@ -154,7 +145,7 @@ def lin_param_grad_fp64(terms, obs_idx, obs, abar, inside, chain=None):
     x = obs[rows].astype(np.float64)
     x = x if obs_idx is None else x[:, list(obs_idx)]
     ab = abar[rows].astype(np.float64)
-    phi = pv.features(terms, x)
+    phi = clc.features(terms, x)
     abs_sum = np.abs(ab).T @ np.abs(phi)
     out = (ab.T @ phi, abs_sum)
     return out if chain is None else out + (error_bound(terms, x, ab, abs_sum, chain),)
@@ -166,11 +157,10 @@ def oracle_rows(key):
     tests (the GPU test takes the handle's own records instead)"""
     c = case(key)
     A = c["ref"].A
-    roll = pv.closed_loop(c["ref"], c["params"].astype(np.float64), c["init"].astype(np.float64), c["h0"], c["terms"], c["obs_idx"],
-                          c["W"].astype(np.float64), np.zeros((N, T, A)))
-    length = lengths_of(roll[4])
+    roll = clc.closed_loop(c["ref"], c["params"].astype(np.float64), c["init"].astype(np.float64), c["h0"], clc.policy_of(c), np.zeros((N, T, A)))
+    length = lengths_of(roll.done)
     inside = np.arange(T)[:, None] < length[None, :]
-    obs = roll[2][:T].astype(np.float32)
+    obs = roll.obs[:T].astype(np.float32)
     return frozen(dict(obs=obs.reshape(T * N, -1), inside=inside.reshape(-1), abar=abar_of(key).transpose(1, 0, 2).reshape(T * N, A)))
 
 
@@ -237,7 +227,7 @@ def test_the_bound_resolves_a_mutated_column(key):
     g, _, bound = lin_param_grad_fp64(c["terms"], c["obs_idx"], r["obs"], r["abar"], r["inside"], chain=chain_of(ld_of(N), T))
     assert (bound >= 0.0).all() and (bound <= 1e-2 * np.abs(g).max(axis=1, keepdims=True)).all(), float((bound / np.abs(g).max(axis=1, keepdims=True)).max())
     x = r["obs"][r["inside"]].astype(np.float64)
-    phi = pv.features(c["terms"], x if c["obs_idx"] is None else x[:, list(c["obs_idx"])])
+    phi = clc.features(c["terms"], x if c["obs_idx"] is None else x[:, list(c["obs_idx"])])
     ab = r["abar"][r["inside"]].astype(np.float64)
     seen = 0
     for q in range(g.shape[1]):

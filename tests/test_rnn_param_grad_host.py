@@ -19,7 +19,7 @@ from simurlacra_amd import _lib as L
 torch = pytest.importorskip("torch")
 
 import rnn_param_grad_fp64 as ref64  # noqa: E402
-import test_rnn_vjp_host as cells  # noqa: E402  (unpack_rnn, torch_policy)
+import closed_loop_cases as cells  # noqa: E402  (unpack_rnn, torch_policy)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the table of test_gpu_rnn_param_grad: (env class, dt, cell, layers, units, output nonlinearity)

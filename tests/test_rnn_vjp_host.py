@@ -1,7 +1,7 @@
 """
 Closed-loop reverse-mode rollouts of recurrent policies, the parts that need no GPU: the C-ABI declaration, export and binding of
 vs_rollout_vjp_rnn, its NULL refusals before any device call, DifferentiableRecurrentRollout's argument validation, the NumPy fp64
-restatement of the three cells that tests/test_gpu_rnn_vjp.py uses as the policy of its oracle (held to the torch modules here), and the
+restatement of the three cells in tests/closed_loop_cases.py, the policy of the recurrent sweep's oracle (held to the torch modules here), and the
 convention of the hidden-state adjoint: row t of d_hid is the cotangent of p_{t+1}, and one batched single-step pass over the recorded
 (obs_t, p_t) with (abar_t, d_hid[t]) as grad_outputs is the parameter gradient of backpropagation through time.
 """
@@ -17,75 +17,9 @@ from simurlacra_amd import _lib as L
 
 torch = pytest.importorskip("torch")
 
+from closed_loop_cases import hidden_size, rnn_step, torch_policy, unpack_rnn  # noqa: E402  (the fp64 cells)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GATES = {"tanh": 1, "relu": 1, "gru": 3, "lstm": 4}
-
-
-# ---------------------------------------------------------------------------------------- the fp64 cells (torch's gate order)
-def sigmoid(z):
-    return 1.0 / (1.0 + np.exp(-z))
-
-
-def unpack_rnn(flat, cell, n_layers, hidden, n_in, n_act):
-    """the flat parameter vector in torch's order (weight_ih, weight_hh, bias_ih, bias_hh per layer, output weight and bias) -> a
-    dict of fp64 arrays; the dtype of flat is kept out of it"""
-    flat = np.asarray(flat, dtype=np.float64)
-    G, at, layers = GATES[cell], 0, []
-
-    def take(*shape):
-        nonlocal at
-        out = flat[at:at + int(np.prod(shape))].reshape(shape)
-        at += out.size
-        return out
-
-    for l in range(n_layers):
-        layers.append(dict(w_ih=take(G * hidden, n_in if l == 0 else hidden), w_hh=take(G * hidden, hidden), b_ih=take(G * hidden),
-                           b_hh=take(G * hidden)))
-    net = dict(cell=cell, n_layers=n_layers, hidden=hidden, layers=layers, w_out=take(n_act, hidden), b_out=take(n_act))
-    assert at == flat.size
-    return net
-
-
-def hidden_size(net):
-    return net["n_layers"] * net["hidden"] * (2 if net["cell"] == "lstm" else 1)
-
-
-def rnn_step(net, x, p, output_nonlin=None):
-    """one step of the policy: x [n, in], packed hidden p [n, Hs] (h of layer 0, 1, .., then the LSTM's c of layer 0, 1, ..) ->
-    (act [n, A], p_new [n, Hs], the pre-activations of an Elman cell [[n, H]] per layer)"""
-    H, nl, cell = net["hidden"], net["n_layers"], net["cell"]
-    hs, cs, pres = [], [], []
-    inp = x
-    for l, w in enumerate(net["layers"]):
-        h = p[:, l * H:(l + 1) * H]
-        gi = inp @ w["w_ih"].T + w["b_ih"]
-        gh = h @ w["w_hh"].T + w["b_hh"]
-        if cell in ("tanh", "relu"):
-            pres.append(gi + gh)
-            hn = np.tanh(gi + gh) if cell == "tanh" else np.maximum(gi + gh, 0.0)
-        elif cell == "gru":
-            r = sigmoid(gi[:, :H] + gh[:, :H])
-            z = sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
-            n = np.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
-            hn = (1.0 - z) * n + z * h
-        else:
-            c = p[:, (nl + l) * H:(nl + l + 1) * H]
-            s = gi + gh
-            i, f, g, o = sigmoid(s[:, :H]), sigmoid(s[:, H:2 * H]), np.tanh(s[:, 2 * H:3 * H]), sigmoid(s[:, 3 * H:])
-            cn = f * c + i * g
-            cs.append(cn)
-            hn = o * np.tanh(cn)
-        hs.append(hn)
-        inp = hn
-    y = inp @ net["w_out"].T + net["b_out"]
-    act = {None: lambda v: v, "tanh": np.tanh, "relu": lambda v: np.maximum(v, 0.0), "sigmoid": sigmoid}[output_nonlin](y)
-    return act, np.concatenate(hs + cs, axis=1), pres
-
-
-def torch_policy(spec, cell, n_layers, hidden, output_nonlin=None):
-    if cell in ("tanh", "relu"):
-        return vs.RNNPolicy(spec, hidden, n_layers, hidden_nonlin=cell, output_nonlin=output_nonlin)
-    return (vs.GRUPolicy if cell == "gru" else vs.LSTMPolicy)(spec, hidden, n_layers, output_nonlin=output_nonlin)
 
 
 @pytest.mark.parametrize("cell,n_layers,hidden,out", [("tanh", 1, 1, None), ("relu", 2, 3, None), ("gru", 1, 5, None),
