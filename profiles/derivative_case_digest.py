@@ -4,7 +4,7 @@ references, to compare two versions of tests/ bit for bit.  No device is needed:
     python profiles/derivative_case_digest.py --tree OLD_TREE > old.txt
     python profiles/derivative_case_digest.py --tree . > new.txt  &&  diff old.txt new.txt
 
---tree: the checkout whose tests/ and oracle/ are imported (default: this one).  --only MODULE ...: a subset of the eight modules.
+--tree: the checkout whose tests/ and oracle/ are imported (default: this one).  --only MODULE ...: a subset of MODULES.
 Per module: a line per case(key) / oracle_case(name) with the digest over every array in it; a line per oracle_reference(...) with the
 digest over every output (lane lengths included) and over the smooth mask; and the (bad share, worst error / tolerance) pairs of the
 module's rule, repr'd floats, for got = the reference itself and for a seeded perturbed copy.  A rule is looked up under its name from
@@ -19,17 +19,27 @@ forms of a reference into one).  Beyond case and oracle_reference they get a lin
 hidden_start() with its actions and pre-activations -- oracle_reference(key, "perturbed"), or what the recurrent module's
 hidden_reference returned next to the hidden block.  test_lin_param_grad_host: a line per case(key), its rows and its fp64
 reference with the bound.
+
+The parameter-gradient lines (PARAM_GRAD) keep the name of the test module they were first printed under, and home_of() reads every
+object from the first module of the tree that has it: the reference modules fnn_param_grad_fp64, lin_param_grad_fp64,
+rnn_param_grad_fp64 and param_grad_cases, or the test modules that held them before.  test_fnn_param_grad_host: per TABLE key the
+seeded random_net and param_grad_fp64 with its bound on the host test's own rows.  test_gpu_rnn_param_grad: case(key) of CASES and
+ELMAN_AS_FNN.  test_rnn_param_grad_host: rows_case(key) and its reference with the bound.  param_grad_grids: the three launch grid
+rules and the linear pass's chain_of at the (ld, t_steps) pairs of the host test, for 256 and 304 compute units (the rules that used
+to ask torch for the device's count are given a stand-in).
 """
 import argparse
 import hashlib
 import importlib
 import os
 import sys
+import types
 
 import numpy as np
 
 MODULES = ("test_gpu_rollout_vjp", "test_gpu_rollout_vjp_params", "test_gpu_trajectory_grad", "test_gpu_policy_vjp", "test_gpu_fnn_vjp",
-           "test_gpu_rnn_vjp", "test_gpu_fnn_param_grad", "test_lin_param_grad_host")
+           "test_gpu_rnn_vjp", "test_gpu_fnn_param_grad", "test_lin_param_grad_host", "test_fnn_param_grad_host", "test_gpu_rnn_param_grad",
+           "test_rnn_param_grad_host", "param_grad_grids")
 SWEEPS = {"test_gpu_policy_vjp": "LINEAR", "test_gpu_fnn_vjp": "FNN", "test_gpu_rnn_vjp": "RNN"}
 GLOBAL = ("test_gpu_rollout_vjp_params", "test_gpu_trajectory_grad")  # one unit per family; the others: one unit per lane
 
@@ -105,13 +115,107 @@ def sweep(mod, m):
                 verdicts(m, mod, f"{key} {start}", f1, f2)
 
 
-def param_grad_host(mod, m):
+def home_of(name, *mods):
+    """the first of the tree's modules `mods` that has `name`"""
+    for mod in mods:
+        try:
+            m = importlib.import_module(mod)
+        except ImportError:
+            continue
+        if hasattr(m, name):
+            assert os.path.abspath(m.__file__).startswith(sys.path[0]), m.__file__
+            return m
+    raise LookupError(name)
+
+
+def fnn_abar(mod):  # the cases are test_gpu_fnn_vjp's; the pass's own input is abar
+    m = home_of("abar_of", "fnn_param_grad_fp64", "test_gpu_fnn_param_grad")
+    dc = importlib.import_module("derivative_cases")
+    for key in getattr(m, "GPU_TABLE", m.TABLE):  # (the GPU test's own TABLE was that list)
+        line(mod, key, "abar", sha(m.abar_of(key, dc.N, dc.T)))
+
+
+def lin_host(mod):
+    m = home_of("lin_param_grad_fp64", "lin_param_grad_fp64", "test_lin_param_grad_host")
+    chain_of = home_of("chain_of", "param_grad_cases", "test_lin_param_grad_host").chain_of
+    dc = importlib.import_module("derivative_cases")
     for key in m.ALL_CASES:
         c, r = m.case(key), m.oracle_rows(key)
         line(mod, key, "case", sha(c))
         line(mod, key, "oracle_rows", sha(r))
-        ref = m.lin_param_grad_fp64(c["terms"], c["obs_idx"], r["obs"], r["abar"], r["inside"], chain=m.chain_of(m.ld_of(m.N), m.T))
+        ref = m.lin_param_grad_fp64(c["terms"], c["obs_idx"], r["obs"], r["abar"], r["inside"], chain=chain_of(m.ld_of(dc.N), dc.T))
         line(mod, key, "lin_param_grad_fp64", sha(list(ref)))
+
+
+def fnn_host(mod):
+    """the rows of test_the_fp64_reference_is_torch_autograd_of_the_double_module, drawn as that test draws them"""
+    m = home_of("param_grad_fp64", "fnn_param_grad_fp64", "test_fnn_param_grad_host")
+    dc = importlib.import_module("derivative_cases")
+    for key in sorted(m.TABLE):
+        name = m.TABLE[key][0]
+        ref = dc.cpu_ref.make_ref(name, max_steps=dc.MAX_STEPS, **dc.KW[name])
+        rng = np.random.default_rng(sorted(m.TABLE).index(key))
+        net = m.random_net(key, rng, ref.O, ref.A)
+        line(mod, key, "random_net", sha(net))
+        obs = rng.normal(size=(300, ref.O)).astype(np.float32)
+        abar = rng.normal(size=(300, ref.A)).astype(np.float32)
+        inside = rng.uniform(size=300) < 0.8
+        line(mod, key, "param_grad_fp64", sha(list(m.param_grad_fp64(net, obs, abar, inside, chains=dict(acc=64, wg=8)))))
+
+
+def rnn_cases(mod):
+    m = home_of("ELMAN_AS_FNN", "param_grad_cases", "test_gpu_rnn_param_grad")
+    for key in {**m.CASES, **m.ELMAN_AS_FNN}:
+        line(mod, key, "case", sha(m.case(key)))
+
+
+def rnn_host(mod):
+    m = home_of("rows_case", "rnn_param_grad_fp64", "test_rnn_param_grad_host")
+    ref64 = importlib.import_module("rnn_param_grad_fp64")
+    for key in m.TABLE:
+        _, net, x, p, abar, d_hid, inside, out = m.rows_case(key)
+        line(mod, key, "rows_case", sha([net, x, p, abar, d_hid, inside, out]))
+        line(mod, key, "param_grad_fp64", sha(list(ref64.param_grad_fp64(net, x, p, abar, d_hid, inside, out))))
+
+
+GRID_PAIRS = ((256, 24), (256, 1), (2304, 40), (3328, 41), (128, 12), (128, 7), (1792, 41), (1536, 41))
+
+
+def grid_rule(kind, n_cu):
+    """(ld, t_steps) -> (n_wg, rows) of one family's rule, from either home"""
+    try:
+        rule = getattr(home_of(kind + "_grid_of", "param_grad_cases"), kind + "_grid_of")
+        return lambda ld, t: rule(ld, t, n_cu)
+    except LookupError:
+        if kind == "lin":
+            return lambda ld, t: importlib.import_module("test_lin_param_grad_host").grid_of(ld, t, n_cu)
+    m = importlib.import_module(f"test_gpu_{kind}_param_grad")
+    import torch
+
+    def asked(ld, t):  # the rule asks torch for the device's compute units
+        real = torch.cuda.get_device_properties
+        torch.cuda.get_device_properties = lambda *a: types.SimpleNamespace(multi_processor_count=n_cu)
+        try:
+            return m.grid_of(ld, t)
+        finally:
+            torch.cuda.get_device_properties = real
+
+    return asked
+
+
+def grids(mod):
+    chain_of = home_of("chain_of", "param_grad_cases", "test_lin_param_grad_host").chain_of
+    for n_cu in (256, 304):
+        for kind in ("fnn", "rnn", "lin"):
+            rule = grid_rule(kind, n_cu)
+            for ld, t in GRID_PAIRS:
+                line(mod, kind, n_cu, ld, t, "grid", *map(int, rule(ld, t)))
+        for ld, t in GRID_PAIRS:
+            line(mod, "lin", n_cu, ld, t, "chain_of", int(chain_of(ld, t, n_cu)), int(chain_of(ld, t, n_cu, 1)))
+
+
+PARAM_GRAD = {"test_gpu_fnn_param_grad": fnn_abar, "test_lin_param_grad_host": lin_host, "test_fnn_param_grad_host": fnn_host,
+              "test_gpu_rnn_param_grad": rnn_cases, "test_rnn_param_grad_host": rnn_host, "param_grad_grids": grids}
 
 
 def main():
@@ -122,15 +226,13 @@ def main():
     tree = os.path.abspath(args.tree)
     sys.path[:0] = [os.path.join(tree, "tests"), tree]
     for mod in args.only:
+        if mod in PARAM_GRAD:
+            PARAM_GRAD[mod](mod)
+            continue
         m = importlib.import_module(mod)
         assert os.path.abspath(m.__file__).startswith(tree), m.__file__
         if mod in SWEEPS:
             sweep(mod, m)
-        elif mod == "test_lin_param_grad_host":
-            param_grad_host(mod, m)
-        elif mod == "test_gpu_fnn_param_grad":  # its cases are test_gpu_fnn_vjp's; its own input is abar
-            for key in m.TABLE:
-                line(mod, key, "abar", sha(m.abar_of(key, m.N, m.T)))
         elif mod == "test_gpu_trajectory_grad":
             for name in m.FAMILIES:
                 c = m.oracle_case(name)

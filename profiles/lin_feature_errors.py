@@ -1,7 +1,7 @@
 """Worst absolute error of the two feature functions of the linear policy for which the project states no figure -- the bell
 exp2f(-0.72134752 (v v)) and the device library's atan2f -- against fp64, over the observations of the derivative test cases.
 
-Per case of tests/test_lin_param_grad_host.TABLE the states of its recorded closed-loop rollout (150 lanes x 24 rows) become the
+Per case of tests/lin_param_grad_fp64.TABLE the states of its recorded closed-loop rollout (150 lanes x 24 rows) become the
 initial states of ONE handle of 3 600 lanes; a recording step_policy(1) with a single-feature linear policy of weight 1 then leaves
 that feature of every lane's observation in the record's raw action, as k_rollout_lin evaluates it (fmaf(1, phi, 0) = phi exactly):
 the bell of observation row k through obs_idx = (k,), atan2 of every ordered pair of rows.  k_lin_param_grad evaluates the same
@@ -19,8 +19,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import simurlacra_amd as vs  # noqa: E402
-import test_gpu_lin_param_grad as gt  # noqa: E402
-import test_lin_param_grad_host as host  # noqa: E402
+import param_grad_cases as pgc  # noqa: E402
+import lin_param_grad_fp64 as host  # noqa: E402
 from derivative_cases import KW, MAX_STEPS, N, T  # noqa: E402
 
 
@@ -31,7 +31,7 @@ def main():
     for key in host.TABLE:
         c = host.case(key)
         name, O, A = c["name"], c["ref"].O, c["ref"].A
-        e = gt.recorded(vs, key)
+        e = pgc.recorded(vs, c, lambda e: e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"]))
         states = e.traj_tensors(T, N)["state"].cpu().numpy().reshape(T * N, -1)
         e.close()
         n = states.shape[0]

@@ -1,6 +1,6 @@
 """
 What the GPU tests of the derivative kernels share (test_gpu_rollout_vjp*, test_gpu_trajectory_grad, test_gpu_policy_vjp, test_gpu_fnn_vjp,
-test_gpu_rnn_vjp, test_gpu_fnn_param_grad, test_gpu_param_derivatives_all): the families' tables and shapes, the edge lanes, the fp64
+test_gpu_rnn_vjp, test_gpu_param_derivatives_all, and through param_grad_cases.py the three parameter-gradient tests): the families' tables and shapes, the edge lanes, the fp64
 open-loop rollout, the all-parameter oracle, the mode-2 recording launch loop, the playback cotangents and the project's tolerance.
 Not a test module: import it by bare name.
 

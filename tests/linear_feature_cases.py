@@ -23,14 +23,14 @@ Exclusions: exactly one -- the atan2 DERIVATIVE at the four (+-0, +-0) pairs (0 
 masked 0 there, by version); excluded() names them and the tests count them.  No other entry is left out and no share of bad entries
 is allowed.
 
-Bounds.  Values: test_lin_param_grad_host.feature_errors as it stands for identity, sign, abs, squared, cubic, sig, sin, cos, sinsin,
+Bounds.  Values: lin_param_grad_fp64.feature_errors as it stands for identity, sign, abs, squared, cubic, sig, sin, cos, sinsin,
 sincos, mult and const; the bell and atan2 from the figures measured on THIS grid (below).  Derivatives: derivative_errors, derived in
 its docstring.  Both get one term feature_errors does not have: a result below the normal range is rounded to a subnormal or flushed,
 either way an absolute error of at most TINY = 2^-126 per operation (squared(1e-30) = 1e-60 is 0 in fp32 in either mode); it is added to
 every bound that is not 0, and is 1.2e-38.
 
 The three figures the project does not state: worst |device - fp64| over this grid on the MI355X, library
-version MEASURED["library"]; the bounds use TWICE each (the margin EPS_BELL and EPS_ATAN2 of test_lin_param_grad_host were given: one
+version MEASURED["library"]; the bounds use TWICE each (the margin EPS_BELL and EPS_ATAN2 of lin_param_grad_fp64 were given: one
 measurement on a finite grid).
   bell    exp2f(-0.72134752 (v v)): BELL_ABS absolute, BELL_ULPS in ulps of |reference|.  The bound is the absolute figure: in the tail the
           rounding of the exponent's argument alone is |arg| u ln 2 relative (hundreds of ulps at |v| = 13), so the ulps figure is a
@@ -43,7 +43,7 @@ measurement on a finite grid).
 import numpy as np
 
 from closed_loop_cases import features  # (the fp64 values)
-import test_lin_param_grad_host as host  # (feature_errors, U, EPS_SIG, EPS_SINCOS, EXTRA)
+import lin_param_grad_fp64 as host  # (feature_errors, U, EPS_SIG, EPS_SINCOS, EXTRA)
 
 U, EPS_SIG, EPS_SINCOS = host.U, host.EPS_SIG, host.EPS_SINCOS
 TINY = 2.0 ** -126

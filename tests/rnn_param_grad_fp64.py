@@ -1,5 +1,6 @@
 """
-The fp64 reference of vs_rnn_param_grad and its first-order error bound.  Not a test module: import it by bare name.
+The fp64 reference of vs_rnn_param_grad and its first-order error bound, and the synthetic rows the host test and the digest tool run
+it on (TABLE, ROWS, rows_case).  Not a test module: import it by bare name.
 
 param_grad_fp64 restates in NumPy fp64
     d_params[q] = sum over the rows (t < L_i, i < n) of (d F / d theta_q)(x_t, p_t)^T (abar_t, d_hid_t)
@@ -202,6 +203,41 @@ def param_grad_fp64(net, x, p, abar, d_hid, inside, output_nonlin=None, chains=N
     return cat(grads, 0), cat(mags, 1), cat(bounds, 2), dict(zmax=zmax, kink=kink)
 
 
-def worst_ratio(err, bound):
-    """max err / bound; an entry whose bound is 0 (every term of it is 0) must be met exactly"""
-    return float(np.where(bound > 0.0, err / np.where(bound > 0.0, bound, 1.0), np.where(err == 0.0, 0.0, np.inf)).max())
+# ------------------------------------------------------------------------------------------------- the host test's rows
+# Synthetic rows (normal inputs, hidden states, cotangents; every fourth row is outside) for the cells of test_gpu_rnn_param_grad's
+# table: (env class, dt, cell, layers, units, output nonlinearity)
+TABLE = {
+    "omo-tanh-3": ("OneMassOscillatorSim", 0.02, "tanh", 1, 3, None),
+    "pend-relu-8": ("PendulumSim", 0.01, "relu", 1, 8, None),
+    "pend-gru-8": ("PendulumSim", 0.01, "gru", 1, 8, None),
+    "qq-su-gru-2x64": ("QQubeSwingUpSim", 0.004, "gru", 2, 64, None),
+    "qcp-su-lstm-64": ("QCartPoleSwingUpSim", 0.002, "lstm", 1, 64, None),
+    "qbb-lstm-2x33-tanh-out": ("QBallBalancerSim", 0.01, "lstm", 2, 33, "tanh"),
+    "bob-gru-63": ("BallOnBeamSim", 0.01, "gru", 1, 63, None),
+}
+ROWS = 240
+
+
+def rows_case(key):
+    """(torch fp64 policy, unpacked fp64 net, x, p, abar, d_hid, inside, output nonlinearity's name)"""
+    import torch
+
+    import closed_loop_cases as cells
+    import simurlacra_amd as vs
+
+    env_cls, dt, cell, nl, H, out = TABLE[key]
+    env = getattr(vs, env_cls)(dt=dt, max_steps=30)
+    O, A = env.obs_space.flat_dim, env.act_space.flat_dim
+    torch.manual_seed(11)
+    policy = cells.torch_policy(env.spec, cell, nl, H, {None: None, "tanh": torch.tanh}[out])
+    with torch.no_grad():  # float32 values, so that the host test's float32 pass runs on the very same parameters
+        flat = policy.param_values.detach().float()
+    policy = policy.double()
+    policy.param_values = flat.double()
+    net = cells.unpack_rnn(flat.numpy(), cell, nl, H, O, A)
+    rng = np.random.default_rng(17)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+    x, p = f32(rng.normal(size=(ROWS, O))), f32(0.5 * rng.normal(size=(ROWS, policy.hidden_size)))
+    abar, d_hid = f32(rng.normal(size=(ROWS, A))), f32(rng.normal(size=(ROWS, policy.hidden_size)))
+    inside = np.arange(ROWS) % 4 != 3
+    return policy, net, x, p, abar, d_hid, inside, out

@@ -3,16 +3,18 @@ vs_lin_param_grad / k_lin_param_grad (+ k_fnn_param_reduce): the weight gradient
 rows of a handle, VecSimEnv.lin_param_grad and DifferentiablePolicyRollout(param_pass="kernel").
 
 Shapes, stacks, weights and seeds are those of test_gpu_policy_vjp.py (closed_loop_cases.py; 150 lanes = 64 + 64 + 22, T = 24, +-5 % per-lane parameters,
-lanes 0 .. 9 end early) plus the two stacks of test_lin_param_grad_host.EXTRA (all 128 features; a stack in a non-slot order).  abar is
-dense, fed directly, and not zero-mean (test_lin_param_grad_host's docstring says why).
+lanes 0 .. 9 end early) plus the two stacks of lin_param_grad_fp64.EXTRA (all 128 features; a stack in a non-slot order).  abar is
+dense, fed directly, and not zero-mean (lin_param_grad_fp64's docstring says why).
 
-Reference: test_lin_param_grad_host.lin_param_grad_fp64 -- sum_rows abar (x) phi(x) in fp64 over the RECORDED observations and
-lengths, with the NumPy feature stack of closed_loop_cases (held to torch.autograd.grad of the .double() LinearPolicy at 1e-12 in
-that file, without a device).  Tolerance, per parameter: test_lin_param_grad_host.error_bound, derived in its docstring,
+Reference: lin_param_grad_fp64.lin_param_grad_fp64 -- sum_rows abar (x) phi(x) in fp64 over the RECORDED observations and
+lengths, with the NumPy feature stack of closed_loop_cases (held to torch.autograd.grad of the .double() LinearPolicy at 1e-12 by
+test_lin_param_grad_host, without a device).  Tolerance, per parameter: lin_param_grad_fp64.error_bound, derived in its docstring,
     bound = sum_rows |abar| e(phi_q) + gamma(chain) sum_rows |abar phi_q|,
-the chain read off the launch's grid rule (grid_of / chain_of there, mirrored from the documented rule with the device's compute-unit
-count).  The kernel is held to the fp64 reference within the bound.  The bound is not tuned to the kernel: the worst measured ratio
-per case is printed (-s) and recorded in DESIGN.md 8n.
+the chain read off the launch's grid rule (param_grad_cases.lin_grid_of / chain_of, mirrored from the documented rule with the
+device's compute-unit count).  The kernel is held to the fp64 reference within the bound.  The bound is not tuned to the kernel: the
+worst measured ratio per case is printed (-s) and recorded in DESIGN.md 8n.
+
+The checks that the three parameter-gradient passes share are bodies in param_grad_cases.py; the tests here hand them this family.
 
 Which assertion catches which kernel mistake:
   * a missing L select / mask          test_nan_behind_the_rows_changes_no_bit, and every table case (lanes 0 .. 9 end early)
@@ -21,8 +23,6 @@ Which assertion catches which kernel mistake:
   * a stale LDS row between tiles      test_runs_of_two_tiles (lengths change inside a run), test_small_batches
   * a nondeterministic reduction       test_two_calls_and_accumulate_are_exact, the autograd test's backward-twice assertion
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -31,56 +31,33 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import closed_loop_cases as clc  # noqa: E402  (features, torch_case, the autograd shapes; a network for the policy-switch tests)
-import test_lin_param_grad_host as host  # noqa: E402  (cases, the fp64 reference and its error bound)
-from derivative_cases import ACT_IN, KW, MAX_STEPS, N, N_EDGE, STATE_BUFFERS, T, dev, record_mode2  # noqa: E402
+import lin_param_grad_fp64 as host  # noqa: E402  (cases, the fp64 reference and its error bound)
+import param_grad_cases as pgc  # noqa: E402
+from derivative_cases import ACT_IN, KW, MAX_STEPS, N, N_EDGE, T, dev, record_mode2  # noqa: E402
+from param_grad_cases import LIN, n_cu, vs, worst_ratio  # noqa: E402,F401  (vs: the fixture)
 
 
-@pytest.fixture(scope="module")
-def vs():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import simurlacra_amd
-
-    return simurlacra_amd
+def set_linear(e, c, noise_std=None):
+    e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
 
 
-def n_cu():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def recorded(vs, key, n=N, t=T, lanes=None, noise_std=None, noise_seed=0, cap=None):
-    """a handle whose rows 0 .. t - 1 hold the closed-loop rollouts of the case (lane k repeats lane k % N, or the case's `lanes`)"""
+def recorded(vs, key, noise_std=None, **kw):
+    """param_grad_cases.recorded of the case under its linear policy"""
     c = host.case(key)
-    name = c["name"]
-    pick = (lambda x: np.resize(x, (n,) + x.shape[1:])) if lanes is None else (lambda x: np.resize(x[lanes], (n,) + x.shape[1:]))
-    e = vs.VecSimEnv(name, n, max_steps=MAX_STEPS, **KW[name])
-
-    def linear(e):
-        e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]), obs_idx=c["obs_idx"], noise_std=noise_std)
-
-    return record_mode2(e, t if cap is None else cap, pick(c["params"]), linear, pick(c["init"]), (t,), noise_seed=noise_seed)
+    return pgc.recorded(vs, c, lambda e: set_linear(e, c, noise_std), **kw)
 
 
-def rows_of(e, n, t):
-    """(obs [t n, O], inside [t n], lengths [n]) of the handle's records, step-major"""
-    obs = e.traj_tensors(t, n)["obs"].cpu().numpy()  # [t, n, O]
-    length = e.rollout_lengths(n, t)[0].cpu().numpy()
-    inside = np.arange(t)[:, None] < length[None, :]
-    return obs.reshape(t * n, -1), inside.reshape(-1), length
+def on_device(vs, e, key):
+    return vs.lanes_last(dev(host.abar_of(key)), e.ld)
 
 
-def reference(e, key, n, t, abar, more_adds=0):
+def reference(e, key, n, t, abar):
     """(fp64 gradient, bound) [A, F] for the handle's records and abar [n, t, A]"""
     c = host.case(key)
-    obs, inside, _ = rows_of(e, n, t)
+    obs, inside, _ = pgc.rows_of(e, n, t)
     want, _, bound = host.lin_param_grad_fp64(c["terms"], c["obs_idx"], obs, abar.transpose(1, 0, 2).reshape(t * n, -1), inside,
-                                              chain=host.chain_of(e.ld, t, n_cu(), more_adds))
+                                              chain=pgc.chain_of(e.ld, t, n_cu()))
     return want, bound
-
-
-def worst_ratio(err, bound):
-    """max err / bound; an entry whose bound is 0 (every term of it is 0) must be met exactly"""
-    return float(np.where(bound > 0.0, err / np.where(bound > 0.0, bound, 1.0), np.where(err == 0.0, 0.0, np.inf)).max())
 
 
 def held(vs, e, key, n, t, abar, what):
@@ -176,7 +153,7 @@ def test_runs_of_two_tiles(vs):
     lane group 24 holds one lane and groups 25 .. 27 none."""
     key, n, t = "qbb", 1537, 41
     e = recorded(vs, key, n=n, t=t)
-    n_wg, acc = host.grid_of(e.ld, t, n_cu())
+    n_wg, acc = pgc.lin_grid_of(e.ld, t, n_cu())
     if n_cu() == 256:
         assert e.ld == 1792 and (e.ld // 64) * t > n_wg and acc == 128 and t % 2 == 1
     held(vs, e, key, n, t, host.abar_of(key, n, t), f"{key} n={n} T={t}")
@@ -186,9 +163,7 @@ def test_runs_of_two_tiles(vs):
 def test_zero_adjoints_give_zeros(vs):
     key = "qcp-su"
     e = recorded(vs, key)
-    out = torch.full((e._lin_n_params,), 7.0, device="cuda")
-    assert e.lin_param_grad(T, torch.zeros(T, host.case(key)["ref"].A, e.ld, device="cuda"), out=out) is out
-    assert not out.any()
+    pgc.check_zero_adjoints_give_zeros(e, LIN, T, [host.case(key)["ref"].A])
     e.close()
 
 
@@ -197,61 +172,23 @@ def test_zero_adjoints_give_zeros(vs):
 def test_nan_behind_the_rows_changes_no_bit(vs, key):
     """NaN in abar at every row t >= L, at lanes n .. ld - 1 and in rows t_steps .. of a larger buffer: the same bits as with zeros there"""
     e = recorded(vs, key)
-    A = host.case(key)["ref"].A
-    length = e.rollout_lengths(N, T)[0]
-    assert e.ld > N and bool((length < T).any())
-    big = torch.zeros(T + 5, A, e.ld, device="cuda")
-    big[:T, :, :N] = vs.lanes_last(dev(host.abar_of(key)), e.ld)[:, :, :N]
-    behind = torch.arange(T, device="cuda")[:, None] >= length[None, :]          # [T, N]
-    big[:T, :, :N] = torch.where(behind[:, None, :], torch.zeros((), device="cuda"), big[:T, :, :N])
-    clean = e.lin_param_grad(T, big[:T])
-    dirty = big.clone()
-    dirty[:T, :, :N] = torch.where(behind[:, None, :], torch.full((), float("nan"), device="cuda"), dirty[:T, :, :N])
-    dirty[:, :, N:] = float("nan")
-    dirty[T:] = float("nan")
-    assert bool(torch.isnan(dirty[:T, :, :N]).any())
-    got = e.lin_param_grad(T, dirty[:T])
-    assert bool(clean.any()) and bool(torch.isfinite(got).all()) and torch.equal(got, clean)
+    pgc.check_nan_behind_the_rows(e, LIN, N, T, [on_device(vs, e, key)])
     e.close()
 
 
 def test_two_calls_and_accumulate_are_exact(vs):
     key = "qbb-full"
     e = recorded(vs, key)
-    ab = vs.lanes_last(dev(host.abar_of(key)), e.ld)
-    g = e.lin_param_grad(T, ab)
-    assert torch.equal(e.lin_param_grad(T, ab), g) and bool(g.any())
-    twice = e.lin_param_grad(T, ab)
-    e.lin_param_grad(T, ab, out=twice, accumulate=True)
-    assert torch.equal(twice, 2.0 * g)
-    r = torch.randn(g.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(3))
-    out = r.clone()
-    e.lin_param_grad(T, ab, out=out, accumulate=True)
-    assert torch.equal(out, r + g)
-    with pytest.raises(vs.ValueErr):
-        e.lin_param_grad(T, ab, accumulate=True)
-    with pytest.raises(vs.ShapeErr):
-        e.lin_param_grad(T, ab[:, :, :64].contiguous())
+    ab = on_device(vs, e, key)
+    pgc.check_two_calls_and_accumulate(vs, e, LIN, T, [ab], [ab[:, :, :64].contiguous()], dense=False)
     e.close()
 
 
 def test_the_handle_is_untouched_and_goes_on_serving(vs):
-    L = vs._lib
     key = "qq-su"
     e = recorded(vs, key)
     cot = clc.cotangents(vs, key, e)
-    da0, di0 = e.rollout_vjp_policy(T, **cot)
-    before = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
-    planes, words = e.traj_planes()
-    rows = [p.clone() for p, _ in planes] + [words.clone()]
-    g = e.lin_param_grad(T, da0)  # straight on the sweep's d_act
-    assert bool(torch.isfinite(g).all()) and bool(g.any())
-    for b, x in zip(STATE_BUFFERS, before):
-        assert np.array_equal(e.get(getattr(L, b)), x), b
-    planes, words = e.traj_planes()
-    assert all(torch.equal(a, b) for a, b in zip([p for p, _ in planes] + [words], rows)) and e.error_count() == 0
-    da1, di1 = e.rollout_vjp_policy(T, **cot)
-    assert torch.equal(da1, da0) and torch.equal(di1, di0)
+    pgc.check_the_handle_is_untouched(vs, e, LIN, T, lambda: e.rollout_vjp_policy(T, **cot))  # straight on the sweep's d_act
     e.close()
 
 
@@ -268,7 +205,7 @@ def test_one_workspace_serves_linear_fnn_linear_in_turn(vs):
         return torch.randn(t, A, e.ld, device="cuda", generator=torch.Generator("cuda").manual_seed(seed))
 
     def linear(e, t, seed):
-        record_mode2(e, long, params, lambda e: e.set_policy_linear(lc["W"].reshape(-1), list(lc["terms"]), obs_idx=lc["obs_idx"]), init, (t,))
+        record_mode2(e, long, params, lambda e: set_linear(e, lc), init, (t,))
         return e.lin_param_grad(t, dense(e, t, seed))
 
     def network(e, t, seed):
@@ -290,120 +227,44 @@ def test_one_workspace_serves_linear_fnn_linear_in_turn(vs):
 
 # ------------------------------------------------------------------------------------------------------- 5. refusals
 def test_refusals_leave_the_output_untouched(vs):
-    L = vs._lib
-    lib = L.load()
     key = "qq-su"
     c = host.case(key)
-    d = vs.env_dims(c["name"])
     e = recorded(vs, key)
-    n_params = e._lin_n_params
-    assert n_params == c["W"].size
-    abar = vs.lanes_last(dev(host.abar_of(key)), e.ld)
-    out = torch.full((n_params + 1,), 7.0, device="cuda")
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-
-    def call(handle, t_steps=T, ab=abar, dp=out, n=None):
-        rc = lib.vs_lin_param_grad(handle._h if handle is not None else None, t_steps, ptr(ab), ptr(dp), n_params if n is None else n, 0)
-        torch.cuda.synchronize()
-        return rc
-
-    def refused(code, handle, **kw):
-        assert call(handle, **kw) == code
-        assert bool((out == 7.0).all())  # the sentinels
-        if handle is not None:
-            assert "vs_lin_param_grad" in lib.vs_last_error(handle._h).decode()
-
-    def served():
-        assert call(e) == L.VS_OK and not bool((out[:n_params] == 7.0).any()) and float(out[n_params]) == 7.0
-        out.fill_(7.0)
-
-    def linear():
-        e.set_policy_linear(c["W"].reshape(-1), list(c["terms"]))
-
-    refused(L.VS_ERR_ARG, None)
-    refused(L.VS_ERR_ARG, e, ab=None)
-    refused(L.VS_ERR_ARG, e, dp=None)
-    for t_steps in (0, -3, T + 1):
-        refused(L.VS_ERR_ARG, e, t_steps=t_steps)
-    for n in (n_params - 1, n_params + 1):
-        refused(L.VS_ERR_ARG, e, n=n)
-    e.set_traj_offset(3)
-    refused(L.VS_ERR_STATE, e)
-    e.set_traj_offset(0)
-    e.set_auto_reset(True)
-    refused(L.VS_ERR_STATE, e)
-    e.set_auto_reset(False)
-    e.set_policy_population(np.tile(c["W"].reshape(1, -1), (3, 1)), lane_set=np.arange(N) // 64)
-    refused(L.VS_ERR_STATE, e)
-    e.set_policy_population(None)
-    served()
-    e.set_policy_linear(None, None)                             # no policy
-    refused(L.VS_ERR_STATE, e)
+    r = pgc.Refusals(vs, e, LIN, T, [on_device(vs, e, key)])
+    assert r.n_params == c["W"].size
+    r.arguments()
+    r.policies(vs.env_dims(c["name"]), c["W"], lambda: e.set_policy_linear(None, None),
+               lambda: e.set_policy_linear(c["W"].reshape(-1), list(c["terms"])), dict(fnn={}, gru={}, playback={}))
+    e.set_policy_linear(None, None)
     with pytest.raises(vs.ValueErr, match="set_policy_linear"):  # the Python face
-        e.lin_param_grad(T, abar)
-    n_fnn = (d["O"] + 1) * 8 + (8 + 1) * d["A"]
-    e.set_policy_fnn(np.zeros(n_fnn, dtype=np.float32), [8])    # an FNN policy
-    refused(L.VS_ERR_STATE, e)
-    n_gru = 3 * 8 * (d["O"] + 8 + 2) + (8 + 1) * d["A"]
-    e.set_policy_rnn(np.zeros(n_gru, dtype=np.float32), cell="gru", n_layers=1, hidden_size=8)
-    refused(L.VS_ERR_STATE, e)
-    e.set_policy_playback(np.zeros((N, T, d["A"]), dtype=np.float32))
-    refused(L.VS_ERR_STATE, e)
-    linear()
-    served()
-    e.set_record_mode(1)
-    e.set_traj_capacity(T)
-    refused(L.VS_ERR_STATE, e)
-    e.set_record_mode(2)
-    e.set_traj_capacity(T)
-    served()                                                    # after the refusals the same handle serves a good call
-    assert e.error_count() == 0
+        e.lin_param_grad(T, r.bufs[0])
     e.close()
-    disc = vs.VecSimEnv("bob-d", 64, dt=0.01, max_steps=MAX_STEPS)
-    disc.set_record_mode(2)
-    disc.set_traj_capacity(T)
-    ab = torch.zeros(T, 1, disc.ld, device="cuda")
-    assert lib.vs_lin_param_grad(disc._h, T, ptr(ab), ptr(out), n_params, 0) == L.VS_ERR_STATE
-    torch.cuda.synchronize()
-    assert bool((out == 7.0).all()) and "vs_lin_param_grad" in lib.vs_last_error(disc._h).decode()
-    disc.close()
+    r.discrete_family()
 
 
 # ------------------------------------------------------------------------------------------------------- 6. autograd
-@pytest.mark.parametrize("name", ["qq-su", "qcp-su"])
-def test_autograd_kernel_against_torch(vs, name, monkeypatch):
+def autograd_policy(vs, name):
     tc = clc.torch_case("linear", name)
-    NT, TT = clc.NT, clc.TT
     env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
     policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
     with torch.no_grad():
         policy.net.weight.copy_(torch.as_tensor(tc["W"]))
+    return tc, env, policy
+
+
+@pytest.mark.parametrize("name", ["qq-su", "qcp-su"])
+def test_autograd_kernel_against_torch(vs, name, monkeypatch):
+    tc, env, policy = autograd_policy(vs, name)
     weight = policy.net.weight
-
-    def grads(roll):
-        init = dev(tc["init"]).requires_grad_(True)
-        obs, rew, act, lengths = roll(init, TT)
-        loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
-        return torch.autograd.grad(loss, [weight, init], retain_graph=True), loss, (obs, rew, act)
-
     by_torch = vs.DifferentiablePolicyRollout(env, policy, batch_lanes=32, param_pass="torch")
-    g_torch, _, out_torch = grads(by_torch)
+    g_torch, _, out_torch = pgc.autograd_grads(vs, by_torch, tc, [weight])
     by_torch.close()
-    # ---- through the kernel: no [N, T, .] copy is made; what every batch's call saw is kept for the bound
-    seen = []
-    plain = vs.VecSimEnv.lin_param_grad
-
-    def spy(self, t_steps, abar, out=None, accumulate=False):
-        obs, inside, _ = rows_of(self, self.n_envs, t_steps)
-        seen.append((obs, inside, vs.lanes_first(abar, self.n_envs).cpu().numpy(), self.ld, bool(accumulate)))
-        return plain(self, t_steps, abar, out=out, accumulate=accumulate)
-
+    # ---- through the kernel: no [N, T, .] copy is made
     roll = vs.DifferentiablePolicyRollout(env, policy, batch_lanes=32, param_pass="kernel")
     assert roll.param_pass == "kernel" and not roll._needs_rows
     init = dev(tc["init"]).requires_grad_(True)
-    obs, rew, act, lengths = roll(init, TT)                      # the forward pass reads the records; the backward pass must not
-    loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
-    assert all(torch.equal(a, b) for a, b in zip((obs, rew, act), out_torch))
+    loss, out_kernel = pgc.autograd_loss(vs, roll, init)         # the forward pass reads the records; the backward pass must not
+    assert all(torch.equal(a, b) for a, b in zip(out_kernel, out_torch))
 
     def no_rows(*a, **k):
         raise AssertionError("traj_tensors was called in backward")
@@ -416,33 +277,23 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     assert torch.equal(again[0], g_kernel[0])                                          # backward() twice: the same bits
     assert torch.equal(g_kernel[1], g_torch[1]) and bool(g_kernel[1].any())            # d init_states: the same sweep
     # ---- once more with the spy, for the rows and adjoints of every batch
-    monkeypatch.setattr(vs.VecSimEnv, "lin_param_grad", spy)
+    seen = []
+    pgc.spy_on(vs, monkeypatch, LIN, seen)
     spied = torch.autograd.grad(loss, [weight], retain_graph=True)
     assert torch.equal(spied[0], g_kernel[0])
-    assert [s[4] for s in seen] == [False, True, True] and [s[2].shape[0] for s in seen] == [32, 32, 6]  # three batches accumulate
-    bound = 0.0
-    for ob, inside, abar, ld, _ in seen:
-        bound = bound + host.lin_param_grad_fp64(clc.SMALL, None, ob, abar.transpose(1, 0, 2).reshape(TT * abar.shape[0], -1), inside,
-                                                 chain=host.chain_of(ld, TT, n_cu()))[2]
+    pgc.check_three_batches_accumulate(seen)
     assert g_kernel[0].shape == weight.shape
-    flat = lambda g: g.detach().cpu().numpy().astype(np.float64)  # noqa: E731
-    worst = worst_ratio(np.abs(flat(g_kernel[0]) - flat(g_torch[0])), 2.0 * bound)
-    print(f"{name}: kernel against torch parameter pass, worst difference / (2 bound) {worst:.3f}")
-    assert np.abs(flat(g_torch[0])).max() > 0.0 and worst <= 1.0, (name, worst)
+
+    def bound_of(s):
+        return host.lin_param_grad_fp64(clc.SMALL, None, s.obs, s.bufs[0], s.inside, chain=pgc.chain_of(s.ld, clc.TT, n_cu()))[2]
+
+    pgc.check_kernel_against_torch_pass(name, seen, bound_of, pgc.flat_grads(g_kernel[:1]), pgc.flat_grads(g_torch[:1]), 2.0, "2 bound")
     roll.close()
 
 
 def test_autograd_fp64_weights_take_the_torch_pass(vs):
-    name = "qq-su"
-    tc = clc.torch_case("linear", name)
-    env = getattr(vs, clc.ENVS[name])(max_steps=MAX_STEPS, **KW[name])
-    policy = vs.LinearPolicy(env.spec, vs.FeatureStack(vs.identity_feat, vs.sin_feat, vs.const_feat, vs.MultFeat((0, 1))))
-    with torch.no_grad():
-        policy.net.weight.copy_(torch.as_tensor(tc["W"]))
+    tc, env, policy = autograd_policy(vs, "qq-su")
     policy.double()
     roll = vs.DifferentiablePolicyRollout(env, policy, batch_lanes=32, param_pass="kernel")
-    assert roll.param_pass == "torch"
-    obs, rew, act, lengths = roll(dev(tc["init"]), clc.TT)
-    g, = torch.autograd.grad(-vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum(), [policy.net.weight])
-    assert g.dtype == torch.float64 and bool(torch.isfinite(g).all()) and bool(g.any())
+    pgc.check_fp64_takes_the_torch_pass(vs, roll, tc, [policy.net.weight])
     roll.close()

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import linear_feature_cases as lc  # noqa: E402
-import test_lin_param_grad_host as host  # noqa: E402
+import lin_param_grad_fp64 as host  # noqa: E402
 from derivative_cases import KW, MAX_STEPS  # noqa: E402
 from oracle import cpu_ref  # noqa: E402
 
@@ -209,7 +209,7 @@ def slots_of(terms, n_vis):
 
 @pytest.mark.parametrize("j", [0, 1])
 def test_wiring_of_all_128_slots_on_the_ball_balancer(vs, j):
-    """qbb-full of test_lin_param_grad_host.EXTRA: each of the 128 slots one-hot in action row j (128 one-step launches of 256 lanes and
+    """qbb-full of lin_param_grad_fp64.EXTRA: each of the 128 slots one-hot in action row j (128 one-step launches of 256 lanes and
     as many sweeps): the hot action row holds that slot's feature, the other one exactly 0, d_init that slot's derivative"""
     terms = host.EXTRA["qbb-full"][1]
     p = Probe(vs, "qbb", lc.qbb_states())

@@ -14,71 +14,31 @@ W_hn h + b_hn near 0, whose error is gamma(131) of 64 products) then exceed it b
 size 0.1 .. 1 and the floor is 1e-4 .. 1e-3 of the largest entry, of the size of the relative term.
 
 Reference: rnn_param_grad_fp64.param_grad_fp64 on the RECORDED observations, hidden states and lengths; tolerance: twice its bound
-(derived in that module's docstring), the chains read off the launch by grid_of.  The worst measured ratio per case is printed (-s).
+(derived in that module's docstring), the chains read off the launch by param_grad_cases.rnn_grid_of.  The worst measured ratio per
+case is printed (-s).  The cases (CASES, ELMAN_AS_FNN, case) and the checks that the three parameter-gradient passes share are in
+param_grad_cases.py; the tests here hand them this family.
 """
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
-
-from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import closed_loop_cases as clc  # noqa: E402  (make_rnn, flat_params, set_rnn, the autograd cases; the [8] tanh network of the pendulum)
+import closed_loop_cases as clc  # noqa: E402  (flat_params, set_rnn, the autograd cases; the [8] tanh network of the pendulum)
+import fnn_param_grad_fp64 as fnn_host  # noqa: E402  (the FNN pass's fp64 reference and bound)
+import param_grad_cases as pgc  # noqa: E402
 import rnn_param_grad_fp64 as ref64  # noqa: E402
-import test_fnn_param_grad_host as fnn_host  # noqa: E402  (the FNN pass's fp64 reference and bound)
-from derivative_cases import ACT_IN, KW, MAX_STEPS, STATE_BUFFERS, dev, draw_params_and_init, frozen, record_mode2  # noqa: E402
+from derivative_cases import ACT_IN, KW, MAX_STEPS, dev, record_mode2  # noqa: E402
+from param_grad_cases import CASES, ELMAN_AS_FNN, RNN, case, vs, worst_ratio  # noqa: E402,F401  (vs: the fixture)
 
-N, T = 70, 12
-# case -> (family, cell, layers, units, output nonlinearity, obs_idx, seed, gain of the output layer, whh, inside a noise strategy)
-CASES = {
-    "omo-tanh-3": ("omo", "tanh", 1, 3, None, None, 71, 1.0, 1.5, False),          # padded to 4 units
-    "pend-view-relu-8": ("pend", "relu", 1, 8, None, (2, 0), 72, 2.0, 4.0, False),  # the policy sees (th_dot, sin th)
-    "pend-gru-8": ("pend", "gru", 1, 8, None, None, 73, 2.5, 1.0, False),
-    "qq-su-gru-2x64": ("qq-su", "gru", 2, 64, None, None, 74, 3.0, 1.0, False),
-    "qcp-su-lstm-64": ("qcp-su", "lstm", 1, 64, None, None, 75, 3.0, 1.0, False),
-    "qbb-lstm-2x33-tanh-out": ("qbb", "lstm", 2, 33, "tanh", None, 76, 1.0, 1.0, False),
-    "bob-gru-63-noise": ("bob", "gru", 1, 63, None, None, 77, 3.0, 1.0, True),
-}
-# Elman tanh cells WITHOUT recurrence: the feed-forward network [H] tanh with bias b_ih + b_hh
-ELMAN_AS_FNN = {"omo-elman-3": ("omo", "tanh", 1, 3, None, None, 81, 1.0, 0.0, False),
-                "qq-su-elman-64": ("qq-su", "tanh", 1, 64, None, None, 82, 3.0, 0.0, False)}
-
-
-@pytest.fixture(scope="module")
-def vs():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import simurlacra_amd
-
-    return simurlacra_amd
-
-
-@functools.lru_cache(maxsize=None)
-def case(key):
-    name, cell, n_layers, H, out, obs_idx, seed, gain, whh, noisy = {**CASES, **ELMAN_AS_FNN}[key]
-    ref = cpu_ref.make_ref(name, max_steps=MAX_STEPS, **KW[name])
-    rng = np.random.default_rng(500 + seed)
-    params, init = draw_params_and_init(ref, name, rng)          # 150 lanes, lanes 0 .. 9 at the edge
-    lanes = np.concatenate([np.arange(64), np.arange(6)])        # the second lane group: six edge lanes
-    params, init = params[lanes].copy(), init[lanes].copy()
-    h0 = ref.reset(params.astype(np.float64), init.astype(np.float64), True)["hidden"]
-    net = clc.make_rnn(ref, name, cell, n_layers, H, out, obs_idx, params.astype(np.float64), init.astype(np.float64), h0, rng, T, gain, whh)
-    Hs = clc.hidden_size(net["cell"])
-    cot = lambda *shape: (rng.normal(size=shape) / (N * T)).astype(np.float32)  # noqa: E731  (see the module docstring)
-    return frozen(dict(name=name, ref=ref, params=params, init=init, net=net, Hs=Hs, noisy=noisy, g_rew=cot(N, T), g_obs=cot(N, T + 1, ref.O),
-                       g_act=cot(N, T, ref.A), g_last=cot(N, ref.S + ref.H), g_hid=cot(N, Hs)))
+N, T = pgc.RNN_N, pgc.RNN_T
 
 
 def recorded(vs, key, t=T, cap=T):
     c = case(key)
-    e = vs.VecSimEnv(c["name"], N, max_steps=MAX_STEPS, **KW[c["name"]])
     std = [0.02 * ACT_IN[c["name"]]] * c["ref"].A if c["noisy"] else None
-    return record_mode2(e, cap, c["params"], lambda e: clc.set_rnn(e, c["net"], std), c["init"], (t,), noise_seed=91)
+    return pgc.recorded(vs, c, lambda e: clc.set_rnn(e, c["net"], std), n=N, t=t, cap=cap, noise_seed=91)
 
 
 def sweep(vs, key, e, t=T):
@@ -90,34 +50,18 @@ def sweep(vs, key, e, t=T):
     return da, dh
 
 
-def grid_of(ld, t_steps):
-    """(workgroups, rows a workgroup accumulates at most): a workgroup per tile while there are fewer tiles than compute units, else
-    one per compute unit, each a contiguous run of tiles"""
-    tiles = (ld // 64) * t_steps
-    n_wg = min(tiles, torch.cuda.get_device_properties(0).multi_processor_count)
-    return n_wg, 64 * -(-tiles // n_wg)
-
-
 def rows_of(vs, key, e, t, abar, d_hid):
     """the handle's records and the two cotangents as step-major rows, and the lengths"""
-    c = case(key)
-    obs = e.traj_tensors(t, N)["obs"].cpu().numpy()                      # [t, N, O]
-    if c["net"]["obs_idx"] is not None:
-        obs = obs[:, :, list(c["net"]["obs_idx"])]
-    hid = vs.lanes_first(e.hidden_record_tensor()[:t], N).cpu().numpy()   # [N, t, Hs]
-    length = e.rollout_lengths(N, t)[0].cpu().numpy()
-    inside = (np.arange(t)[:, None] < length[None, :]).reshape(-1)
-    ab, dh = (vs.lanes_first(x, N).cpu().numpy().transpose(1, 0, 2).reshape(t * N, -1) for x in (abar, d_hid))
-    return obs.reshape(t * N, -1), hid.transpose(1, 0, 2).reshape(t * N, -1), ab, dh, inside, length
+    obs, inside, length = pgc.rows_of(e, N, t, case(key)["net"]["obs_idx"])
+    return obs, pgc.hidden_rows(vs, e, N, t), pgc.device_rows(vs, abar, N), pgc.device_rows(vs, d_hid, N), inside, length
 
 
-def reference(vs, key, e, t, abar, d_hid, more_adds=0):
+def reference(vs, key, e, t, abar, d_hid):
     c = case(key)
     x, p, ab, dh, inside, length = rows_of(vs, key, e, t, abar, d_hid)
     ab, dh = np.where(inside[:, None], ab, 0.0), np.where(inside[:, None], dh, 0.0)  # (the caller may have put NaN behind the rows)
-    n_wg, acc = grid_of(e.ld, t)
     want, mag, bound, info = ref64.param_grad_fp64(c["net"]["cell"], x, p, ab, dh, inside, c["net"]["output_nonlin"],
-                                                   chains=dict(acc=acc, wg=-(-n_wg // 4) + 2 + more_adds))
+                                                   chains=pgc.chains_of(pgc.rnn_grid_of(e.ld, t, pgc.n_cu())))
     assert info["zmax"] <= 8.0 and info["kink"] >= 1e-3 and (bound <= 1e-3 * mag + 1e-4).all()
     return want, bound, length
 
@@ -132,7 +76,7 @@ def test_against_the_fp64_reference(vs, key):
     assert got.dtype == torch.float32 and got.is_cuda and tuple(got.shape) == (clc.flat_params(case(key)["net"]).size,)
     got = got.cpu().numpy().astype(np.float64)
     assert np.isfinite(got).all() and e.error_count() == 0
-    worst = ref64.worst_ratio(np.abs(got - want), 2.0 * bound)
+    worst = worst_ratio(np.abs(got - want), 2.0 * bound)
     print(f"{key}: worst |kernel - fp64| / (2 bound) {worst:.3f}; lengths {np.bincount(length, minlength=T + 1).tolist()}, "
           f"second lane group {length[64:].tolist()}")
     assert np.abs(want).max() > 0.0 and worst <= 1.0, (key, worst)
@@ -156,19 +100,7 @@ def test_every_lane_of_a_group_ends_before_the_last_rows(vs):
 def test_nan_behind_the_rows_changes_no_bit(vs, key):
     """NaN in abar, d_hid and the hidden-state record at every row t >= L and at lanes n .. ld - 1: the same bits, and finite"""
     e = recorded(vs, key)
-    abar, d_hid = sweep(vs, key, e)
-    length = e.rollout_lengths(N, T)[0]
-    assert e.ld > N and bool((length < T).any())
-    clean = e.rnn_param_grad(T, abar, d_hid)
-    behind = torch.arange(T, device="cuda")[:, None] >= length[None, :]  # [T, N]
-    nan = torch.full((), float("nan"), device="cuda")
-    hrec = e.hidden_record_tensor()
-    for x in (abar, d_hid, hrec[:T]):
-        x[:, :, :N] = torch.where(behind[:, None, :], nan, x[:, :, :N])
-        x[:, :, N:] = float("nan")
-    assert bool(torch.isnan(abar[:, :, :N]).any()) and bool(torch.isnan(hrec[:T, :, :N]).any())
-    got = e.rnn_param_grad(T, abar, d_hid)
-    assert bool(clean.any()) and bool(torch.isfinite(got).all()) and torch.equal(got, clean)
+    pgc.check_nan_behind_the_rows(e, RNN, N, T, sweep(vs, key, e), records=[e.hidden_record_tensor()])
     e.close()
 
 
@@ -176,38 +108,14 @@ def test_two_calls_and_accumulate_are_exact(vs):
     key = "qcp-su-lstm-64"
     e = recorded(vs, key)
     abar, d_hid = sweep(vs, key, e)
-    g = e.rnn_param_grad(T, abar, d_hid)
-    assert torch.equal(e.rnn_param_grad(T, abar, d_hid), g) and bool(g.any())
-    e.rnn_param_grad(T - 5, abar[:T - 5].contiguous(), d_hid[:T - 5].contiguous())  # another grid in between
-    assert torch.equal(e.rnn_param_grad(T, abar, d_hid), g)
-    r = torch.randn(g.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(3))
-    out = r.clone()
-    assert e.rnn_param_grad(T, abar, d_hid, out=out, accumulate=True) is out
-    assert torch.equal(out, r + g)
-    out.fill_(7.0)
-    assert e.rnn_param_grad(T, abar, d_hid, out=out) is out and torch.equal(out, g)
-    with pytest.raises(vs.ValueErr):
-        e.rnn_param_grad(T, abar, d_hid, accumulate=True)
-    with pytest.raises(vs.ShapeErr):
-        e.rnn_param_grad(T, abar, d_hid[:, :-1].contiguous())
+    pgc.check_two_calls_and_accumulate(vs, e, RNN, T, [abar, d_hid], [abar, d_hid[:, :-1].contiguous()], dense=False)
     e.close()
 
 
 def test_the_handle_is_untouched(vs):
-    L = vs._lib
     key = "qq-su-gru-2x64"
     e = recorded(vs, key)
-    abar, d_hid = sweep(vs, key, e)
-    before = [e.get(getattr(L, b)).copy() for b in STATE_BUFFERS]
-    planes, words = e.traj_planes()
-    rows = [p.clone() for p, _ in planes] + [words.clone(), e.hidden_record_tensor().clone(), e.policy_hidden().clone()]
-    e.rnn_param_grad(T, abar, d_hid)
-    torch.cuda.synchronize()
-    for b, x in zip(STATE_BUFFERS, before):
-        assert np.array_equal(e.get(getattr(L, b)), x), b
-    planes, words = e.traj_planes()
-    now = [p for p, _ in planes] + [words, e.hidden_record_tensor(), e.policy_hidden()]
-    assert all(torch.equal(a, b) for a, b in zip(now, rows)) and e.error_count() == 0
+    pgc.check_the_handle_is_untouched(vs, e, RNN, T, lambda: sweep(vs, key, e), lambda: [e.hidden_record_tensor(), e.policy_hidden()])
     e.close()
 
 
@@ -232,15 +140,13 @@ def test_an_elman_cell_without_recurrence_is_the_fnn_pass(vs, key):
     e.set_policy_fnn(fnn_host.flat_of(net["W"], net["b"]).astype(np.float32), [H], hidden_nonlin="tanh")
     fnn = e.fnn_param_grad(T, abar).cpu().numpy().astype(np.float64)
     x, _, ab, _, inside, _ = rows_of(vs, key, e, T, abar, d_hid)
-    tiles = (e.ld // 64) * T
-    n_wg = min(-(-tiles // 4), 2 * torch.cuda.get_device_properties(0).multi_processor_count)
-    fb = fnn_host.param_grad_fp64(net, x, ab, inside, chains=dict(acc=64 * -(-tiles // (4 * n_wg)), wg=-(-n_wg // 4) + 2))[3]
+    fb = fnn_host.param_grad_fp64(net, x, ab, inside, chains=pgc.chains_of(pgc.fnn_grid_of(e.ld, T, pgc.n_cu())))[3]
     # rnn order: w_ih [H, O], w_hh [H, H], b_ih [H], b_hh [H], w_out, b_out;  fnn order: W_1 [H, O], b_1 [H], W_out, b_out
     n1, nh = H * O, H * H
     pick = np.concatenate([np.arange(n1), n1 + nh + np.arange(H), n1 + nh + 2 * H + np.arange(A * H + A)])
-    assert ref64.worst_ratio(np.abs(rnn - want), 2.0 * bound) <= 1.0                                  # (dW_hh = delta h_t^T included: h_t is not 0)
+    assert worst_ratio(np.abs(rnn - want), 2.0 * bound) <= 1.0                                  # (dW_hh = delta h_t^T included: h_t is not 0)
     assert np.array_equal(rnn[n1 + nh:n1 + nh + H], rnn[n1 + nh + H:n1 + nh + 2 * H])                 # db_ih and db_hh: the same sums
-    worst = ref64.worst_ratio(np.abs(rnn[pick] - fnn), 2.0 * bound[pick] + 2.0 * fb)
+    worst = worst_ratio(np.abs(rnn[pick] - fnn), 2.0 * bound[pick] + 2.0 * fb)
     print(f"{key}: worst |rnn pass - fnn pass| / (sum of the doubled bounds) {worst:.3f}")
     assert np.abs(fnn).max() > 0.0 and worst <= 1.0, (key, worst)
     e.close()
@@ -249,63 +155,20 @@ def test_an_elman_cell_without_recurrence_is_the_fnn_pass(vs, key):
 # ------------------------------------------------------------------------------------------------------- 4. refusals
 def test_refusals_leave_the_output_untouched(vs):
     L = vs._lib
-    lib = L.load()
     key = "pend-gru-8"
     c = case(key)
-    d = vs.env_dims(c["name"])
     e = recorded(vs, key)
-    n_params = e._rnn_n_params
-    abar, d_hid = sweep(vs, key, e)
-    out = torch.full((n_params + 1,), 7.0, device="cuda")
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-
-    def call(handle, t_steps=T, ab=abar, dh=d_hid, dp=out, n=None):
-        rc = lib.vs_rnn_param_grad(handle._h if handle is not None else None, t_steps, ptr(ab), ptr(dh), ptr(dp),
-                                   n_params if n is None else n, 0)
-        torch.cuda.synchronize()
-        return rc
-
-    def refused(code, handle, **kw):
-        assert call(handle, **kw) == code
-        assert bool((out == 7.0).all())  # the sentinels
-        if handle is not None:
-            assert "vs_rnn_param_grad" in lib.vs_last_error(handle._h).decode()
-
-    def served():
-        assert call(e) == L.VS_OK and not bool((out[:n_params] == 7.0).any()) and float(out[n_params]) == 7.0
-        out.fill_(7.0)
-
-    refused(L.VS_ERR_ARG, None)
-    refused(L.VS_ERR_ARG, e, ab=None)
-    refused(L.VS_ERR_ARG, e, dh=None)
-    refused(L.VS_ERR_ARG, e, dp=None)
-    for t_steps in (0, -3, T + 1):
-        refused(L.VS_ERR_ARG, e, t_steps=t_steps)
-    for n in (n_params - 1, n_params + 1):
-        refused(L.VS_ERR_ARG, e, n=n)
-    served()
+    r = pgc.Refusals(vs, e, RNN, T, sweep(vs, key, e))
+    r.arguments()
     e.set_policy_hidden_record(c["Hs"] + 1)                     # a record plane of another width
-    refused(L.VS_ERR_STATE, e)
+    r.refused(L.VS_ERR_STATE, e)
     e.set_policy_hidden_record(0)
-    refused(L.VS_ERR_STATE, e)
+    r.refused(L.VS_ERR_STATE, e)
     e.set_policy_hidden_record(c["Hs"])
-    e.set_policy_population(np.tile(clc.flat_params(c["net"])[None, :], (2, 1)), lane_set=np.arange(N) // 64)
-    refused(L.VS_ERR_STATE, e)
-    e.set_policy_population(None)
-    e.set_policy_rnn(None)                                      # no policy
-    refused(L.VS_ERR_STATE, e)
-    e.set_policy_linear(np.zeros(d["A"], dtype=np.float32), ["const"])
-    refused(L.VS_ERR_STATE, e)
-    clc.set_rnn(e, c["net"])
-    e.set_record_mode(1)
-    e.set_traj_capacity(T)
-    refused(L.VS_ERR_STATE, e)
-    e.set_record_mode(2)
-    e.set_traj_capacity(T)
-    clc.set_rnn(e, c["net"])
-    served()                                                    # after the refusals the same handle serves a good call
-    assert e.error_count() == 0
+    r.policies(vs.env_dims(c["name"]), clc.flat_params(c["net"]), lambda: e.set_policy_rnn(None), lambda: clc.set_rnn(e, c["net"]),
+               dict(linear={}, fnn={}, playback={}))
     e.close()
+    r.discrete_family()
 
 
 # ------------------------------------------------------------------------------------------------------- 5. autograd
@@ -319,46 +182,25 @@ def test_autograd_kernel_against_torch(vs, name, monkeypatch):
     th0 = clc.flat_params(tc["net"])
     policy.param_values = torch.as_tensor(th0)
     weights = list(policy.parameters())
-
-    def grads(roll):
-        init = dev(tc["init"]).requires_grad_(True)
-        obs, rew, act, lengths = roll(init, TT)
-        loss = -vs.discounted_return(rew, lengths, clc.GAMMA).sum() + 1e-3 * act.pow(2).sum()
-        return torch.autograd.grad(loss, weights + [init], retain_graph=True), loss
-
+    grads = lambda roll: pgc.autograd_grads(vs, roll, tc, weights)[:2]  # noqa: E731
+    flat = lambda g: pgc.flat_grads(g[:-1])  # noqa: E731
     by_torch = vs.DifferentiableRecurrentRollout(env, policy, batch_lanes=32, param_pass="torch")
     g_torch, _ = grads(by_torch)
     by_torch.close()
     seen = []
-    plain = vs.VecSimEnv.rnn_param_grad
-
-    def spy(self, t_steps, abar, d_hid, out=None, accumulate=False):
-        n = self.n_envs
-        obs = self.traj_tensors(t_steps, n)["obs"].cpu().numpy().reshape(t_steps * n, -1)
-        hid = vs.lanes_first(self.hidden_record_tensor()[:t_steps], n).cpu().numpy().transpose(1, 0, 2).reshape(t_steps * n, -1)
-        length = self.rollout_lengths(n, t_steps)[0].cpu().numpy()
-        ab, dh = (vs.lanes_first(x, n).cpu().numpy().transpose(1, 0, 2).reshape(t_steps * n, -1) for x in (abar, d_hid))
-        seen.append((obs, hid, ab, dh, (np.arange(t_steps)[:, None] < length[None, :]).reshape(-1), self.ld, bool(accumulate), n))
-        return plain(self, t_steps, abar, d_hid, out=out, accumulate=accumulate)
-
-    monkeypatch.setattr(vs.VecSimEnv, "rnn_param_grad", spy)
+    pgc.spy_on(vs, monkeypatch, RNN, seen)
     roll = vs.DifferentiableRecurrentRollout(env, policy, batch_lanes=32, param_pass="kernel")
     assert roll.param_pass == "kernel"
     g_kernel, loss = grads(roll)
-    assert [s[6] for s in seen] == [False, True, True] and [s[7] for s in seen] == [32, 32, 6]  # three batches accumulate
-    again = torch.autograd.grad(loss, weights, retain_graph=True)
-    assert all(torch.equal(a, b) for a, b in zip(again, g_kernel[:-1]))                # backward() twice: the same bits
-    assert torch.equal(g_kernel[-1], g_torch[-1]) and bool(g_kernel[-1].any())         # d init_states: the same sweep
-    bound = 0.0
-    for obs, hid, ab, dh, inside, ld, _, _ in seen[:3]:
-        n_wg, acc = grid_of(ld, TT)
-        bound = bound + ref64.param_grad_fp64(tc["net"]["cell"], obs, hid, ab, dh, inside, None,
-                                              chains=dict(acc=acc, wg=-(-n_wg // 4) + 3))[2]
-    flat = lambda g: torch.cat([x.reshape(-1) for x in g[:-1]]).cpu().numpy().astype(np.float64)  # noqa: E731
-    assert all(a.shape == w.shape for a, w in zip(g_kernel, weights))
-    worst = ref64.worst_ratio(np.abs(flat(g_kernel) - flat(g_torch)), 4.0 * bound)  # each side within the doubled bound of the reference
-    print(f"{name}: kernel against torch parameter pass, worst difference / (2 x 2 bound) {worst:.3f}")
-    assert np.abs(flat(g_torch)).max() > 0.0 and worst <= 1.0, (name, worst)
+    pgc.check_three_batches_accumulate(seen)
+    pgc.check_backward_twice_and_the_sweep(loss, weights, g_kernel, g_torch)
+
+    def bound_of(s):  # (one more add: accumulate)
+        return ref64.param_grad_fp64(tc["net"]["cell"], s.obs, s.hid, *s.bufs, s.inside, None,
+                                     chains=pgc.chains_of(pgc.rnn_grid_of(s.ld, TT, pgc.n_cu()), 1))[2]
+
+    # each side within the doubled bound of the reference
+    pgc.check_kernel_against_torch_pass(name, seen, bound_of, flat(g_kernel), flat(g_torch), 4.0, "2 x 2 bound")
     # ---- two plain gradient steps (in units of |theta|) lower the loss
     scale = np.abs(th0.astype(np.float64))
     eta = 0.02 / np.abs(flat(g_kernel) * scale).max()

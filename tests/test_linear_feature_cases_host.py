@@ -12,7 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import linear_feature_cases as lc  # noqa: E402
-import test_lin_param_grad_host as host  # noqa: E402
+import lin_param_grad_fp64 as host  # noqa: E402
 
 f32 = np.float32
 SCALAR_TERMS = lc.ELEM + ("const",)

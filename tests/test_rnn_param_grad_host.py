@@ -3,56 +3,19 @@ vs_rnn_param_grad / DifferentiableRecurrentRollout(param_pass=...), the parts th
 binding, the NULL refusals, the fp64 restatement of rnn_param_grad_fp64 against torch.autograd.grad of the .double() modules, and what
 its error bound lets through and what it catches.
 
-Rows here are synthetic (normal inputs, hidden states, cotangents; every fourth row is outside): the modules' default initialisation,
-uniform in +-1 / sqrt(H), keeps every gate unsaturated, which the test checks (|z| <= 8).
+Rows here are synthetic (rnn_param_grad_fp64.rows_case: normal inputs, hidden states, cotangents; every fourth row is outside): the
+modules' default initialisation, uniform in +-1 / sqrt(H), keeps every gate unsaturated, which the test checks (|z| <= 8).
 """
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import simurlacra_amd as vs
-from simurlacra_amd import _lib as L
 
 torch = pytest.importorskip("torch")
 
+import param_grad_cases as pgc  # noqa: E402
 import rnn_param_grad_fp64 as ref64  # noqa: E402
-import closed_loop_cases as cells  # noqa: E402  (unpack_rnn, torch_policy)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the table of test_gpu_rnn_param_grad: (env class, dt, cell, layers, units, output nonlinearity)
-TABLE = {
-    "omo-tanh-3": ("OneMassOscillatorSim", 0.02, "tanh", 1, 3, None),
-    "pend-relu-8": ("PendulumSim", 0.01, "relu", 1, 8, None),
-    "pend-gru-8": ("PendulumSim", 0.01, "gru", 1, 8, None),
-    "qq-su-gru-2x64": ("QQubeSwingUpSim", 0.004, "gru", 2, 64, None),
-    "qcp-su-lstm-64": ("QCartPoleSwingUpSim", 0.002, "lstm", 1, 64, None),
-    "qbb-lstm-2x33-tanh-out": ("QBallBalancerSim", 0.01, "lstm", 2, 33, "tanh"),
-    "bob-gru-63": ("BallOnBeamSim", 0.01, "gru", 1, 63, None),
-}
-ROWS = 240
-
-
-def rows_case(key):
-    """(torch fp64 policy, unpacked fp64 net, x, p, abar, d_hid, inside, output nonlinearity's name)"""
-    env_cls, dt, cell, nl, H, out = TABLE[key]
-    env = getattr(vs, env_cls)(dt=dt, max_steps=30)
-    O, A = env.obs_space.flat_dim, env.act_space.flat_dim
-    torch.manual_seed(11)
-    policy = cells.torch_policy(env.spec, cell, nl, H, {None: None, "tanh": torch.tanh}[out])
-    with torch.no_grad():  # float32 values, so that the float32 pass below runs on the very same parameters
-        flat = policy.param_values.detach().float()
-    policy = policy.double()
-    policy.param_values = flat.double()
-    net = cells.unpack_rnn(flat.numpy(), cell, nl, H, O, A)
-    rng = np.random.default_rng(17)
-    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
-    x, p = f32(rng.normal(size=(ROWS, O))), f32(0.5 * rng.normal(size=(ROWS, policy.hidden_size)))
-    abar, d_hid = f32(rng.normal(size=(ROWS, A))), f32(rng.normal(size=(ROWS, policy.hidden_size)))
-    inside = np.arange(ROWS) % 4 != 3
-    return policy, net, x, p, abar, d_hid, inside, out
+from rnn_param_grad_fp64 import TABLE, rows_case  # noqa: E402
 
 
 def torch_grad(policy, x, p, abar, d_hid, inside, dtype):
@@ -65,30 +28,15 @@ def torch_grad(policy, x, p, abar, d_hid, inside, dtype):
 
 # --------------------------------------------------------------------------------------------------------- the C-ABI
 def test_header_declares_the_exact_signature():
-    header = open(os.path.join(ROOT, "include", "vecsim.h")).read()
-    sig = (r"int\s+vs_rnn_param_grad\(vs_handle h, int t_steps, const float\* abar, const float\* d_hid,\s*float\* d_params, "
-           r"int64_t n_params, int accumulate\);")
-    assert re.search(sig, header)
+    pgc.check_header_declares_the_signature(pgc.RNN)
 
 
 def test_symbol_is_exported_and_bound():
-    lib = C.CDLL(L.LIB_PATH)
-    assert hasattr(lib, "vs_rnn_param_grad")
-    assert "vs_rnn_param_grad" in L.exported_symbols()
-    fn = L.load().vs_rnn_param_grad
-    assert fn.restype is C.c_int and len(fn.argtypes) == 7 and fn.argtypes[5] is C.c_int64
-    assert L.load().vs_version() >= 317
-    assert callable(vs.VecSimEnv.rnn_param_grad)
+    pgc.check_symbol_is_exported_and_bound(pgc.RNN)
 
 
 def test_null_handle_and_null_pointers_are_refused_before_a_device_is_touched():
-    out = (C.c_float * 4)()
-    fn = L.load().vs_rnn_param_grad
-    assert fn(None, 1, out, out, out, 4, 0) == L.VS_ERR_ARG
-    assert fn(None, 1, None, out, out, 4, 0) == L.VS_ERR_ARG
-    assert fn(None, 1, out, None, out, 4, 0) == L.VS_ERR_ARG
-    assert fn(None, 1, out, out, None, 4, 0) == L.VS_ERR_ARG
-    assert all(v == 0.0 for v in out)
+    pgc.check_null_handle_and_null_pointers_are_refused(pgc.RNN)
 
 
 # ------------------------------------------------------------------------------------------------- the fp64 restatement
@@ -109,7 +57,7 @@ def test_bound_admits_the_fp32_pass_and_stays_small(key):
     assert info["zmax"] <= 8.0                                   # gates unsaturated: the bound's assumption
     assert (bound <= 1e-3 * mag + 1e-4).all()            # the bound cannot hide an error of a thousandth of a parameter's terms
     fp32 = torch_grad(policy, x, p, abar, d_hid, inside, torch.float32)
-    worst = ref64.worst_ratio(np.abs(fp32 - want), 2.0 * bound)
+    worst = pgc.worst_ratio(np.abs(fp32 - want), 2.0 * bound)
     print(f"{key}: torch fp32 pass against fp64, worst error / (2 bound) {worst:.3f}; bound / sum |term| at most "
           f"{float((bound / np.where(mag > 0, mag, 1.0)).max()):.1e}")
     assert worst <= 1.0, (key, worst)
