@@ -597,6 +597,28 @@ int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float
  * Refused with nothing written: everything vs_rollout_vjp_rnn refuses, with the same codes; NULL abar, d_hid or d_params, n_params
  * other than the policy's parameter count, more than 2^31 - 1 tiles of 64 lanes x one step (VS_ERR_ARG). */
 int vs_rnn_param_grad(vs_handle h, int t_steps, const float* abar, const float* d_hid, float* d_params, int64_t n_params, int accumulate);
+/* The gradient of the exploration noise's std that the three closed-loop sweeps leave out, as one device pass.  The policy kernels
+ * form the raw action as a_t = mean_t + noise_std (.) eps_t (NormalActNoiseExplStrat, P/exploration/stochastic_action.py:121-180:
+ * the reparameterised sample of Normal(mean, std)), eps_t ~ N(0, 1) keyed by (noise_seed, index offset + lane, episode, step), and
+ * the sweeps return the TOTAL adjoint abar_t of the raw action as d_act, so
+ *     d Phi / d noise_std[j] = sum over the rows t < L of every lane i < n_envs of abar_t[j] eps_t[j].
+ * eps is not stored anywhere: it is drawn again with the rollout kernels' own calls and is their noise bit for bit -- the noise a
+ * recording vs_step_policy(.., noise_seed) adds to rows 0 .. t_steps - 1 of a record that starts at a reset (step counter 0 at row 0,
+ * in one launch or several; the episode counter is the handle's current one).  A policy set with noise_std = 0 is served: eps is
+ * defined by the key alone, it is the noise a launch with this noise_seed WOULD add, and the derivative at 0 is the same sum.
+ *   abar        [t_steps][A][ld]  a sweep's d_act as written (lanes last); behind a lane's end and at lanes >= n_envs it is never read
+ *   d_std       [A], device       out: the gradient; accumulate != 0: added to what it holds, one fp32 add per entry
+ *   d_std_lane  [A][ld] or NULL   out: every lane's own sum over t (in increasing t), 0 at lanes >= n_envs
+ *   eps         [t_steps][A][ld] or NULL   out: the regenerated noise, exact zeros behind a lane's end and at lanes >= n_envs
+ * Runs on the handle's stream and writes nothing of the handle.  Deterministic, no atomics: a partial sum per workgroup, then one
+ * reduction in a fixed order; the grid is a function of (ld, t_steps, device), so two calls return the same bits.  The workspace
+ * belongs to the policy on the handle: allocated at the first call, freed when the policy is replaced or removed.
+ * Accepted: a handle with a linear, feed-forward or recurrent policy and the records of record mode 2.  Refused with nothing
+ * written: everything vs_rollout_vjp refuses, with the same codes; no policy, a playback policy, a population (VS_ERR_STATE); NULL
+ * abar or d_std -- both (and d_std_lane) may be NULL only together, with eps given: the eps-only call --, more than 2^31 - 1 tiles
+ * of 64 lanes x one step (VS_ERR_ARG). */
+int vs_noise_std_grad(vs_handle h, int t_steps, uint64_t noise_seed, const float* abar, float* d_std, int accumulate,
+                      float* d_std_lane, float* eps);
 /* the hidden-state record plane VS_POLICY_HIDDEN_REC: width floats per env and recorded step (0 = off, the default: no traffic).
  * A recording vs_step_policy with a recurrent policy fills it when width equals the policy's packed hidden size. */
 int vs_set_policy_hidden_record(vs_handle h, int width);

@@ -585,8 +585,8 @@ static int drop_policy(vs_handle h) {
     if (int rc = drop_lin(h)) return rc;
     if (int rc = drop_play(h)) return rc;
     if (int rc = drop_pop(h)) return rc;
-    if (int rc = dfree(h, h->pg.part, h->pg.map)) return rc;
-    h->pg.wgs = 0;
+    if (int rc = dfree(h, h->pg.part, h->pg.map, h->pg.npart, h->pg.nmap)) return rc;
+    h->pg.wgs = h->pg.nwgs = 0;
     h->pol_map.clear();
     h->pol_n_params = 0;
     return VS_OK;
@@ -662,7 +662,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 319; }
+int vs_version(void) { return 320; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1918,6 +1918,62 @@ int vs_lin_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
     auto kern = rows.A == 1 ? k_lin_param_grad<1> : k_lin_param_grad<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64), 0, h->stream, rows, abar, h->lin, t_steps, h->pg.part);
     launch_param_reduce(h, n_wg, psize, d_params, accumulate);
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+// what vs_noise_std_grad needs of the policy slot: a policy that adds NormalActNoiseExplStrat's noise, whatever its kind
+static const char* noise_sweep_policy(vs_handle h) {
+    if (!h->lin.w && !h->fnn.w && !h->rnn.w)
+        return h->play.act ? "a playback policy adds no exploration noise" : "no linear, feed-forward or recurrent policy on the handle";
+    if (h->pop.w) return "not available with a policy population on the handle";
+    return nullptr;
+}
+
+// workgroups of k_noise_std_grad: a function of (ld, t_steps, device) only -- a wave per tile while there are fewer tiles than wave
+// slots, else four workgroups of four waves per compute unit, each wave a contiguous run of tiles
+static int noise_std_grad_wgs(const vs_env* h, int t_steps) {
+    const int64_t tiles = (int64_t)(h->d.ld / 64) * t_steps;
+    return (int)std::min<int64_t>((tiles + NSG_WAVES - 1) / NSG_WAVES, 4 * (int64_t)h->n_cu);
+}
+
+int vs_noise_std_grad(vs_handle h, int t_steps, uint64_t noise_seed, const float* abar, float* d_std, int accumulate, float* d_std_lane,
+                      float* eps) {
+    const char* who = "vs_noise_std_grad";
+    // the eps-only call has neither abar nor a sum; every other call needs abar and d_std
+    const bool eps_only = !abar && !d_std && !d_std_lane && eps;
+    static const float some = 0.f;  // (stands in for the two pointers vjp_checks asks for, in the eps-only call)
+    if (int rc = vjp_checks(h, who, t_steps, eps_only ? &some : abar, eps_only ? &some : d_std, noise_sweep_policy,
+                            "NULL handle, abar or d_std (both may be NULL only when eps alone is asked for)"))
+        return rc;
+    if ((int64_t)(h->d.ld / 64) * t_steps > INT_MAX) return fail(h, VS_ERR_ARG, who, "more than 2^31 - 1 row tiles");
+    const int A = ENV_INFO[h->type].A, n_wg = noise_std_grad_wgs(h, t_steps);
+    if (A < 1 || A > 2) return fail(h, VS_ERR_STATE, who, "the noise of one Philox block serves one or two action rows");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (d_std) {  // the workspace belongs to the policy slot (drop_policy frees it)
+        if (!h->pg.nmap) {
+            const int ident[2] = {0, 1};
+            int* map = nullptr;
+            HIPCHK(h, hipMalloc((void**)&map, sizeof(ident)));
+            hipError_t e = hipMemcpy(map, ident, sizeof(ident), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(map); return fail(h, VS_ERR_HIP, who, "index map upload", e); }
+            h->pg.nmap = map;
+        }
+        if (n_wg > h->pg.nwgs) {
+            if (h->pg.npart) HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the smaller one)
+            if (int rc = dfree(h, h->pg.npart)) return rc;
+            h->pg.nwgs = 0;
+            HIPCHK(h, hipMalloc((void**)&h->pg.npart, (size_t)n_wg * A * sizeof(float)));
+            h->pg.nwgs = n_wg;
+        }
+    }
+    const NoiseRows rows{h->d.traj_done, h->d.ep_idx, h->d.idx0, h->d.n, h->d.ld};
+    auto kern = A == 1 ? k_noise_std_grad<1> : k_noise_std_grad<2>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * NSG_WAVES), 0, h->stream, rows, noise_seed, abar, t_steps,
+                       d_std ? h->pg.npart : (float*)nullptr, d_std_lane, eps);
+    if (d_std)
+        hipLaunchKernelGGL((k_fnn_param_reduce<4>), dim3(1), dim3(BLOCK), 0, h->stream, (const float*)h->pg.npart, n_wg, A,
+                           (const int*)h->pg.nmap, d_std, accumulate != 0 ? 1 : 0);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

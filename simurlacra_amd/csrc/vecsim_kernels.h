@@ -21,6 +21,7 @@
 //   k_fnn_param_grad / k_fnn_param_reduce  vs_fnn_param_grad   the network's parameter gradients from the records and the sweep's d_act
 //   k_rnn_param_grad (+ k_fnn_param_reduce)  vs_rnn_param_grad  the recurrent policy's, from the records, the sweep's d_act and d_hid
 //   k_lin_param_grad (+ k_fnn_param_reduce)  vs_lin_param_grad  the linear policy's weights, from the records and the sweep's d_act
+//   k_noise_std_grad (+ k_fnn_param_reduce)  vs_noise_std_grad  the exploration noise's std, from the regenerated noise and the sweep's d_act
 //   k_reset / k_set_params / k_sample_params / k_observe   control path
 // Variants carrying the wrapper pipeline (action noise / delay, observation normalisation / noise) are separate
 // instantiations (template parameter PIPE): the default kernels do not pay for it.
@@ -3432,6 +3433,146 @@ __global__ __launch_bounds__(64) void k_lin_param_grad(FnnRows R, const float* a
         for (int s = 0; s < 2; ++s) part[(size_t)blockIdx.x * (NA * LIN_SLOTS) + j * LIN_SLOTS + 64 * s + lane] = acc[j][s];
 }
 
+// ------------------------------------------------------------------------------ gradient of the exploration noise's std
+// vs_noise_std_grad: the one trainable quantity of a stochastic policy the sweeps leave out.  k_rollout_fnn / k_rollout_rnn /
+// k_rollout_lin form the raw action as a_t = mean_t + sigma (.) eps_t, and the three closed-loop sweeps return the TOTAL adjoint abar_t of
+// the raw action as d_act, so
+//     d Phi / d sigma_j = sum over the rows (t < L_i, i < n) of abar[t][j][i] eps[t][j][i].
+// eps is never stored: it is a pure function of (noise_seed, idx0 + lane, episode, step) and is drawn again here with the rollout
+// kernels' own two calls (noise_draw below is their statements: the same key, the same order of arguments, the same box_muller), so
+// it is the rollout's noise bit for bit.  The kernel needs nothing of the family or of the policy's kind: one instantiation per A.
+//   * The key.  Episode: Dev::ep_idx of the lane, where the recording kernels load es.epi from.  vjp_checks asks for auto-reset off,
+//     and with auto-reset off no launch changes es.epi (only auto_reset does), so what the handle holds now is what every recorded
+//     row was drawn with; k_reset sets it to 1.  Step: the kernels draw with the lane's step counter BEFORE step_one increments it.
+//     k_reset zeroes the counter, so row t of a record that starts at a reset (the sweeps' contract: one rollout per lane, started
+//     at a reset, trajectory offset 0) was drawn with step = t.  A record made by several launches is no exception: a later launch
+//     writes from row `rows so far` on and loads the counter the earlier ones stored, which is that row for every lane still
+//     running; a frozen lane keeps its counter, but its rows lie behind L and are not drawn here.  Hence step = t, for every t < L.
+//   * Lane = env.  Workgroups of NSG_WAVES = 4 waves; a wave owns a contiguous run of tiles (64 lanes x one step, lane-group major, as
+//     in k_fnn_param_grad: L -- the first done bit among rows 0 .. t_steps - 1, lane_length below, the sweeps' loop -- and the
+//     episode once per lane group).  Per live row the lane draws z, loads abar and does acc[j] = fmaf(abar, z[j], acc[j]).  Rows
+//     t >= L, lanes >= n and rows behind t_steps are never loaded (a branch on `live`, not a multiply by zero: they may hold NaN); a
+//     tile no lane reaches is skipped unless eps is asked for.
+//   * eps [t_steps][NA][ld] (optional): the z of every live row, exact zeros elsewhere, ordinary vector stores.
+//   * d_std_lane [NA][ld] (optional): every lane's own sum, a plain register sum in increasing t.  A wave's run of tiles need not
+//     hold all steps of a lane group, so this is a second loop of the same launch -- wave gw takes lane groups gw, gw + waves, ..
+//     and walks t = 0 .. L - 1 with the same draws; lanes >= n have L = 0 and store 0.
+//   * Deterministic, no atomics: wave_sum_to_lane63 per action row, the four waves' sums into LDS, one thread per action row adds
+//     them in wave order into row blockIdx.x of the workspace [n_wg][NA]; k_fnn_param_reduce then adds the rows in its fixed order
+//     through an identity map.  The grid depends on (ld, t_steps, device) only.
+// (NA: the family's action dimensions, which makes this a template, so the translation unit that launches it is the one that holds it.)
+constexpr int NSG_WAVES = 4;
+struct NoiseRows {
+    const uint32_t* done;    // Dev::traj_done
+    const uint32_t* ep_idx;  // Dev::ep_idx
+    uint32_t idx0;           // Dev::idx0
+    int n, ld;
+};
+// the lane's length: the first done bit among rows 0 .. t_steps - 1 (the sweeps' and k_fnn_param_grad's loop), 0 for lanes >= n
+__device__ __forceinline__ int lane_length(const uint32_t* done, size_t ld, int n, int i, int t_steps) {
+    int L = 0;
+    if (i < n) {
+        L = t_steps;
+        for (int w = 0; w * 32 < t_steps; ++w) {
+            uint32_t m = done[(size_t)w * ld + i];
+            const int rem = t_steps - w * 32;
+            if (rem < 32) m &= (1u << rem) - 1u;
+            if (m) {
+                L = w * 32 + __ffs((int)m);
+                break;
+            }
+        }
+    }
+    return L;
+}
+// NormalActNoiseExplStrat's draw of env index `env`, episode epi, step counter `step`: the statements of k_rollout_fnn / _rnn / _lin
+__device__ __forceinline__ void noise_draw(uint64_t noise_seed, uint32_t env, uint32_t epi, int step, float* z) {
+    uint4 b = Rng::philox(noise_seed, env, RNG_POLICY_NOISE, ((uint64_t)epi << 32) | (uint32_t)step);
+    Rng::box_muller(b.x, b.y, z[0], z[1]);
+}
+template <int NA>
+__global__ __launch_bounds__(64 * NSG_WAVES) void k_noise_std_grad(NoiseRows R, uint64_t noise_seed, const float* abar, int t_steps,
+                                                                   float* part, float* d_std_lane, float* eps) {
+    static_assert(NA >= 1 && NA <= 2 && NA <= MAXA, "one Philox block serves z[0] and z[1]");
+    __shared__ float l_sum[NSG_WAVES][NA];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    float acc[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) acc[j] = 0.f;
+
+    // ---- the wave's run of tiles: tile = lane group * t_steps + step
+    const size_t ld = (size_t)R.ld;
+    const int groups = R.ld / 64;
+    const int tiles = groups * t_steps;
+    const int n_waves = (int)gridDim.x * NSG_WAVES;
+    const int chunk = (tiles + n_waves - 1) / n_waves;
+    const int gw = (int)blockIdx.x * NSG_WAVES + wave;
+    const long long first = (long long)gw * chunk;
+    const int tile0 = first < tiles ? (int)first : tiles;
+    const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
+    int g_of_L = -1, L = 0;
+    uint32_t epi = 0u;
+    if (part || eps) {
+        for (int tile = tile0; tile < tile1; ++tile) {
+            const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform
+            const int i = g * 64 + lane;
+            if (g != g_of_L) {
+                g_of_L = g;
+                L = lane_length(R.done, ld, R.n, i, t_steps);
+                epi = i < R.n ? R.ep_idx[i] : 0u;
+            }
+            const bool live = t < L;
+            if (!eps && __ballot(live) == 0ull) continue;  // no lane of the tile reaches step t: nothing is drawn or loaded
+            float z[2] = {0.f, 0.f};
+            if (live) {  // t >= L, lane >= n: neither drawn nor loaded
+                noise_draw(noise_seed, R.idx0 + (uint32_t)i, epi, t, z);
+                if (part) {
+#pragma unroll
+                    for (int j = 0; j < NA; ++j) acc[j] = fmaf(abar[((size_t)t * NA + j) * ld + i], z[j], acc[j]);
+                }
+            }
+            if (eps) {
+#pragma unroll
+                for (int j = 0; j < NA; ++j) eps[((size_t)t * NA + j) * ld + i] = z[j];
+            }
+        }
+    }
+    // ---- every lane's own sum, in increasing t: lane groups gw, gw + waves, ..
+    if (d_std_lane) {
+        for (int g = gw; g < groups; g += n_waves) {
+            const int i = g * 64 + lane;
+            const int Li = lane_length(R.done, ld, R.n, i, t_steps);
+            const uint32_t ep = i < R.n ? R.ep_idx[i] : 0u;
+            float la[NA];
+#pragma unroll
+            for (int j = 0; j < NA; ++j) la[j] = 0.f;
+            for (int t = 0; t < Li; ++t) {
+                float z[2];
+                noise_draw(noise_seed, R.idx0 + (uint32_t)i, ep, t, z);
+#pragma unroll
+                for (int j = 0; j < NA; ++j) la[j] = fmaf(abar[((size_t)t * NA + j) * ld + i], z[j], la[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < NA; ++j) d_std_lane[(size_t)j * ld + i] = la[j];
+        }
+    }
+    // ---- the wave's sums, the four waves in wave order, the workgroup's row of the workspace
+    if (part) {  // (uniform over the launch)
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const float s = wave_sum_to_lane63(acc[j]);
+            if (lane == 63) l_sum[wave][j] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < NA) {
+            float s = l_sum[0][threadIdx.x];
+            for (int w = 1; w < NSG_WAVES; ++w) s += l_sum[w][threadIdx.x];
+            part[(size_t)blockIdx.x * NA + threadIdx.x] = s;
+        }
+    }
+}
+
 // --------------------------------------------------------------------- reverse-mode sweep with a recurrent policy in the loop
 // vs_rollout_vjp_rnn: k_rollout_vjp for rollouts that k_rollout_rnn recorded -- (a_t, p_{t+1}) = F(x_t, p_t) + (n_t, 0) with the
 // handle's recurrent policy (Rnn: the same packed blocks and observation view), p the packed hidden state [hs] and n_t constant.  Two
@@ -5083,6 +5224,9 @@ struct vs_env {
         float* part = nullptr;    // the workgroups' partial vectors [wgs][packed size], allocated on first use and grown, never shrunk
         int* map = nullptr;       // pol_map on the device, uploaded on first use
         int wgs = 0;
+        float* npart = nullptr;   // vs_noise_std_grad: its workgroups' rows [nwgs][A], allocated on first use and grown, never shrunk
+        int* nmap = nullptr;      // ... and its identity map [A]
+        int nwgs = 0;
     } pg;
     vs::Lin lin{};                // vs_set_policy_linear: the linear policy vs_step_policy evaluates (lin.w == nullptr: none)
     vs::Play play{};              // vs_set_policy_playback / vs_set_rollout_target: the tables vs_step_policy replays (play.act == nullptr: none)

@@ -277,7 +277,27 @@ class _ClosedLoopRollout(_RecordedBatches):
             return torch.autograd.grad(mean, list(self._mean.parameters()),
                                        grad_outputs=abar.reshape(N * T, -1).to(device=mean.device, dtype=mean.dtype))
 
-    def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0):
+    def _check_noise_std(self, noise_std):
+        """noise_std= of a call as a float32 tensor [A] (a scalar is broadcast: its gradient is the sum over the entries)"""
+        A = self._dims()[0]
+        if not hasattr(noise_std, "dim"):
+            raise TypeErr(msg="noise_std must be a torch tensor (or None: the exploration strategy's own std, a constant)")
+        if noise_std.dtype != torch.float32:
+            raise TypeErr(msg=f"noise_std must be a float32 tensor, got {noise_std.dtype}")
+        if noise_std.dim() > 1 or (noise_std.dim() == 1 and noise_std.shape[0] != A):
+            raise ShapeErr(msg=f"noise_std must be [{A}] or a scalar, got shape {tuple(noise_std.shape)}")
+        std = noise_std.expand(A)
+        if not bool((std.detach() >= 0).all()):
+            raise ValueErr(msg=f"noise_std must be >= 0, got {std.detach().cpu().tolist()}")
+        return std
+
+    def __call__(self, init_states, T, domain_params=None, names: Optional[Sequence[str]] = None, noise_seed: int = 0,
+                 noise_std=None):
+        """noise_std: None -- the std of the NormalActNoiseExplStrat around the policy (none: no noise), a constant of the graph;
+        or a float32 tensor [A] (a scalar is broadcast): the recording launch adds noise_std * eps_t with these values, eps_t keyed
+        by noise_seed, and obs, rew and act carry gradients to it -- a_t = mean_t + noise_std * eps_t, reparameterised: one
+        noise_std_grad per batch straight on the sweep's action adjoints (vs_noise_std_grad), under either param_pass; rollout n
+        then draws the noise of env index n whatever batch_lanes is.  Entries below 0 raise ValueErr, another shape ShapeErr."""
         _, S, _ = self._dims()
         if not hasattr(init_states, "dim"):
             raise TypeErr(msg="init_states must be a torch tensor")
@@ -291,18 +311,24 @@ class _ClosedLoopRollout(_RecordedBatches):
             raise ShapeErr(msg=f"domain_params needs one row per rollout ({N}), got {params.shape[0]}")
         if not init_states.is_cuda or init_states.dtype != torch.float32:
             raise TypeErr(msg="init_states must be a float32 tensor on the GPU")
-        noise_std = self._noise_std()                                # (the std may have been updated since the constructor)
+        std = None if noise_std is None else self._check_noise_std(noise_std)
+        if std is None:
+            noise_std = self._noise_std()                            # (the std may have been updated since the constructor)
+        else:
+            noise_std = std.detach().cpu().numpy()                   # (the values the recording launch adds the noise with)
         self._calls += 1
-        setup = (self, self._calls, params, int(T), noise_std, int(noise_seed))
-        obs, rew, act, lengths = _PolicyRolloutFn.apply(setup, init_states, *self._mean.parameters())
+        # with noise_std= the noise of rollout n is keyed by n itself, whatever the batches are (the index offset of a batch's handle)
+        setup = (self, self._calls, params, int(T), noise_std, int(noise_seed), std is not None)
+        obs, rew, act, lengths = _PolicyRolloutFn.apply(setup, std, init_states, *self._mean.parameters())
         return obs, rew, act, lengths
 
     def _record(self, b, setup, n0, n1, init_states, weights):
         """the recording closed-loop launch of one batch (rollouts n0 .. n1 - 1) on its handle; a handle that still holds these
         records is left alone"""
-        _, call, params, T, noise_std, noise_seed = setup
+        _, call, params, T, noise_std, noise_seed, by_index = setup
 
         def launch(v):
+            v.set_index_offset(n0 if by_index else 0)
             v.set_params(params[n0:n1])
             self._set_policy(v, weights, noise_std)
             v.reset(init_state=init_states[n0:n1].detach().cpu().numpy())
@@ -333,8 +359,9 @@ class _ClosedLoopRollout(_RecordedBatches):
         obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
         return obs, rew * inside, act * inside[:, :, None], lengths
 
-    def _backward(self, setup, init_states, weights, grad_obs, grad_rew, grad_act):
-        """(gradients of the policy's parameters, d init_states)"""
+    def _backward(self, setup, init_states, weights, grad_obs, grad_rew, grad_act, want_std=False):
+        """(gradients of the policy's parameters, d init_states, d noise_std [A] or None); want_std: the call's noise_std= asks for
+        its gradient -- one noise_std_grad per batch on the sweep's action adjoints, the first batch writes, later batches add"""
         A, S, O = self._dims()
         N, T, dev = init_states.shape[0], setup[3], init_states.device
         kernel = self.param_pass == "kernel"
@@ -342,7 +369,7 @@ class _ClosedLoopRollout(_RecordedBatches):
         abar = torch.empty(N, T, A, dtype=torch.float32, device=dev) if rows else None
         seen = torch.empty(N, T, O, dtype=torch.float32, device=dev) if rows else None
         d_init = torch.empty(N, S, dtype=torch.float32, device=dev)
-        flat, kept = None, []
+        flat, kept, d_std = None, [], None
         for b, (n0, n1) in enumerate(self._batches(N)):
             n = n1 - n0
             v = self._record(b, setup, n0, n1, init_states, weights)
@@ -357,13 +384,15 @@ class _ClosedLoopRollout(_RecordedBatches):
                     flat = self._device_pass(v, T, da, more, out=flat, accumulate=flat is not None)
                 else:
                     kept.append(self._keep(v, T, n, more))
+                if want_std:
+                    d_std = v.noise_std_grad(T, setup[5], da, out=d_std, accumulate=d_std is not None)
         if not kernel:
-            return self._param_grads(seen, abar, kept), d_init
+            return self._param_grads(seen, abar, kept), d_init, d_std
         grads, at = [], 0
         for p in self._mean.parameters():  # parameters_to_vector's order
             grads.append(flat[at:at + p.numel()].view_as(p).to(p.device))  # (as the torch pass: on the parameter's device)
             at += p.numel()
-        return tuple(grads), d_init
+        return tuple(grads), d_init, d_std
 
 
 class DifferentiablePolicyRollout(_ClosedLoopRollout):
@@ -375,7 +404,8 @@ class DifferentiablePolicyRollout(_ClosedLoopRollout):
     obs [N, T + 1, O], rew [N, T], act [N, T, A] (the raw policy actions, exploration noise included) and lengths [N] (int64);
     rows behind a rollout's end are 0.  obs, rew and act carry gradients to init_states and to policy.parameters() -- through the
     dynamics AND through the policy's dependence on the observations.  The exploration noise (keyed by noise_seed) is a constant
-    of the graph: its std gets no gradient; domain_params get none either.
+    of the graph, and so is the strategy's std -- unless the call hands the std over as a tensor (noise_std=, see __call__ of
+    _ClosedLoopRollout): then it gets its gradient from vs_noise_std_grad; domain_params get none.
     Forward: set_policy_linear from the module's current weights, reset(init_state), one recording step_policy(T).  Backward: one
     rollout_vjp_policy per batch for the action adjoints and d init_states, and the weight gradient by param_pass:
       "torch"   (the default) ONE batched pass of the policy over the recorded [N T] observations;
@@ -560,10 +590,12 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
 
 class _PolicyRolloutFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, setup, init_states, *params):
+    def forward(ctx, setup, noise_std, init_states, *params):
+        # noise_std [A] or None: its values are in setup already (the recording launch's); the tensor only ties the graph to it
         roll = setup[0]
         obs, rew, act, lengths = roll._forward(setup, init_states.detach(), [p.detach() for p in params])
         ctx.setup = setup
+        ctx.std_device = None if noise_std is None else noise_std.device
         ctx.save_for_backward(init_states, *params)
         ctx.mark_non_differentiable(lengths)
         return obs, rew, act, lengths
@@ -571,6 +603,7 @@ class _PolicyRolloutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_obs, grad_rew, grad_act, _grad_lengths):
         init_states, *params = ctx.saved_tensors
-        d_params, d_init = ctx.setup[0]._backward(ctx.setup, init_states.detach(), [p.detach() for p in params], grad_obs, grad_rew,
-                                                  grad_act)
-        return (None, d_init) + tuple(d_params)
+        want_std = ctx.std_device is not None and ctx.needs_input_grad[1]
+        d_params, d_init, d_std = ctx.setup[0]._backward(ctx.setup, init_states.detach(), [p.detach() for p in params], grad_obs,
+                                                         grad_rew, grad_act, want_std)
+        return (None, d_std.to(ctx.std_device) if want_std else None, d_init) + tuple(d_params)

@@ -921,9 +921,10 @@ class VecSimEnv:
         self._check(getattr(self._lib, entry)(self._h, T, *ptrs, *(C.c_void_p(x.data_ptr()) for x in res)), entry)
         return res
 
-    def _param_grad(self, entry, t_steps, inputs, n_params, out, accumulate):
+    def _param_grad(self, entry, t_steps, inputs, n_params, out, accumulate, call=None):
         """the parameter-gradient pass `entry` (vs_fnn_param_grad / vs_rnn_param_grad / vs_lin_param_grad) on its inputs [(name, tensor, width)], each
-        a contiguous float32 device tensor [t_steps, width, ld]; returns the flat gradient [n_params]: `out`, or a new tensor"""
+        a contiguous float32 device tensor [t_steps, width, ld]; returns the flat gradient [n_params]: `out`, or a new tensor.
+        call: how an entry point with another argument list (vs_noise_std_grad) is called with the checked arguments"""
         import torch
 
         T = int(t_steps)
@@ -942,8 +943,9 @@ class VecSimEnv:
             raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
         elif tuple(out.shape) != (n_params,):
             raise ShapeErr(msg=f"out must be {(n_params,)}, got {tuple(out.shape)}")
-        self._check(getattr(self._lib, entry)(self._h, T, *(C.c_void_p(x.data_ptr()) for _, x, _ in inputs),
-                                              C.c_void_p(out.data_ptr()), n_params, int(bool(accumulate))), entry)
+        call = call or (lambda fn, *args: fn(*args))
+        self._check(call(getattr(self._lib, entry), self._h, T, *(C.c_void_p(x.data_ptr()) for _, x, _ in inputs),
+                         C.c_void_p(out.data_ptr()), n_params, int(bool(accumulate))), entry)
         return out
 
     def rollout_vjp_policy(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
@@ -1012,6 +1014,40 @@ class VecSimEnv:
             raise ValueErr(msg="no recurrent policy set (set_policy_rnn)")
         return self._param_grad("vs_rnn_param_grad", t_steps, (("abar", abar, self.dims["A"]), ("d_hid", d_hid, Hs)),
                                 self._rnn_n_params, out, accumulate)
+
+    def noise_std_grad(self, t_steps, noise_seed, abar, out=None, accumulate=False, per_lane=False):
+        """The gradient of the exploration noise's std that goes with the three closed-loop sweeps, in one device pass
+        (vs_noise_std_grad): a_t = mean_t + std * eps_t, so d Phi / d std[j] = sum over the rows t < L of the lanes < n_envs of
+        abar[t][j] eps[t][j], eps regenerated bit for bit from (noise_seed, lane, episode, step) -- the noise a recording
+        step_policy(noise_seed=noise_seed) from a reset adds (with noise_std = 0 on the handle: would add).  abar [t_steps, A, ld]
+        is the sweep's d_act as returned (lanes last); what it holds behind a lane's end and at lanes >= n_envs is never read.
+        Returns the float32 gradient [A] on the handle's device: a new tensor, or `out` [A], to which accumulate=True adds
+        instead of overwriting; with per_lane=True also every lane's own sum [A, ld] (zeros at lanes >= n_envs).
+        Deterministic: two calls on the same inputs return the same bits."""
+        import torch
+
+        A = self.dims["A"]
+        lane = None
+        if per_lane:
+            lane = torch.empty(A, self.ld, dtype=torch.float32, device=f"cuda:{self.device}")
+        g = self._param_grad("vs_noise_std_grad", t_steps, (("abar", abar, A),), A, out, accumulate,
+                             call=lambda fn, h, T, ab, o, n, acc: fn(h, T, int(noise_seed) & (2 ** 64 - 1), ab, o, acc,
+                                                                     None if lane is None else C.c_void_p(lane.data_ptr()), None))
+        return (g, lane) if per_lane else g
+
+    def policy_noise(self, t_steps, noise_seed):
+        """eps [t_steps, A, ld]: the standard-normal draws that a recording step_policy(noise_seed=noise_seed) from a reset
+        multiplies by the policy's noise_std, regenerated by vs_noise_std_grad for the lanes' current episode; exact zeros
+        behind a lane's end (t >= L) and at lanes >= n_envs."""
+        import torch
+
+        T = int(t_steps)
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        eps = torch.empty(T, self.dims["A"], self.ld, dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self._lib.vs_noise_std_grad(self._h, T, int(noise_seed) & (2 ** 64 - 1), None, None, 0, None,
+                                                C.c_void_p(eps.data_ptr())), "vs_noise_std_grad")
+        return eps
 
     def sync(self):
         self._check(self._lib.vs_sync(self._h), "vs_sync")
