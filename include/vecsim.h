@@ -597,6 +597,39 @@ int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float
  * Refused with nothing written: everything vs_rollout_vjp_rnn refuses, with the same codes; NULL abar, d_hid or d_params, n_params
  * other than the policy's parameter count, more than 2^31 - 1 tiles of 64 lanes x one step (VS_ERR_ARG). */
 int vs_rnn_param_grad(vs_handle h, int t_steps, const float* abar, const float* d_hid, float* d_params, int64_t n_params, int accumulate);
+/* The closed-loop sweep for a handle with a policy POPULATION (vs_set_policy_population) of linear policies or of feed-forward
+ * networks of one or two hidden layers; it dispatches on the policy slot.  Every lane's sweep runs with the weights of the set its
+ * aligned group of 64 lanes names -- the statements of vs_rollout_vjp_policy / vs_rollout_vjp_fnn on that set's packed vector.
+ * Arguments, layouts (ld = vs_ld(h)), the NULL-is-zero rule of the cotangents, the stream and "writes nothing of the handle" are
+ * vs_rollout_vjp_policy's.  The lanes of an inert group (set -1) have L = 0 whatever their done bits hold, as vs_rollout_lengths has
+ * it: zero rows of d_act, a zero d_init, no record and no cotangent read.
+ * Refused with nothing written: everything vs_rollout_vjp refuses, with the same codes; no population on the handle, a recurrent or
+ * playback policy (or none), a network of more than two hidden layers (VS_ERR_STATE).  The single-policy sweeps keep refusing a
+ * handle with a population; a population of recurrent policies has no sweep. */
+int vs_rollout_vjp_pop(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, float* d_act, float* d_init);
+/* The parameter gradients that vs_rollout_vjp_pop leaves to the caller, one row per member, as one device pass over the same records:
+ *     d_params[s][q] = sum over the rows t < L of the lanes i < n_envs whose group names set s of (d a_t / d theta_q)^T abar_t
+ * with the terms of vs_lin_param_grad (linear) or vs_fnn_param_grad (network, evaluated with set s's weights).
+ *   abar      [t_steps][A][ld]      device: d_act as vs_rollout_vjp_pop returned it.  Rows t >= L, lanes >= n_envs, inert groups and
+ *                                   anything behind row t_steps are never read: they may hold anything, NaN included
+ *   d_params  [n_sets][n_params]    device, out: row s in the order of the parameter vector the policy's setter took (net.weight for a
+ *                                   linear policy, parameters_to_vector for a network).  A set that no group names gets zeros.
+ *                                   accumulate != 0: added to what is there, one fp32 add per entry; an unnamed set's row is left alone
+ * Runs on the handle's stream and writes nothing of the handle.  Deterministic: no atomics; a workgroup serves exactly one set, the
+ * partition of the tile space among the sets and the order of every sum depend on (lane table, t_steps, device) only, so two calls on
+ * the same inputs return the same bits.  The workspace is the policy slot's, the partition tables are kept with the population.
+ * Refused with nothing written: everything vs_rollout_vjp_pop refuses, with the same codes; NULL abar or d_params, n_sets other than
+ * the population's, n_params other than the policy's parameter count, more than 2^31 - 1 tiles of 64 lanes x one step (VS_ERR_ARG). */
+int vs_pop_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int n_sets, int64_t n_params, int accumulate);
+/* The partition vs_pop_param_grad derives for a lane table, on the host alone (no handle, no device): groups [n_groups] is the set of
+ * every aligned group of 64 lanes (-1: inert or past n_envs), per_wg the waves of a workgroup (1 linear, 4 network), cap the grid cap of
+ * the single-policy pass (4 x / 2 x the compute units).  Writes seg [n_sets][2] = {first workgroup, workgroups} of every set and, where
+ * given, wg [n_wg][4] = {first entry of the set, its entries, rank, workgroups of the set} (only if n_wg <= wg_cap) and ent (at most
+ * n_groups entries: the groups that name a set, in stable order by (set, group)).  Returns the number of workgroups, or VS_ERR_ARG
+ * (negative) for a NULL table or seg, counts below 1, a set id outside -1 .. n_sets - 1 or more than 2^31 - 1 tiles. */
+int vs_pop_partition(const int32_t* groups, int n_groups, int n_sets, int t_steps, int per_wg, int64_t cap, int32_t* seg, int32_t* wg,
+                     int wg_cap, int32_t* ent);
 /* The gradient of the exploration noise's std that the three closed-loop sweeps leave out, as one device pass.  The policy kernels
  * form the raw action as a_t = mean_t + noise_std (.) eps_t (NormalActNoiseExplStrat, P/exploration/stochastic_action.py:121-180:
  * the reparameterised sample of Normal(mean, std)), eps_t ~ N(0, 1) keyed by (noise_seed, index offset + lane, episode, step), and

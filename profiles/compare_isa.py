@@ -6,7 +6,8 @@ OLD_OBJ_DIR / NEW_OBJ_DIR are the `build/` object directories of two in-tree bui
 the parent commit and one of the working tree.  Every kernel whose name matches REGEX (default: every kernel) must exist in
 both builds with the same instructions: a kernel of the old build that the new one lacks is MISSING, one that only the new
 build has is NEW.  Addresses, encodings and branch-target labels are dropped (the kernels may sit elsewhere in the code
-object); branch offsets stay.  Names are compared demangled, without the parameter list.  Exits 1 on any difference.
+object); branch offsets stay.  Names are compared demangled, without the parameter list and without the space between two template
+closers (`> >`): two symbols that demangle to the same text are one kernel here.  Exits 1 on any difference.
 A kernel that differs is listed with its registers in both builds (VGPRs of which AGPRs -- vgpr_count of a gfx950 code object
 is the unified total --, SGPRs, VGPR / SGPR spills, scratch and LDS bytes, waves per SIMD = 512 / (VGPRs rounded up to 8), at
 most 8) and marked WORSE if it spills more, gained scratch or lost a wave per SIMD.  The waves are what the registers alone
@@ -45,7 +46,10 @@ def kernels(obj_path):
     dm = codeobj._demangle(names)
     res = {}
     for n, d in zip(names, dm):
-        d = d.replace("void ", "").replace("vs::", "")
+        # A kernel whose template ends in an EMPTY parameter pack is another symbol than the kernel without the pack (its mangled template
+        # arguments gain "JE") and demangles to the same text but for one space: `k<A<0>>` against `k<A<0> >`.  Template closers
+        # are written without that space here, in both builds alike; no C++ name has `> >` anywhere else.
+        d = re.sub(r">\s+(?=>)", ">", d.replace("void ", "").replace("vs::", ""))
         d = re.sub(r"\(.*$", "", d)
         res[d] = (n, out[n])
     return res

@@ -47,6 +47,7 @@ def __getattr__(name):
 
         return getattr(sysid, name)
     if name in ("DifferentiableRollout", "DifferentiablePolicyRollout", "DifferentiableNetRollout", "DifferentiableRecurrentRollout",
+                "DifferentiablePopulationRollout",
                 "discounted_return"):
         from . import diffsim
 

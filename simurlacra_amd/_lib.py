@@ -113,6 +113,9 @@ _SIGNATURES = {
     "vs_lin_param_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int]),
     "vs_noise_std_grad": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.c_int, _P, _P]),
     "vs_rollout_vjp_rnn": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vs_rollout_vjp_pop": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "vs_pop_param_grad": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, C.c_int]),
+    "vs_pop_partition": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int, _P]),
     "vs_set_policy_hidden_record": (C.c_int, [_P, C.c_int]),
     "vs_record_hidden": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int]),
     "vs_set_policy_population": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),

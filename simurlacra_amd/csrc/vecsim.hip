@@ -533,7 +533,9 @@ static int mixed_upload(vs_mixed* m, const float* const* acts, const int64_t* en
 
 // ---- the policy slot of a handle: one in-kernel policy at a time, shared by the setters of the four kinds and vs_destroy
 static int drop_pop(vs_handle h) {
-    if (int rc = dfree(h, h->pop.w, h->pop.wg_set)) return rc;
+    if (int rc = dfree(h, h->pop.w, h->pop.wg_set, h->pp.ent, h->pp.wg, h->pp.seg)) return rc;
+    h->pp.wg_host.clear();
+    h->pp.t_steps = h->pp.n_wg = 0;
     h->pop = Pop{};
     h->pop_sets = 0;
     h->pop_g256 = h->pop_inert = false;
@@ -662,7 +664,7 @@ static int upload_packed(vs_handle h, const char* who, const std::vector<int>& m
 
 extern "C" {
 
-int vs_version(void) { return 320; }
+int vs_version(void) { return 321; }
 
 static int record_width(int t, int mode) {
     const EnvInfo& e = ENV_INFO[t];
@@ -1658,6 +1660,7 @@ int vs_set_policy_population(vs_handle h, const float* params, int64_t n_params,
         return fail(h, VS_ERR_HIP, "vs_set_policy_population: upload / pack", e);
     }
     h->pop = Pop{dw, dwg, stride};
+    h->pp.wg_host = wg;  // (vs_pop_param_grad derives its partition from it)
     h->pop_sets = n_sets;
     h->pop_g256 = g256;
     h->pop_inert = inert;
@@ -1831,6 +1834,22 @@ int vs_rollout_vjp_rnn(vs_handle h, int t_steps, const float* g_rew, const float
     if (int rc = vjp_checks(h, "vs_rollout_vjp_rnn", t_steps, d_act, d_init, rnn_sweep_policy)) return rc;
     VJP_LAUNCH(Launch<E>::rollout_vjp_rnn(h, v, g_act, g_hid_last, d_hid, d_hid0, t_steps));
 }
+// what vs_rollout_vjp_pop and vs_pop_param_grad need of the policy slot: a population of linear policies or of networks of one or two
+// hidden layers (a recurrent policy's parameter pass has its own LDS layout; a playback policy has no parameters)
+static const char* pop_sweep_policy(vs_handle h) {
+    if (h->play.act) return "a playback policy has no parameters to vary";
+    if (h->rnn.w) return "a population of recurrent policies has no sweep (linear and feed-forward policies only)";
+    if (!h->lin.w && !h->fnn.w) return "no linear or feed-forward policy on the handle (vs_set_policy_linear / vs_set_policy_fnn)";
+    if (!h->pop.w) return "no policy population on the handle (vs_set_policy_population)";
+    if (h->fnn.w && h->fnn.n_hidden > 2) return "the sweep takes networks of one or two hidden layers";
+    return nullptr;
+}
+
+int vs_rollout_vjp_pop(vs_handle h, int t_steps, const float* g_rew, const float* g_obs, const float* g_act,
+                       const float* g_state_last, float* d_act, float* d_init) {
+    if (int rc = vjp_checks(h, "vs_rollout_vjp_pop", t_steps, d_act, d_init, pop_sweep_policy)) return rc;
+    VJP_LAUNCH(Launch<E>::rollout_vjp_pop(h, v, g_act, t_steps));
+}
 #undef VJP_LAUNCH
 
 // ---- vs_fnn_param_grad / vs_rnn_param_grad / vs_lin_param_grad: one pass over the records a sweep read, a partial vector per workgroup, then one reduction
@@ -1893,7 +1912,8 @@ int vs_fnn_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
     if (psize != f.off_b[f.n_hidden] + 8 || psize > FNNG_PMAX) return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_fnn's");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
-    auto kern = f.n_hidden == 1 ? k_fnn_param_grad<1> : k_fnn_param_grad<2>;
+    void (*kern)(FnnRows, const float*, Fnn, int, int, float*) = k_fnn_param_grad<1>;  // (the kernel without its population pack)
+    if (f.n_hidden != 1) kern = k_fnn_param_grad<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->pg.part);
     launch_param_reduce(h, n_wg, psize, d_params, accumulate);
     HIPCHK(h, hipGetLastError());
@@ -1915,9 +1935,128 @@ int vs_lin_param_grad(vs_handle h, int t_steps, const float* abar, float* d_para
     if (psize != rows.A * LIN_SLOTS || rows.A > MAXA) return fail(h, VS_ERR_STATE, who, "the packed layout is not vs_set_policy_linear's");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
-    auto kern = rows.A == 1 ? k_lin_param_grad<1> : k_lin_param_grad<2>;
+    void (*kern)(FnnRows, const float*, Lin, int, float*) = k_lin_param_grad<1>;  // (the kernel without its population pack)
+    if (rows.A != 1) kern = k_lin_param_grad<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64), 0, h->stream, rows, abar, h->lin, t_steps, h->pg.part);
     launch_param_reduce(h, n_wg, psize, d_params, accumulate);
+    HIPCHK(h, hipGetLastError());
+    return VS_OK;
+}
+
+// ---- vs_pop_param_grad: the tile space partitioned by set of the population
+// From the table's groups (set of every aligned group of 64 lanes, -1: inert or past n_envs):
+//   ent   the groups that name a set, in stable order by (set, group): set s owns cnt_s consecutive entries
+//   seg   per set {first workgroup, workgroups k_s}
+//   wg    per workgroup {first entry of its set, cnt_s, rank among the set's workgroups, k_s}
+// A set has cnt_s * t_steps tiles and `per_wg` tiles keep the waves of one workgroup busy, so it WANTS ceil(tiles_s / per_wg) workgroups.
+// While all wants fit under `cap` (the grid cap of the single-policy pass) every set gets what it wants; beyond, set s gets
+// floor(cap * tiles_s / tiles) of them, at least 1 and at most what it wants: shares in proportion to the sets' tiles, every named set
+// served, at most n_sets workgroups above the cap.  A function of (table, t_steps, per_wg, cap) only.  tests/population_vjp_cases.py
+// mirrors it line by line.
+static int pop_partition(const std::vector<int>& groups, int n_sets, int t_steps, int per_wg, int64_t cap, std::vector<int>& ent,
+                         std::vector<int>& wg, std::vector<int>& seg) {
+    std::vector<int64_t> cnt((size_t)n_sets, 0), first((size_t)n_sets, 0);
+    for (int s : groups)
+        if (s >= 0) ++cnt[(size_t)s];
+    int64_t n_ent = 0;
+    for (int s = 0; s < n_sets; ++s) first[(size_t)s] = n_ent, n_ent += cnt[(size_t)s];
+    ent.assign((size_t)n_ent, 0);
+    std::vector<int64_t> at = first;
+    for (size_t g = 0; g < groups.size(); ++g)
+        if (groups[g] >= 0) ent[(size_t)at[(size_t)groups[g]]++] = (int)g;
+    const int64_t tiles = n_ent * t_steps;
+    int64_t want = 0;
+    for (int s = 0; s < n_sets; ++s) want += (cnt[(size_t)s] * t_steps + per_wg - 1) / per_wg;
+    seg.assign(2 * (size_t)n_sets, 0);
+    wg.clear();
+    int64_t n_wg = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const int64_t ts = cnt[(size_t)s] * t_steps, ws = (ts + per_wg - 1) / per_wg;
+        int64_t k = ws;
+        if (want > cap && ts > 0) k = std::min(ws, std::max<int64_t>(1, cap * ts / tiles));
+        seg[2 * (size_t)s] = (int)n_wg, seg[2 * (size_t)s + 1] = (int)k;
+        for (int64_t r = 0; r < k; ++r) {
+            const int row[4] = {(int)first[(size_t)s], (int)cnt[(size_t)s], (int)r, (int)k};
+            wg.insert(wg.end(), row, row + 4);
+        }
+        n_wg += k;
+    }
+    return (int)n_wg;
+}
+
+int vs_pop_partition(const int32_t* groups, int n_groups, int n_sets, int t_steps, int per_wg, int64_t cap, int32_t* seg, int32_t* wg,
+                     int wg_cap, int32_t* ent) {
+    if (!groups || n_groups < 1 || n_sets < 1 || t_steps < 1 || per_wg < 1 || cap < 1 || !seg) return VS_ERR_ARG;
+    if ((int64_t)n_groups * t_steps > INT_MAX) return VS_ERR_ARG;
+    for (int g = 0; g < n_groups; ++g)
+        if (groups[g] < -1 || groups[g] >= n_sets) return VS_ERR_ARG;
+    std::vector<int> e, w, s;
+    const int n_wg = pop_partition(std::vector<int>(groups, groups + n_groups), n_sets, t_steps, per_wg, cap, e, w, s);
+    std::copy(s.begin(), s.end(), seg);
+    if (wg && n_wg <= wg_cap) std::copy(w.begin(), w.end(), wg);
+    if (ent) std::copy(e.begin(), e.end(), ent);
+    return n_wg;
+}
+
+// the partition for t_steps on the device: rebuilt when t_steps is not the last call's (a pure function: the bits of a result do not
+// depend on what was built before)
+static int pop_partition_upload(vs_handle h, const char* who, int t_steps, int per_wg, int64_t cap) {
+    if (h->pp.t_steps == t_steps) return VS_OK;
+    std::vector<int> ent, wg, seg;
+    const int n_wg = pop_partition(h->pp.wg_host, h->pop_sets, t_steps, per_wg, cap, ent, wg, seg);
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (an earlier call may still read the tables this replaces)
+    if (int rc = dfree(h, h->pp.ent, h->pp.wg, h->pp.seg)) return rc;
+    h->pp.t_steps = h->pp.n_wg = 0;
+    auto up = [&](int*& dst, const std::vector<int>& src) {
+        hipError_t e = hipMalloc((void**)&dst, std::max<size_t>(src.size(), 4) * sizeof(int));
+        if (e == hipSuccess && !src.empty()) e = hipMemcpy(dst, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice);
+        return e;
+    };
+    hipError_t e = up(h->pp.ent, ent);
+    if (e == hipSuccess) e = up(h->pp.wg, wg);
+    if (e == hipSuccess) e = up(h->pp.seg, seg);
+    if (e != hipSuccess) {
+        (void)dfree(h, h->pp.ent, h->pp.wg, h->pp.seg);
+        return fail(h, VS_ERR_HIP, who, "partition upload", e);
+    }
+    h->pp.t_steps = t_steps;
+    h->pp.n_wg = n_wg;
+    return VS_OK;
+}
+
+int vs_pop_param_grad(vs_handle h, int t_steps, const float* abar, float* d_params, int n_sets, int64_t n_params, int accumulate) {
+    const char* who = "vs_pop_param_grad";
+    if (int rc = vjp_checks(h, who, t_steps, abar, d_params, pop_sweep_policy, "NULL handle, abar or d_params")) return rc;
+    if (n_sets != h->pop_sets) return fail(h, VS_ERR_ARG, who, "n_sets is not the population's");
+    FnnRows rows;
+    if (int rc = param_grad_checks(h, who, "policy", t_steps, n_params, rows)) return rc;
+    const int psize = (int)h->pol_map.size();
+    const Fnn& f = h->fnn;
+    if (h->lin.w ? (psize != rows.A * LIN_SLOTS || rows.A > MAXA) : (psize != f.off_b[f.n_hidden] + 8 || psize > FNNG_PMAX))
+        return fail(h, VS_ERR_STATE, who, "the packed layout is not the setter's");
+    HIPCHK(h, hipSetDevice(h->device));
+    // the grid caps of the single-policy passes: one wave per workgroup and four per compute unit (linear), four waves per workgroup
+    // and two per compute unit (network)
+    if (int rc = pop_partition_upload(h, who, t_steps, h->lin.w ? 1 : FNNG_WAVES, (h->lin.w ? 4 : 2) * (int64_t)h->n_cu)) return rc;
+    const int n_wg = h->pp.n_wg;
+    const PopSeg S{h->pop.w, h->pop.stride, h->pop.wg_set, h->pp.ent, (const int4*)h->pp.wg};
+    if (n_wg > 0) {
+        if (int rc = param_grad_workspace(h, who, psize, n_wg)) return rc;
+        if (h->lin.w) {
+            void (*kern)(FnnRows, const float*, Lin, int, float*, PopSeg) = k_lin_param_grad<1, PopSeg>;
+            if (rows.A != 1) kern = k_lin_param_grad<2, PopSeg>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64), 0, h->stream, rows, abar, h->lin, t_steps, h->pg.part, S);
+        } else {
+            void (*kern)(FnnRows, const float*, Fnn, int, int, float*, PopSeg) = k_fnn_param_grad<1, PopSeg>;
+            if (f.n_hidden != 1) kern = k_fnn_param_grad<2, PopSeg>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(64 * FNNG_WAVES), 0, h->stream, rows, abar, f, t_steps, psize, h->pg.part, S);
+        }
+    } else if (int rc = param_grad_workspace(h, who, psize, 1)) {  // (no set is named: the reduction writes zeros; it needs the map)
+        return rc;
+    }
+    hipLaunchKernelGGL((k_pop_param_reduce<4>), dim3((unsigned)((psize + BLOCK - 1) / BLOCK), (unsigned)std::min(n_sets, 65535)), dim3(BLOCK),
+                       0, h->stream, (const float*)h->pg.part, (const int2*)h->pp.seg, n_sets, psize, (const int*)h->pg.map, d_params,
+                       (long long)n_params, accumulate != 0 ? 1 : 0);
     HIPCHK(h, hipGetLastError());
     return VS_OK;
 }

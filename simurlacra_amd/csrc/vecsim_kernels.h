@@ -1021,6 +1021,16 @@ struct Pop {
     const int* wg_set;  // [ld / 64]
     int64_t stride;
 };
+// the one argument of a trailing kernel-parameter pack (the reverse-mode kernels take their population as `POP... pop`: with an empty
+// pack the kernel has the name, the signature and the kernel-argument layout it had before it knew of populations)
+template <class T>
+__device__ __forceinline__ const T& only_of(const T& x) { return x; }
+// the pack is empty or exactly one T
+template <class T, class... P>
+constexpr bool pack_is_none_or(std::integral_constant<int, sizeof...(P)> = {}) {
+    if constexpr (sizeof...(P) == 0) return true;
+    else return sizeof...(P) == 1 && (std::is_same<T, P>::value && ...);
+}
 template <class E, bool AR, int REC, int NHID, int NE, bool MF = false, bool POP = false>
 __global__ __launch_bounds__(64 * fnn_waves(NHID)) void k_rollout_fnn(Task T, Dev d, Fnn P, int k_steps, uint64_t reset_seed,
                                                                       uint64_t noise_seed, Pop pop) {
@@ -2566,11 +2576,30 @@ __global__ __launch_bounds__(64) void k_rollout_vjp_dp(Task T, Dev d, Vjp V, Vjp
 //     the observation rows directly.  gx goes back to observation rows through obs_idx by wave-uniform selects: the next gpol.
 //   * After t = 0: vjp_observe with g_obs[0] + gpol, d_init = lambda.  Rows t >= L of d_act and lanes >= n are 0 and read no cotangent.
 // With a stack whose features are all constant gpol stays +0 and every float operation is k_rollout_vjp's: the same bits.
-template <class E>
-__global__ __launch_bounds__(64) void k_rollout_vjp_lin(Task T, Dev d, Vjp V, const float* g_act, Lin P, int t_steps) {
+// POP (vs_rollout_vjp_pop): the workgroup -- one aligned group of 64 lanes -- takes the weights of its set of
+// the population as k_rollout_lin does; an inert group (set -1) has L = 0 on every lane whatever its done bits hold: it writes its
+// zero rows of d_act and its zero d_init and leaves before the loop, having read no record and no cotangent.  The flag is the
+// trailing parameter pack: empty, the kernel has the name, the arguments and, instruction for instruction, the code it had before.
+template <class E, class... POPT>
+__global__ __launch_bounds__(64) void k_rollout_vjp_lin(Task T, Dev d, Vjp V, const float* g_act, Lin P, int t_steps, POPT... popt) {
+    static_assert(pack_is_none_or<Pop, POPT...>(), "the population pack is empty or one Pop");
+    constexpr bool POP = sizeof...(POPT) > 0;
     typedef const __attribute__((address_space(4))) float* cfp;  // wave-uniform reads: scalar loads
     constexpr int NS = E::S + E::H, NI = NS + E::A;
-    const cfp W = (cfp)P.w;
+    const float* w0 = P.w;
+    if constexpr (POP) {
+        const Pop& pop = only_of(popt...);
+        const int set = __builtin_amdgcn_readfirstlane(pop.wg_set[blockIdx.x]);  // (uniform by construction)
+        if (set < 0) {
+            const size_t at = (size_t)blockIdx.x * 64 + threadIdx.x;
+            for (int r = 0; r < t_steps * E::A; ++r) V.d_act[(size_t)r * d.ld + at] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) V.d_init[(size_t)k * d.ld + at] = 0.f;
+            return;
+        }
+        w0 = pop.w + (size_t)set * (size_t)pop.stride;
+    }
+    const cfp W = (cfp)w0;
     const unsigned kinds = P.kinds;
     const int i = blockIdx.x * 64 + threadIdx.x;
     const size_t ld = d.ld;
@@ -2794,8 +2823,13 @@ __device__ __forceinline__ float fnn_row_dot(const float* w, const float* row) {
     }
     return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
-template <class E, int NHID>
-__global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev d, Vjp V, const float* g_act, Fnn P, int t_steps) {
+// POP (vs_rollout_vjp_pop): as in the linear sweep -- the workgroup's set is the base of every weight read of
+// its network waves; in an inert group the env wave writes the zeros and all five waves leave before the first barrier.
+template <class E, int NHID, class... POPT>
+__global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev d, Vjp V, const float* g_act, Fnn P, int t_steps,
+                                                                     POPT... popt) {
+    static_assert(pack_is_none_or<Pop, POPT...>(), "the population pack is empty or one Pop");
+    constexpr bool POP = sizeof...(POPT) > 0;
     static_assert(NHID == 1 || NHID == 2, "hidden layers: deeper networks' weights and transposes do not fit the registers");
     static_assert(E::O <= MAXO && MAXO + 1 <= FNN_XS, "input row");
     constexpr int NS = E::S + E::H, NI = NS + E::A;
@@ -2805,6 +2839,20 @@ __global__ __launch_bounds__(64 * FNNB_WAVES) void k_rollout_vjp_fnn(Task T, Dev
     __shared__ __attribute__((aligned(16))) float l_h[NHID > 1 ? 64 * FNN_W : 4];  // y_1, then delta_2: [env][unit]
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
+    if constexpr (POP) {
+        const Pop& pop = only_of(popt...);
+        const int set = __builtin_amdgcn_readfirstlane(pop.wg_set[blockIdx.x]);  // (uniform by construction)
+        if (set < 0) {
+            if (wave == 0) {
+                const size_t at = (size_t)blockIdx.x * 64 + lane;
+                for (int r = 0; r < t_steps * E::A; ++r) V.d_act[(size_t)r * d.ld + at] = 0.f;
+#pragma unroll
+                for (int k = 0; k < E::S + E::H; ++k) V.d_init[(size_t)k * d.ld + at] = 0.f;
+            }
+            return;
+        }
+        P.w = pop.w + (size_t)set * (size_t)pop.stride;
+    }
 
     if (wave > 0) {
         // ================================================================================ network waves: lane = hidden unit
@@ -3019,9 +3067,25 @@ struct FnnRows {            // the records k_fnn_param_grad reads
     int F, O, A;            // floats per record row, observation and action width of the family
     int n, ld;
 };
-template <int NHID>
+// vs_pop_param_grad: the same pass with the tile space partitioned BY SET of a population, so that a workgroup serves exactly one set
+// and its partial vector belongs to one row of the result.  The host derives, from the lane table vs_set_policy_population validated,
+//   ent [n_ent]        the lane groups that name a set, in stable order by (set, group): set s owns entries first_s .. first_s + cnt_s - 1
+//   wg  [n_wg] int4    per workgroup: {first_s, cnt_s, its rank r among the k_s workgroups of its set, k_s}; the workgroups of a set are
+//                      consecutive rows of the workspace
+// and workgroup (r of k_s) walks its contiguous run of the set's cnt_s * t_steps tiles (entry major, so L is still once per group), exactly
+// as the single-policy kernel walks its run of all tiles.  SEG is the trailing parameter pack (PopSeg, or nothing: the kernel as it was).
+struct PopSeg {
+    const float* w;      // Pop::w, Pop::stride, Pop::wg_set
+    int64_t stride;
+    const int* wg_set;
+    const int* ent;
+    const int4* wg;
+};
+template <int NHID, class... SEGT>
 __global__ __launch_bounds__(64 * FNNG_WAVES) void k_fnn_param_grad(FnnRows R, const float* abar, Fnn P, int t_steps, int psize,
-                                                                    float* part) {
+                                                                    float* part, SEGT... segt) {
+    static_assert(pack_is_none_or<PopSeg, SEGT...>(), "the population pack is empty or one PopSeg");
+    constexpr bool SEG = sizeof...(SEGT) > 0;
     static_assert(NHID == 1 || NHID == 2, "hidden layers");
     __shared__ __attribute__((aligned(16))) float l_x[FNNG_WAVES][64 * FNN_XS];  // the tile's input rows: [env][input]
     __shared__ float l_ab[FNNG_WAVES][64 * MAXA];                               // abar: [env][A]
@@ -3031,6 +3095,15 @@ __global__ __launch_bounds__(64 * FNNG_WAVES) void k_fnn_param_grad(FnnRows R, c
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const int A = R.A, in_dim = P.in_dim;
+    int seg_e0 = 0, seg_ne = 0, seg_r = 0, seg_k = 1;  // SEG: the workgroup's set (entries, rank, workgroups of the set)
+    if constexpr (SEG) {
+        const PopSeg& S = only_of(segt...);
+        const int4 q = S.wg[blockIdx.x];
+        seg_e0 = __builtin_amdgcn_readfirstlane(q.x), seg_ne = __builtin_amdgcn_readfirstlane(q.y);
+        seg_r = __builtin_amdgcn_readfirstlane(q.z), seg_k = __builtin_amdgcn_readfirstlane(q.w);
+        const int set = __builtin_amdgcn_readfirstlane(S.wg_set[S.ent[seg_e0]]);  // (>= 0: only named sets have workgroups)
+        P.w = S.w + (size_t)set * (size_t)S.stride;
+    }
 
     float w1[FNN_XS], wh[NHID > 1 ? FNN_W : 1], wt[NHID > 1 ? FNN_W : 1], bh[NHID], wo[MAXA], bo[MAXA];
 #pragma unroll
@@ -3059,18 +3132,24 @@ __global__ __launch_bounds__(64 * FNNG_WAVES) void k_fnn_param_grad(FnnRows R, c
 
     // ---- the wave's run of tiles: tile = lane group * t_steps + step
     const size_t ld = (size_t)R.ld;
-    const int tiles = (R.ld / 64) * t_steps;
-    const int n_waves = (int)gridDim.x * FNNG_WAVES;
+    const int tiles = (SEG ? seg_ne : R.ld / 64) * t_steps;
+    const int n_waves = (SEG ? seg_k : (int)gridDim.x) * FNNG_WAVES;
     const int chunk = (tiles + n_waves - 1) / n_waves;
-    const int gw = (int)blockIdx.x * FNNG_WAVES + wave;
+    const int gw = (SEG ? seg_r : (int)blockIdx.x) * FNNG_WAVES + wave;
     const long long first = (long long)gw * chunk;
     const int tile0 = first < tiles ? (int)first : tiles;
     const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
     const int NQ = R.F / 4, H2 = (R.F % 4) >= 2 ? 1 : 0;
-    int g_of_L = -1, L = 0;
+    int g_of_L = -1, L = 0, gcur = 0;
     for (int tile = tile0; tile < tile1; ++tile) {
-        const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform
-        const int i = g * 64 + lane;
+        int g = tile / t_steps;  // wave-uniform; SEG: the entry of the set, its lane group below
+        const int t = tile - g * t_steps;
+        if constexpr (SEG) {
+            if (g != g_of_L) gcur = __builtin_amdgcn_readfirstlane(only_of(segt...).ent[seg_e0 + g]);
+        } else {
+            gcur = g;
+        }
+        const int i = gcur * 64 + lane;
         if (g != g_of_L) {
             // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (k_rollout_vjp_fnn's)
             g_of_L = g;
@@ -3245,6 +3324,42 @@ __global__ __launch_bounds__(BLOCK) void k_fnn_param_reduce(const float* part, i
     d_params[q] = accumulate ? d_params[q] + s : s;
 }
 
+// vs_pop_param_grad: the same sum per set of a population -- rows seg[s].x .. seg[s].x + seg[s].y - 1 of the workspace are set s's
+// workgroups, added in the order above into row s of d_params [n_sets][n_params]; a set with no workgroup (no group names it) gets
+// zeros, or is left as it was under `accumulate`.  blockIdx.y strides over the sets.
+template <int NSUM>
+__global__ __launch_bounds__(BLOCK) void k_pop_param_reduce(const float* part, const int2* seg, int n_sets, int psize, const int* map,
+                                                            float* d_params, long long n_params, int accumulate) {
+    const int p = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (p >= psize) return;
+    static_assert(NSUM == 4, "four interleaved partial sums");
+    const int q = map[p];
+    if (q < 0) return;
+    for (int s = (int)blockIdx.y; s < n_sets; s += (int)gridDim.y) {
+        const int2 sg = seg[s];
+        const float* rows = part + (size_t)sg.x * psize;
+        const int n_wg = sg.y;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int w = 0;
+        for (; w + 4 <= n_wg; w += 4) {
+            a0 += rows[(size_t)w * psize + p];
+            a1 += rows[(size_t)(w + 1) * psize + p];
+            a2 += rows[(size_t)(w + 2) * psize + p];
+            a3 += rows[(size_t)(w + 3) * psize + p];
+        }
+        if (w < n_wg) a0 += rows[(size_t)w * psize + p];
+        if (w + 1 < n_wg) a1 += rows[(size_t)(w + 1) * psize + p];
+        if (w + 2 < n_wg) a2 += rows[(size_t)(w + 2) * psize + p];
+        const float sum = (a0 + a1) + (a2 + a3);
+        float* dst = d_params + (size_t)s * (size_t)n_params + q;
+        if (n_wg == 0) {
+            if (!accumulate) *dst = 0.f;
+        } else {
+            *dst = accumulate ? *dst + sum : sum;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ parameter gradients of the linear policy
 // vs_lin_param_grad: what k_rollout_vjp_lin leaves to the caller -- d Phi / d W = sum over the rows (t < L_i, i < n) of
 //     dW[j][q] += abar[t][j][i] phi_q(x_t,i)
@@ -3265,8 +3380,12 @@ __global__ __launch_bounds__(BLOCK) void k_fnn_param_reduce(const float* part, i
 //     written).  The grid depends on (ld, t_steps, device) only.
 // (NA: the family's action dimensions, which makes this a template, so the translation unit that launches it is the one that holds it.)
 constexpr int LING_PITCH = LIN_SLOTS + 1;
-template <int NA>
-__global__ __launch_bounds__(64) void k_lin_param_grad(FnnRows R, const float* abar, Lin P, int t_steps, float* part) {
+// SEG (vs_pop_param_grad): the tile space partitioned by set as in k_fnn_param_grad -- the features do not depend on the weights,
+// so the kernel reads nothing of the population but the partition.
+template <int NA, class... SEGT>
+__global__ __launch_bounds__(64) void k_lin_param_grad(FnnRows R, const float* abar, Lin P, int t_steps, float* part, SEGT... segt) {
+    static_assert(pack_is_none_or<PopSeg, SEGT...>(), "the population pack is empty or one PopSeg");
+    constexpr bool SEG = sizeof...(SEGT) > 0;
     static_assert(NA >= 1 && NA <= MAXA && LIN_SLOTS == 128 && MAXO == 8, "two slots per lane, eight rows per kind");
     __shared__ float l_phi[64 * LING_PITCH];  // the tile's features: [env][slot | 0]
     __shared__ float l_ab[64 * NA];           // abar: [env][NA]
@@ -3290,17 +3409,30 @@ __global__ __launch_bounds__(64) void k_lin_param_grad(FnnRows R, const float* a
 
     // ---- the wave's run of tiles: tile = lane group * t_steps + step
     const size_t ld = (size_t)R.ld;
-    const int tiles = (R.ld / 64) * t_steps;
-    const int chunk = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const long long first = (long long)blockIdx.x * chunk;
+    int seg_e0 = 0, seg_ne = 0, seg_r = 0, seg_k = 1;  // SEG: the workgroup's set (entries, rank, workgroups of the set)
+    if constexpr (SEG) {
+        const int4 q = only_of(segt...).wg[blockIdx.x];
+        seg_e0 = __builtin_amdgcn_readfirstlane(q.x), seg_ne = __builtin_amdgcn_readfirstlane(q.y);
+        seg_r = __builtin_amdgcn_readfirstlane(q.z), seg_k = __builtin_amdgcn_readfirstlane(q.w);
+    }
+    const int tiles = (SEG ? seg_ne : R.ld / 64) * t_steps;
+    const int n_runs = SEG ? seg_k : (int)gridDim.x;
+    const int chunk = (tiles + n_runs - 1) / n_runs;
+    long long first = (long long)blockIdx.x * chunk;
+    if constexpr (SEG) first = (long long)seg_r * chunk;
     const int tile0 = first < tiles ? (int)first : tiles;
     const int tile1 = tiles - tile0 > chunk ? tile0 + chunk : tiles;
     const int NQ = R.F / 4, H2 = (R.F % 4) >= 2 ? 1 : 0;
     float* const prow = l_phi + lane * LING_PITCH;  // phase one: the lane's own row
-    int g_of_L = -1, L = 0;
+    int g_of_L = -1, L = 0, gcur = 0;
     for (int tile = tile0; tile < tile1; ++tile) {
-        const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform
-        const int i = g * 64 + lane;
+        const int g = tile / t_steps, t = tile - g * t_steps;  // wave-uniform; SEG: the entry of the set, its lane group below
+        if constexpr (SEG) {
+            if (g != g_of_L) gcur = __builtin_amdgcn_readfirstlane(only_of(segt...).ent[seg_e0 + g]);
+        } else {
+            gcur = g;
+        }
+        const int i = gcur * 64 + lane;
         if (g != g_of_L) {
             // ---- the lane's length: the first done bit among rows 0 .. t_steps - 1 (k_rollout_vjp_lin's)
             g_of_L = g;
@@ -5238,6 +5370,13 @@ struct vs_env {
     int pop_sets = 0;             // ... number of sets
     bool pop_g256 = false;        // ... every aligned group of 256 lanes names one set (the 256-env shapes are allowed)
     bool pop_inert = false;       // ... some lane of the table is -1
+    struct PopPart {              // vs_pop_param_grad: the partition of the tile space by set, kept with the population (drop_pop)
+        std::vector<int> wg_host;   // the table's groups (host copy of pop.wg_set), from which every partition is derived
+        int* ent = nullptr;         // device: lane groups in stable order by (set, group)
+        int* wg = nullptr;          // device: int4 per workgroup {first entry, entries, rank in its set, workgroups of its set}
+        int* seg = nullptr;         // device: int2 per set {first workgroup, workgroups}
+        int t_steps = 0, n_wg = 0;  // what wg / seg were built for (0: not built)
+    } pp;
     std::vector<int> pol_map;     // the policy packer's index map: packed slot -> source index of the parameter vector, -1 zero
     int64_t pol_n_params = 0;     // ... and the parameter count of the policy of the last vs_set_policy_fnn / vs_set_policy_rnn
     int policy_shape = -1;        // vs_set_policy_shape: -1 automatic, 0 / 1: k_rollout_fnn in 64- / 256-env workgroups, 2: 256-env + matrix cores
@@ -5282,6 +5421,7 @@ struct Launch {
     static void rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_fnn
     static void rollout_vjp_rnn(vs_env* h, const Vjp& v, const float* g_act, const float* g_hid_last, float* d_hid, float* d_hid0,
                                 int t_steps);                                               // vs_rollout_vjp_rnn
+    static void rollout_vjp_pop(vs_env* h, const Vjp& v, const float* g_act, int t_steps);  // vs_rollout_vjp_pop (linear or network slot)
     static int variant(vs_env* h);  // RolloutVariant vs_step_random would launch for the handle's configuration
     static void jac(vs_env* h, const float* act, long es, long ds);
     static void set_params(vs_env* h, const float* src, long pitch, int bcast, const uint8_t* mask);
@@ -5586,6 +5726,21 @@ void Launch<E>::rollout_vjp_fnn(vs_env* h, const Vjp& v, const float* g_act, int
                                h->d, v, g_act, h->fnn, t_steps);
         else no_kernel("rollout_vjp_fnn");
     });
+}
+
+template <class E>
+void Launch<E>::rollout_vjp_pop(vs_env* h, const Vjp& v, const float* g_act, int t_steps) {
+    // the grids of rollout_vjp_lin / rollout_vjp_fnn: a workgroup per aligned group of 64 lanes, which is one group of the population
+    if constexpr (!std::is_same<E, BobD>::value) {
+        if (h->lin.w)
+            hipLaunchKernelGGL((k_rollout_vjp_lin<E, Pop>), dim3((unsigned)(h->d.ld / 64)), dim3(64), 0, h->stream, h->task, h->d, v, g_act,
+                               h->lin, t_steps, h->pop);
+        else
+            with_int<1, 2>(h->fnn.n_hidden, [&](auto NH) __attribute__((always_inline)) {
+                hipLaunchKernelGGL((k_rollout_vjp_fnn<E, NH, Pop>), dim3((unsigned)(h->d.ld / 64)), dim3(64 * FNNB_WAVES), 0, h->stream,
+                                   h->task, h->d, v, g_act, h->fnn, t_steps, h->pop);
+            });
+    } else no_kernel("rollout_vjp_pop");
 }
 
 template <class E>

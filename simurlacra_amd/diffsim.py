@@ -21,6 +21,9 @@ gradient of the policy's parameters.  DifferentiableNetRollout is the same for a
 DifferentiableRecurrentRollout is the form for RNNPolicy / GRUPolicy / LSTMPolicy (vs_set_policy_rnn, vs_rollout_vjp_rnn,
 k_rollout_vjp_rnn): the sweep carries a second adjoint for the policy's hidden state, and the parameter pass is one batched
 single-step pass over the recorded observations and hidden states.
+DifferentiablePopulationRollout runs a POPULATION of linear policies or networks on handles with a policy population
+(vs_set_policy_population): one gradient row per member from one sweep (vs_rollout_vjp_pop) and one device parameter pass
+(vs_pop_param_grad) per batch.
 """
 from typing import Optional, Sequence
 
@@ -586,6 +589,173 @@ class DifferentiableRecurrentRollout(_ClosedLoopRollout):
                 total = g if total is None else tuple(a + b for a, b in zip(total, g))
             n0 += d_hid.shape[0]
         return total
+
+
+def population_lanes(n_members: int, n_rollouts: int):
+    """The lanes of a population of n_members members with n_rollouts rollouts each: every member takes whole groups of 64 lanes.
+    Returns (src, real, lane_set) as int64 / bool / int32 numpy arrays over the n_members * 64 * ceil(n_rollouts / 64) lanes:
+    src[l] the flat rollout index (member * n_rollouts + rollout) lane l runs -- the padding lanes of a member's last group repeat
+    its last rollout --, real[l] whether the lane IS that rollout (padding lanes get zero cotangents), lane_set[l] its member."""
+    import numpy as np
+
+    per = -(-int(n_rollouts) // 64) * 64
+    j = np.tile(np.arange(per, dtype=np.int64), int(n_members))
+    member = np.repeat(np.arange(int(n_members), dtype=np.int64), per)
+    return member * int(n_rollouts) + np.minimum(j, int(n_rollouts) - 1), j < int(n_rollouts), member.astype(np.int32)
+
+
+class DifferentiablePopulationRollout(_RecordedBatches):
+    """roll = DifferentiablePopulationRollout(env, policy);  obs, rew, act, lengths = roll.roll(params, init_states, T)
+
+    The closed-loop rollouts of a POPULATION of policies of one architecture, attached to torch autograd: one gradient per member
+    from the same launches (SVPG-style particles, ensembles, multi-start backpropagation through time).  policy gives the
+    architecture only -- a LinearPolicy on a stack that linear_kernel_spec accepts, or an FNN / FNNPolicy of one or two hidden layers
+    that fnn_kernel_spec accepts, optionally inside a NormalActNoiseExplStrat whose noise is a constant of the sweep; another policy
+    raises TypeErr, one the kernel cannot take ValueErr.  The weights come with the call: params [P, n_params] float32, row s in the
+    order of the policy's setter (net.weight flattened, or parameters_to_vector), and init_states [P, M, S].  Returns obs
+    [P, M, T + 1, O], rew [P, M, T], act [P, M, T, A] and lengths [P, M]; obs, rew and act carry gradients to params and init_states.
+    Every member takes whole groups of 64 lanes of a handle with a policy population (set_policy_population); the padding lanes of
+    its last group repeat its last initial state and get zero cotangents, so they add exact zeros.  More than batch_lanes lanes run
+    in batches that split on group boundaries; a member may span batches.  Backward: per batch one rollout_vjp_population and one
+    population_param_grad straight on its action adjoints -- the first batch writes the [P, n_params] gradient (zeros for members it
+    does not hold), later batches add to it; no [N, T, .] copy of observations or adjoints is made.  Deterministic: backward() twice
+    returns the same bits.  Recurrent policies are not taken (vs_rollout_vjp_pop refuses them), and the std of the noise gets no
+    gradient here."""
+
+    def __init__(self, env, policy, batch_lanes: int = 65536):
+        from .policies import FNN, FNNPolicy, LinearPolicy, NormalActNoiseExplStrat, fnn_kernel_spec, linear_kernel_spec
+
+        inner = policy.policy if isinstance(policy, NormalActNoiseExplStrat) else policy
+        if isinstance(inner, LinearPolicy):
+            spec = linear_kernel_spec(policy)
+            if spec is None:
+                raise ValueErr(msg=f"the rollout kernel cannot evaluate {inner.features}")
+            terms = spec["terms"]
+            self._install = lambda v, flat, std: v.set_policy_linear(flat, terms, noise_std=std)
+            self._spec_of = linear_kernel_spec
+            dims = inner.env_spec.obs_space.flat_dim, inner.env_spec.act_space.flat_dim
+        elif isinstance(inner, (FNN, FNNPolicy)):
+            spec = fnn_kernel_spec(policy)
+            if spec is None:
+                raise ValueErr(msg="the rollout kernel cannot evaluate this network: hidden layers of at most 64 units, tanh / relu / "
+                                   "sigmoid / no nonlinearities, no dropout")
+            if len(spec["hidden_sizes"]) > 2:
+                raise ValueErr(msg=f"the closed-loop sweep takes one or two hidden layers, got {len(spec['hidden_sizes'])}")
+            arch = {k: spec[k] for k in ("hidden_sizes", "hidden_nonlin", "output_nonlin", "feat")}
+            self._install = lambda v, flat, std: v.set_policy_fnn(flat, noise_std=std, **arch)
+            self._spec_of = fnn_kernel_spec
+            net = inner.net if isinstance(inner, FNNPolicy) else inner
+            dims = net.hidden_layers[0].in_features - (1 if spec["feat"] else 0), net.output_layer.out_features
+        else:
+            raise TypeErr(msg="DifferentiablePopulationRollout takes a LinearPolicy, an FNN or an FNNPolicy, optionally inside a "
+                              f"NormalActNoiseExplStrat, got {type(inner).__name__}")
+        if batch_lanes < 64:
+            raise ValueErr(given=batch_lanes, ge_constraint="64")
+        super().__init__(env, "DifferentiablePopulationRollout", batch_lanes // 64 * 64)  # (batches split on group boundaries)
+        A, _, O = self._dims()
+        if dims != (O, A):
+            raise ShapeErr(msg=f"the policy maps {dims[0]} observation rows to {dims[1]} actions, the env has {O} and {A}")
+        self.policy = policy
+        self.n_params = sum(p.numel() for p in inner.parameters())
+
+    def roll(self, params, init_states, T, noise_seed: int = 0):
+        _, S, _ = self._dims()
+        if not hasattr(params, "dim") or not hasattr(init_states, "dim"):
+            raise TypeErr(msg="params and init_states must be torch tensors")
+        if params.dim() != 2 or params.shape[0] < 1 or params.shape[1] != self.n_params:
+            raise ShapeErr(msg=f"params must be [P, {self.n_params}], got shape {tuple(params.shape)}")
+        if init_states.dim() != 3 or init_states.shape[0] != params.shape[0] or init_states.shape[1] < 1 or init_states.shape[2] != S:
+            raise ShapeErr(msg=f"init_states must be [{params.shape[0]}, M, {S}], got shape {tuple(init_states.shape)}")
+        if int(T) < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        for name, x in (("params", params), ("init_states", init_states)):
+            if not x.is_cuda or x.dtype != torch.float32:
+                raise TypeErr(msg=f"{name} must be a float32 tensor on the GPU")
+        self._calls += 1
+        setup = (self, self._calls, int(T), self._spec_of(self.policy)["noise_std"], int(noise_seed))
+        return tuple(_PopulationRolloutFn.apply(setup, params, init_states))
+
+    __call__ = roll
+
+    def _record(self, b, setup, l0, l1, lanes, params, init_flat):
+        _, call, T, noise_std, noise_seed = setup
+        src, _, lane_set = lanes
+
+        def launch(v):
+            v.set_index_offset(0)
+            v.set_params(domain_param_matrix(self._base, [dict()] * (l1 - l0)))
+            flat = params.detach().contiguous()
+            self._install(v, flat[0], noise_std)
+            v.set_policy_population(flat, lane_set=lane_set[l0:l1])
+            v.reset(init_state=init_flat[torch.as_tensor(src[l0:l1], device=init_flat.device)].cpu().numpy())
+            v.set_traj_offset(0)
+            v.step_policy(T, record=True, noise_seed=noise_seed)
+
+        return self._recorded(b, (call, b), l1 - l0, launch)
+
+    def _forward(self, setup, params, init_states):
+        A, S, O = self._dims()
+        (P, M), T, dev = init_states.shape[:2], setup[2], init_states.device
+        lanes = population_lanes(P, M)
+        init_flat = init_states.reshape(P * M, S)
+        obs = torch.empty(P * M, T + 1, O, dtype=torch.float32, device=dev)
+        rew = torch.empty(P * M, T, dtype=torch.float32, device=dev)
+        act = torch.empty(P * M, T, A, dtype=torch.float32, device=dev)
+        lengths = torch.empty(P * M, dtype=torch.int64, device=dev)
+        for b, (l0, l1) in enumerate(self._batches(len(lanes[0]))):
+            n = l1 - l0
+            v = self._record(b, setup, l0, l1, lanes, params, init_flat)
+            at = torch.as_tensor(lanes[1][l0:l1].nonzero()[0], device=dev)   # the batch's lanes that are rollouts ...
+            to = torch.as_tensor(lanes[0][l0:l1][lanes[1][l0:l1]], device=dev)  # ... and which ones
+            with v.on_current_stream():
+                tt = v.traj_tensors(T, n)
+                lengths[to] = v.rollout_lengths(n, T)[0][at]
+                obs[to, :T] = tt["obs"].transpose(0, 1)[at]
+                obs[to, T] = v.tensor(L.VS_OBS)[:, :n].t()[at]
+                rew[to] = tt["rew"].t()[at]
+                act[to] = tt["act"].transpose(0, 1)[at]
+        steps = torch.arange(T + 1, device=dev)
+        inside = (steps[None, :T] < lengths[:, None]).to(torch.float32)
+        obs = obs * (steps[None, :] <= lengths[:, None]).to(obs.dtype)[:, :, None]
+        return (obs.view(P, M, T + 1, O), (rew * inside).view(P, M, T), (act * inside[:, :, None]).view(P, M, T, A), lengths.view(P, M))
+
+    def _backward(self, setup, params, init_states, grad_obs, grad_rew, grad_act):
+        """(d params [P, n_params], d init_states [P, M, S])"""
+        A, S, O = self._dims()
+        (P, M), T, dev = init_states.shape[:2], setup[2], init_states.device
+        lanes = population_lanes(P, M)
+        init_flat = init_states.reshape(P * M, S)
+        d_init = torch.empty(P * M, S, dtype=torch.float32, device=dev)
+        grads = [None if g is None else g.reshape((P * M,) + tuple(g.shape[2:])).to(torch.float32) for g in (grad_rew, grad_obs, grad_act)]
+        d_params = None
+        for b, (l0, l1) in enumerate(self._batches(len(lanes[0]))):
+            n = l1 - l0
+            v = self._record(b, setup, l0, l1, lanes, params, init_flat)
+            src = torch.as_tensor(lanes[0][l0:l1], device=dev)
+            real = torch.as_tensor(lanes[1][l0:l1], device=dev)
+            with v.on_current_stream():
+                # the batch's cotangents, lanes last; a padding lane gets zeros: its sweep and its rows of the parameter pass are 0
+                g = [None if x is None else lanes_last(x[src] * real.view((n,) + (1,) * (x.dim() - 1)).to(x.dtype), v.ld) for x in grads]
+                da, di = v.rollout_vjp_population(T, g_rew=g[0], g_obs=g[1], g_act=g[2])
+                d_init[src[real]] = lanes_first(di[:S], n)[real]
+                d_params = v.population_param_grad(T, da, out=d_params, accumulate=d_params is not None)
+        return d_params, d_init.view(P, M, S)
+
+
+class _PopulationRolloutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, setup, params, init_states):
+        obs, rew, act, lengths = setup[0]._forward(setup, params.detach(), init_states.detach())
+        ctx.setup = setup
+        ctx.save_for_backward(params, init_states)
+        ctx.mark_non_differentiable(lengths)
+        return obs, rew, act, lengths
+
+    @staticmethod
+    def backward(ctx, grad_obs, grad_rew, grad_act, _grad_lengths):
+        params, init_states = ctx.saved_tensors
+        d_params, d_init = ctx.setup[0]._backward(ctx.setup, params.detach(), init_states.detach(), grad_obs, grad_rew, grad_act)
+        return None, d_params.clone(), d_init
 
 
 class _PolicyRolloutFn(torch.autograd.Function):

@@ -603,6 +603,7 @@ class VecSimEnv:
         noise_std: exploration noise per action dimension.  params=None removes the network."""
         self._rnn_hs = 0  # (a network replaces a recurrent policy)
         self._fnn_n_params = self._lin_n_params = 0
+        self._pop_shape = None  # (every policy setter drops the population with the policy it was set for)
         if params is None:
             self._check(self._lib.vs_set_policy_fnn(self._h, None, None, 0), "vs_set_policy_fnn")
             return
@@ -633,6 +634,7 @@ class VecSimEnv:
         'lstm'; obs_idx / noise_std as in set_policy_fnn.  Zeroes the running hidden state (policy_hidden()).  params=None
         removes the policy."""
         self._lin_n_params = 0  # (a recurrent policy replaces a linear one)
+        self._pop_shape = None
         if params is None:
             self._check(self._lib.vs_set_policy_rnn(self._h, None, None, 0), "vs_set_policy_rnn")
             self._rnn_hs = 0
@@ -663,6 +665,7 @@ class VecSimEnv:
         as in set_policy_fnn.  params=None removes the policy."""
         self._rnn_hs = 0  # (a linear policy replaces a recurrent one)
         self._lin_n_params = 0
+        self._pop_shape = None
         if params is None:
             self._check(self._lib.vs_set_policy_linear(self._h, None, None, 0), "vs_set_policy_linear")
             return
@@ -707,6 +710,7 @@ class VecSimEnv:
         replays (index offset + i) % n_rec).  The row is the env's own step counter.  actions=None removes the policy."""
         self._rnn_hs = 0  # (a playback policy replaces a recurrent one)
         self._lin_n_params = 0
+        self._pop_shape = None
         if actions is None:
             self._check(self._lib.vs_set_policy_playback(self._h, None, 0, 0, None, None), "vs_set_policy_playback")
             return
@@ -798,6 +802,7 @@ class VecSimEnv:
         policy of the last set_policy_fnn / set_policy_rnn / set_policy_linear, each in that call's torch order; a torch tensor (host or device) or
         an array -- and lane_set [n_envs] the set every lane runs (-1: the lane takes no part; every aligned group of 64 lanes
         names one set).  params=None removes the population."""
+        self._pop_shape = None
         if params is None:
             self._check(self._lib.vs_set_policy_population(self._h, None, 0, 0, None), "vs_set_policy_population")
             return
@@ -809,6 +814,7 @@ class VecSimEnv:
             raise ShapeErr(msg=f"lane_set needs one entry per env ({self.n_envs}), got {ls.size}")
         self._check(self._lib.vs_set_policy_population(self._h, C.c_void_p(ptr), int(shape[1]), int(shape[0]),
                                                        ls.ctypes.data_as(C.c_void_p)), "vs_set_policy_population")
+        self._pop_shape = (int(shape[0]), int(shape[1]))  # (what population_param_grad returns)
 
     def set_policy_hidden_record(self, width):
         """Record the policy's hidden state before every recorded step (width floats per env; 0 = off)"""
@@ -986,6 +992,43 @@ class VecSimEnv:
         if not n_params:
             raise ValueErr(msg="no feed-forward network set (set_policy_fnn)")
         return self._param_grad("vs_fnn_param_grad", t_steps, (("abar", abar, self.dims["A"]),), n_params, out, accumulate)
+
+    def rollout_vjp_population(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None):
+        """rollout_vjp_policy / rollout_vjp_fnn for records made with a policy population on the handle (set_policy_population over a
+        linear policy or a network of one or two hidden layers; vs_rollout_vjp_pop): every lane's sweep runs with the weights of the
+        set its group of 64 lanes names.  Same cotangents, same returns; the lanes of an inert group (set -1) get zeros."""
+        return self._closed_loop_vjp("vs_rollout_vjp_pop", t_steps, g_rew, g_obs, g_act, g_state_last)
+
+    def population_param_grad(self, t_steps, abar, out=None, accumulate=False):
+        """The parameter gradients that go with rollout_vjp_population, one row per member, in one device pass over the same records
+        (vs_pop_param_grad): row s sums the rows t < L of the lanes whose group names set s.  abar [t_steps, A, ld] is
+        rollout_vjp_population's d_act as returned; what it holds behind a lane's end, at lanes >= n_envs and in inert groups is never
+        read.  Returns float32 [n_sets, n_params], each row in the order of the policy's setter: a new tensor, or `out`, to which
+        accumulate=True adds instead of overwriting.  A set that no group names gets zeros (accumulate: is left as it was).
+        Deterministic: two calls on the same inputs return the same bits."""
+        import torch
+
+        shape = getattr(self, "_pop_shape", None)
+        if not shape:
+            raise ValueErr(msg="no policy population set (set_policy_population)")
+        T, A = int(t_steps), self.dims["A"]
+        if T < 1:
+            raise ValueErr(given=T, ge_constraint="1")
+        if not hasattr(abar, "data_ptr") or not abar.is_cuda or abar.dtype != torch.float32 or not abar.is_contiguous():
+            raise TypeErr(msg="abar must be a contiguous float32 tensor on the GPU")
+        if tuple(abar.shape) != (T, A, self.ld):
+            raise ShapeErr(msg=f"abar must be {(T, A, self.ld)}, got {tuple(abar.shape)}")
+        if out is None:
+            if accumulate:
+                raise ValueErr(msg="accumulate=True needs the tensor to add to (out)")
+            out = torch.empty(shape, dtype=torch.float32, device=abar.device)
+        elif not hasattr(out, "data_ptr") or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeErr(msg="out must be a contiguous float32 tensor on the GPU")
+        elif tuple(out.shape) != shape:
+            raise ShapeErr(msg=f"out must be {shape}, got {tuple(out.shape)}")
+        self._check(self._lib.vs_pop_param_grad(self._h, T, C.c_void_p(abar.data_ptr()), C.c_void_p(out.data_ptr()), shape[0], shape[1],
+                                                int(bool(accumulate))), "vs_pop_param_grad")
+        return out
 
     def rollout_vjp_rnn(self, t_steps, g_rew=None, g_obs=None, g_act=None, g_state_last=None, g_hid_last=None):
         """rollout_vjp_policy for records made with the recurrent policy of set_policy_rnn that is still on the handle, with the
